@@ -2,7 +2,7 @@
 """bench.py — the hot path on MI355X: Nedelec p=3 curl-curl `ParOperator::Mult` throughput and PCG
 iterations/s on a ~10M-dof cylinder cavity (BASELINE.json metric), one JSON line on rank 0.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
   (N > 1: launched by torch.distributed.run, one rank per GPU, RCCL over xGMI)
 
 A "step" is one `ParOperator::Mult` (BC masking + P + fused E-B-D-B^T-E^T kernel + P^T) of the
@@ -66,7 +66,37 @@ def parse():
                          "with \"rehearsal\": true.  Timings are those of N ranks sharing one GPU, not a scaling result.")
     ap.add_argument("--no-nranks-legs", action="store_true", help="N > 1: skip the order-4 and tetrahedral legs")
     ap.add_argument("--no-traffic", action="store_true", help="skip the rocprofv3 --pmc child processes that measure roofline.traffic")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float64, at most 64 MB in all: a larger output "
+                         "is cut to a fixed seeded sample), so that two builds can be compared output for output")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_BYTES = 60 << 20  # (--dump-outputs: 60 MiB of data, headroom for the .npy headers under 64 MB)
+
+
+def dump_outputs(dirname, arrays, budget):
+    """--dump-outputs: every device array of `arrays` as dirname/<name>.npy in float64.  An array larger than its share of `budget`
+    bytes is replaced by the entries at a fixed sample of positions (sorted, drawn with seed 0), the same in every run with the
+    same arguments.  Returns what was written, for the result line."""
+    import torch
+
+    os.makedirs(dirname, exist_ok=True)
+    cap = budget // len(arrays) // 8
+    info = {}
+    for name, a in arrays.items():
+        a = a.reshape(-1)
+        n = a.numel()
+        if n > cap:
+            idx = np.sort(np.random.default_rng(0).permutation(n)[:cap])
+            a = a[torch.from_numpy(idx).to(a.device)]
+        np.save(os.path.join(dirname, name + ".npy"), a.to(torch.float64).cpu().numpy())
+        info[name] = {"entries": int(a.numel()), "of": int(n), "dtype": "float64",
+                      "sample": "sorted positions of np.random.default_rng(0).permutation(of)[:entries]" if n > cap else None}
+    return {"dir": os.path.abspath(dirname), "arrays": info}
 
 
 def rehearse(args):
@@ -218,10 +248,8 @@ def main():
         torch.cuda.synchronize()
 
     # ---- M1: ParOperator::Mult throughput --------------------------------------------------------
-    # W untimed warm-up steps, then blocks of EXACTLY K steps between barrier + synchronize; a K-step block shorter than
-    # 100 ms (the driver's --steps 20 is 3 ms of device work) is repeated back to back inside one bracket until the timed
-    # window is >= 100 ms, so that `value` is not a statement about one clock state (round-4 review): value = dofs x
-    # (blocks x K) / elapsed, ms_per_step = elapsed / (blocks x K); `timed_blocks` is in the line.
+    # W untimed warm-up steps, then EXACTLY K timed steps between barrier + synchronize: value = dofs x K / elapsed,
+    # ms_per_step = elapsed / K.  A window long enough to say more than one clock state is the caller's choice of K.
     for _ in range(args.warmup):
         K.mult(x, y)
     barrier()
@@ -229,26 +257,16 @@ def main():
     for _ in range(args.steps):
         K.mult(x, y)
     barrier()
-    probe = time.perf_counter() - t0
-    if world > 1:
-        t = torch.tensor([probe], dtype=torch.float64, device=cdev)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        probe = float(t.item())
-    blocks = 1 if probe >= 0.1 else int(min(10000, np.ceil(0.1 / max(probe, 1e-6))))
-    barrier()
-    t0 = time.perf_counter()
-    for _ in range(blocks):
-        for _ in range(args.steps):
-            K.mult(x, y)
-    barrier()
     elapsed = time.perf_counter() - t0
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=cdev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-    ms_per_step = 1e3 * elapsed / (args.steps * blocks)
-    value = n_global * args.steps * blocks / elapsed
-    first_block_ms_per_step = 1e3 * probe / args.steps
+    ms_per_step = 1e3 * elapsed / args.steps
+    value = n_global * args.steps / elapsed
+    dumped = None
+    if args.dump_outputs:  # y of the last timed step (each rank its own slab of true dofs)
+        dumped = dump_outputs(args.dump_outputs, {"y" if world == 1 else f"y_rank{rank}": y}, DUMP_BYTES // world)
 
     # ---- roofline of the dominant kernel (fused apply), HIP events on the launch stream -----------
     local_op = prob.local_curlcurl
@@ -506,7 +524,7 @@ def main():
         out = {
             "metric": "curl-curl Mult DOF/s + PCG iters/s, p=3 H(curl) 10M DOF @1/2/4/8 GPU",
             "value": value, "unit": "DOF/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": ms_per_step, "timed_blocks": blocks, "first_block_ms_per_step": first_block_ms_per_step,
+            "ms_per_step": ms_per_step, "dump_outputs": dumped,
             "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None,
             "dtype": "f64", "data": "synthetic",
             "config": {"workload": f"ND p={p} curl-curl ParOperator::Mult, O-grid cylinder cavity (hex27, PEC), "

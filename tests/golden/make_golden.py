@@ -331,7 +331,43 @@ def cpw_fixture():
     print("wrote cpw_mesh.npz", m.tets.shape, m.verts.shape, np.unique(m.attr), np.unique(m.bdr_attr))
 
 
+def fixtures_live():
+    """The draws of tests/test_oracle_ref.py::test_live_reference_library (seed 11: geometry factor + hdiv_33) and
+    tests/test_oracle_rest.py::test_live_reference_headers_when_present (seed 7: geometry factor + hdiv of 32 | 31 | 21, the
+    coefficients of qf_rest_golden.npz) with the reference headers' results, so that both checks run without the reference."""
+    from tests.test_oracle_rest import _cm
+
+    capi.build(ref=True)
+    rng = np.random.default_rng(11)
+    Q = 27
+    J = np.eye(3).reshape(9, 1) + 0.2 * rng.uniform(-1, 1, (9, Q))
+    qw = rng.uniform(0.1, 1, Q)
+    geom = np.zeros((11, Q))
+    capi.ref_call("f_build_geom_factor_33", None, Q, [np.ones(Q), qw, np.ascontiguousarray(J)], [geom])
+    ctx = po.CoeffCtx(attr_mat=[0], mat_coeff=[rng.uniform(-1, 1, (3, 3)) + 2 * np.eye(3)])
+    u = rng.uniform(-1, 1, (3, Q))
+    v = np.zeros((3, Q))
+    capi.ref_call("f_apply_hdiv_33", ctx.pack(), Q, [geom, u], [v])
+    out = dict(J33=J, qw33=qw, geom33=geom, ctx33=ctx.pack(), u33=u, hdiv_33=v)
+    rng = np.random.default_rng(7)
+    Q = 16
+    attr, qw = rng.integers(1, 3, Q).astype(np.float64), rng.uniform(0.01, 0.2, Q)
+    out.update(attr=attr, qw=qw)
+    for tag in (32, 31, 21):
+        sdim, dim = tag // 10, tag % 10
+        J = rng.uniform(-1, 1, (sdim * dim, Q)) + np.array([1, 0, 0, 0, 1, 0.3, 0, 0, 1][: sdim * dim]).reshape(-1, 1)
+        g = np.zeros((2 + sdim * dim, Q))
+        capi.ref_call("f_build_geom_factor_%d" % tag, None, Q, [attr, qw, np.ascontiguousarray(J)], [g])
+        u = rng.uniform(-1, 1, (dim, Q))
+        v = np.zeros((dim, Q))
+        capi.ref_call("f_apply_hdiv_%d" % tag, _cm(tag).pack(), Q, [g, u], [v])
+        out.update({"J%d" % tag: J, "geom%d" % tag: g, "u%d" % tag: u, "hdiv_%d" % tag: v})
+    np.savez(os.path.join(ROOT, "tests", "golden", "qf_live_golden.npz"), **out)
+    print("wrote qf_live_golden.npz")
+
+
 if __name__ == "__main__":
+    fixtures_live()
     mesh_fixture()
     fixtures_2d()
     fixtures_line()

@@ -11,6 +11,7 @@ torch = pytest.importorskip("torch")
 from palace_amd import ceed, linalg  # noqa: E402
 from palace_amd.fem.fespace import H1HexSpace, NDHexSpace, lowest_order_gradient, vertex_coordinates  # noqa: E402
 from palace_amd.fem.mesh import ogrid_cylinder  # noqa: E402
+from palace_amd.lib import PalaceAmdError  # noqa: E402
 from oracle import palace_oracle as po  # noqa: E402
 
 
@@ -178,7 +179,9 @@ def test_cycles_with_the_steps_in_the_sparse_products_epilogues(problem, monkeyp
 @pytest.mark.parametrize("policy", ["one", "zero"])
 def test_chebyshev_on_an_assembled_operator_with_the_step_in_the_sparse_product(problem, monkeypatch, policy):
     """ChebyshevSmoother over ParOperator(CsrOperator) -- the level-0 smoother of the bench's plain p-multigrid: the step in the
-    product's epilogue against product + vector kernel, zero and non-zero initial guess."""
+    product's epilogue against product + vector kernel, zero and non-zero initial guess.  The Jacobi scaling needs the unit
+    diagonal on the essential rows: over the zero-diagonal policy the set-up, fused or not, refuses instead of smoothing with
+    infinite weights."""
     nd, geom = problem["nd"], problem["geom"]
     op = ceed.curlcurlmass_operator(geom, nd, problem["mass"], problem["ident"])
     ess = nd.ess_dofs()
@@ -187,7 +190,14 @@ def test_chebyshev_on_an_assembled_operator_with_the_step_in_the_sparse_product(
     pol = linalg.DIAG_ONE if policy == "one" else linalg.DIAG_ZERO
     A = linalg.AssembledParOperator(ctx, csr, ess, pol)
     if policy == "zero":
-        pytest.skip("a Jacobi-scaled smoother needs the unit diagonal on the essential rows")
+        d = torch.empty(nd.ndofs, dtype=torch.float64, device="cuda")
+        A.assemble_diagonal(d)
+        assert ess.size > 0 and not d[_dev(ess).long()].any()
+        for form in ("1", "0"):
+            monkeypatch.setenv("PALACE_AMD_FUSED_STEP_CSR", form)
+            with pytest.raises(PalaceAmdError):  # (its spectral estimate meets the infinite weights first)
+                linalg.chebyshev(ctx, A, order=4)
+        return
     S = linalg.chebyshev(ctx, A, order=4)
     assert S.fused_step()
     monkeypatch.setenv("PALACE_AMD_FUSED_STEP_CSR", "0")

@@ -5,9 +5,9 @@ P / P^T around it (rap.cpp:195-234) on real communicators.
   ("ghosts") with g owned dofs, so y = P^T A P x can be checked against the same product formed with numpy index
   operations around the local operator.  Runs in a subprocess with a time limit: an RCCL build that cannot send to itself
   is reported as a skip, not a hang.
-* two or more GPUs (skipped on the one-GPU boxes): two processes, one per GPU, RCCL bootstrapped through
-  torch.distributed (gloo store) -- the slab partition of palace_amd/fem/partition.py on the device, ParOperator applies,
-  global dot products and the PCG + p-multigrid solve compared with the undivided cylinder on one GPU."""
+* two processes, one per GPU with RCCL bootstrapped through torch.distributed (gloo store), or both on the one GPU over the
+  peer transport where there is only one -- the slab partition of palace_amd/fem/partition.py on the device, ParOperator
+  applies, global dot products and the PCG + p-multigrid solve compared with the undivided cylinder on one GPU."""
 import os
 import subprocess
 import sys
@@ -94,30 +94,35 @@ def test_halo_self_neighbour_one_gpu(p):
     assert _self_halo(p, False, inplace=False) == b
 
 
-def _worker(rank, world, port, out):
+def _worker(rank, world, port, out, rccl):
     import torch
     import torch.distributed as dist
 
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), HSA_ENABLE_IPC_MODE_LEGACY="0")
-    torch.cuda.set_device(rank)
-    dist.init_process_group("gloo", rank=rank, world_size=world)  # bootstrap only: the data path is RCCL inside the library
+    torch.cuda.set_device(rank if rccl else 0)
+    dist.init_process_group("gloo", rank=rank, world_size=world)  # bootstrap only: the data path is inside the library
     try:
         from palace_amd import linalg
+        from palace_amd import lib as _lib
         from palace_amd.fem.partition import SlabProblem
 
         ctx = linalg.Context()
-        # the RCCL unique id travels over the gloo group
-        import ctypes as C
-        from palace_amd import lib as _lib
-        L = _lib.load()
-        buf = C.create_string_buffer(128)
-        if rank == 0:
-            _lib.check(L.pa_comm_unique_id(buf))
-        t = torch.frombuffer(bytearray(buf.raw), dtype=torch.uint8)
-        dist.broadcast(t, src=0)
-        _lib.check(L.pa_context_init_comm(ctx.handle, rank, world, bytes(t.numpy().tobytes())))
-        ctx.rank, ctx.size = rank, world
+        if rccl:
+            # the RCCL unique id travels over the gloo group
+            import ctypes as C
+            L = _lib.load()
+            buf = C.create_string_buffer(128)
+            if rank == 0:
+                _lib.check(L.pa_comm_unique_id(buf))
+            t = torch.frombuffer(bytearray(buf.raw), dtype=torch.uint8)
+            dist.broadcast(t, src=0)
+            _lib.check(L.pa_context_init_comm(ctx.handle, rank, world, bytes(t.numpy().tobytes())))
+            ctx.rank, ctx.size = rank, world
+        elif world > 1:
+            ctx.init_comm_peer_from_torch_distributed()
         prob = SlabProblem(ctx, rank, world, 2, 0, shape=(2, 4 // world))
+        if world > 1:
+            assert all(bool(_lib.load().pa_halo_uses_peer(h.handle)) != rccl for h in prob.halos)
         K, b, x = prob.pcg_gmg_solver(max_it=100, rel_tol=1e-8, hiptmair=True, coarse="cg")
         K.mult(b, x)
         st = K.stats()
@@ -134,16 +139,17 @@ def _worker(rank, world, port, out):
 
 
 def test_two_rank_rccl_halo_matches_one_rank():
+    """Two ranks, one per GPU, over RCCL.  RCCL refuses two ranks of one communicator on the same device, so on a one-GPU machine
+    the two processes share the device and exchange over the library's peer transport (the halo path the library takes there)."""
     import torch
 
-    if torch.cuda.device_count() < 2:
-        pytest.skip("needs two GPUs")
+    rccl = torch.cuda.device_count() >= 2
     import torch.multiprocessing as mp
 
     results = {}
     for world, port in ((1, 29611), (2, 29612)):
         q = mp.get_context("spawn").SimpleQueue()
-        mp.spawn(_worker, args=(world, port, q), nprocs=world, join=True)
+        mp.spawn(_worker, args=(world, port, q, rccl), nprocs=world, join=True)
         results[world] = q.get()
     one, two = results[1], results[2]
     assert one["n"] == two["n"] and one["converged"] and two["converged"]

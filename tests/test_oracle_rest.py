@@ -1,7 +1,7 @@
 """The members of the `32 | 31 | 21` QFunction families no integrator of the hot path's callers uses, and the div-div + mass and
 gradient forms (fem/qfunctions/{32,31,21}/hdiv_*, hcurlhdiv_*, fem/qfunctions/*/l2mass_*,
 hcurlh1d_*): the oracle's restatements against vectors the reference's own headers produced (tests/golden/make_golden.py::
-fixtures_rest, oracle/ref_shim.cpp), and -- when the reference tree is here -- against the compiled headers directly."""
+fixtures_rest, oracle/ref_shim.cpp), and -- when oracle/_ref is built -- against the compiled headers directly."""
 import os
 
 import numpy as np
@@ -10,6 +10,7 @@ import pytest
 from oracle import palace_oracle as po
 
 G = np.load(os.path.join(os.path.dirname(__file__), "golden", "qf_rest_golden.npz"))
+L = np.load(os.path.join(os.path.dirname(__file__), "golden", "qf_live_golden.npz"))
 TOL = dict(rtol=1e-12, atol=1e-13)
 
 
@@ -62,22 +63,20 @@ def test_vector_valued_scalar_spaces(n):
 
 
 def test_live_reference_headers_when_present():
-    """The same functions against oracle/_ref (the reference's headers compiled in place) on fresh random draws."""
+    """Fresh draws of the same functions with the reference headers' results (tests/golden/qf_live_golden.npz): the oracle against
+    them, and when oracle/_ref (the reference's headers compiled in place) is built, the headers themselves on the same draws."""
     from oracle import capi
 
-    if not os.path.isdir("/root/reference/palace/fem/qfunctions"):
-        pytest.skip("no reference tree on this machine")
-    capi.build(ref=True)
-    rng = np.random.default_rng(7)
-    Q = 16
-    attr, qw = rng.integers(1, 3, Q).astype(np.float64), rng.uniform(0.01, 0.2, Q)
+    attr, qw = L["attr"], L["qw"]
+    Q = qw.size
     for tag in (32, 31, 21):
         sdim, dim = tag // 10, tag % 10
-        J = rng.uniform(-1, 1, (sdim * dim, Q)) + np.array([1, 0, 0, 0, 1, 0.3, 0, 0, 1][: sdim * dim]).reshape(-1, 1)
-        g = np.zeros((2 + sdim * dim, Q))
-        capi.ref_call("f_build_geom_factor_%d" % tag, None, Q, [attr, qw, np.ascontiguousarray(J)], [g])
-        u = rng.uniform(-1, 1, (dim, Q))
-        v = np.zeros((dim, Q))
-        capi.ref_call("f_apply_hdiv_%d" % tag, _cm(tag).pack(), Q, [g, u], [v])
+        J, g, u, v = L["J%d" % tag], L["geom%d" % tag], L["u%d" % tag], L["hdiv_%d" % tag]
         f = po.apply_hdiv_32 if tag == 32 else po.apply_hdiv_line
         np.testing.assert_allclose(f(_cm(tag), g[None], u[None])[0], v, **TOL)
+        if capi.ref_available():
+            g2, v2 = np.zeros((2 + sdim * dim, Q)), np.zeros((dim, Q))
+            capi.ref_call("f_build_geom_factor_%d" % tag, None, Q, [attr, qw, np.ascontiguousarray(J)], [g2])
+            capi.ref_call("f_apply_hdiv_%d" % tag, _cm(tag).pack(), Q, [g2, u], [v2])
+            np.testing.assert_array_equal(g2, g)
+            np.testing.assert_array_equal(v2, v)
