@@ -227,10 +227,6 @@ Halo::Halo(Comm &comm, int nnbr, const int *nbr, const int *send_off, const int3
   send_off_.assign(send_off, send_off + nnbr + 1);
   recv_off_.assign(recv_off, recv_off + nnbr + 1);
   nsend_ = send_off_[nnbr], nrecv_ = recv_off_[nnbr];
-  iface_.assign(send_idx, send_idx + nsend_);
-  iface_.insert(iface_.end(), recv_idx, recv_idx + nrecv_);
-  std::sort(iface_.begin(), iface_.end());
-  iface_.erase(std::unique(iface_.begin(), iface_.end()), iface_.end());
   send_min_ = recv_min_ = std::numeric_limits<int>::max(), send_max_ = recv_max_ = -1;
   for (int i = 0; i < nsend_; i++) send_min_ = std::min(send_min_, send_idx[i]), send_max_ = std::max(send_max_, send_idx[i]);
   for (int i = 0; i < nrecv_; i++) recv_min_ = std::min(recv_min_, recv_idx[i]), recv_max_ = std::max(recv_max_, recv_idx[i]);
@@ -604,8 +600,6 @@ __global__ __launch_bounds__(256) void k_peer_consume_p(const PeerNbr *__restric
 // order: the result does not depend on arrival times).  FUSED (ParOperator::Mult): the result goes to y with ParOperator's
 // essential rows fixed on the way (rap.cpp:222-233): y[i] = ess ? (x[i] | 0) : ly[i] + contributions, mask bit 1 = essential,
 // bit 2 = the dof has sharers (its row of the contribution lists is found by bisection)
-// MODE 2 (direct form): v = y already holds the local sums of the true dofs (the run gather wrote them, essential rows fixed);
-// the contributions are added in place, essential rows are left alone
 template <int MODE>
 __global__ __launch_bounds__(256) void k_peer_consume_r(const PeerNbr *__restrict__ nb, const int nnbr,
                                                          const PeerLocal *__restrict__ F, PeerCounters *__restrict__ L,
@@ -656,9 +650,7 @@ __global__ __launch_bounds__(256) void k_peer_consume_r(const PeerNbr *__restric
         for (int a = info[j].w; a < rptr[i + 1]; a++) t += ld_sys_f64(&src[rpos[a]]);
       if (FUSED)
         y[d] = (mask[d] & 1) ? (diag_one ? x[d] : 0.0) : t;
-      else if (MODE == 2) {
-        if (!(mask[d] & 1)) v[d] = t;
-      } else
+      else
         v[d] = t;
     }
   }
@@ -669,8 +661,8 @@ __global__ __launch_bounds__(256) void k_peer_consume_r(const PeerNbr *__restric
 
 // (3) P^T of the direct form in ONE kernel: ghost rows (contiguous: the local apply wrote them to GhostOut) into the owners' mailboxes,
 // flags, acknowledgement of this Mult's P messages -- then the same blocks wait for the neighbours' rows and add them to y in place
-// (k_peer_send<0> + k_peer_consume_r<2> behind one launch: at the per-rank sizes of a strong-scaling run a launch costs what
-// the exchange does).  Every block takes part in both phases; the exchange counter is advanced by the block that finishes last,
+// (send and sum behind one launch: at the per-rank sizes of a strong-scaling run a launch costs what the exchange does; the
+// contributions are added to the local sums in y, essential rows are left alone).  Every block takes part in both phases; the exchange counter is advanced by the block that finishes last,
 // after every block has read it.  A block spinning in the second phase waits for OTHER ranks' first phases only, which never wait.
 // STEP: y is read only (this rank's partial sums of the interface dofs) and the completed sum is consumed by the smoother step
 // `st` instead of being stored (Halo::Step)
@@ -1176,10 +1168,11 @@ void Halo::SendDirect(const double *d_x, const uint8_t *d_mask, hipStream_t s) c
   PA_HIP(hipGetLastError());
 }
 namespace {
-bool halo_merged() {
-  static const bool merged = !(std::getenv("PALACE_AMD_HALO_MERGED") && std::getenv("PALACE_AMD_HALO_MERGED")[0] == '0');
-  return merged;
-}
+// Every block of the merged P^T kernel takes part in both phases: a block spinning in the second one waits for the FIRST phase of
+// other ranks' grids, so each grid has to be resident as a whole -- also when the ranks share one device (rehearsals, CU-masked or
+// partitioned devices).  Both loops are grid-stride: the grid is clamped to this rank's share of what the device holds at once
+// (the ranks on THIS device -- one per GPU on the target node, where nothing has to be shared; a rehearsal or a partitioned
+// device puts several on one.  Determined at the plan's set-up, PeerSetup.)
 int restrict_resident_blocks() {
   static const int resident = [] {
     int per_cu = 0, dev = 0;
@@ -1192,7 +1185,7 @@ int restrict_resident_blocks() {
   return resident;
 }
 }  // namespace
-bool Halo::StepOk() const { return peer_ != nullptr && halo_merged(); }
+bool Halo::StepOk() const { return peer_ != nullptr; }
 void Halo::RestrictAddDirectStep(const uint8_t *d_mask, const double *d_t_iface, const Step &st, hipStream_t s) const {
   PA_REQUIRE(StepOk() && d_mask && d_t_iface && st.r0 && (st.mode == 1 ? (st.dinv && st.ek && st.out) : (st.mode == 2 && (st.res || st.out))),
              "halo step: peer transport in its merged form and a complete step expected");
@@ -1207,31 +1200,9 @@ void Halo::RestrictAddDirectStep(const uint8_t *d_mask, const double *d_t_iface,
 void Halo::RestrictAddDirect(const uint8_t *d_mask, double *d_y, hipStream_t s) const {
   const PeerPlan &p = *peer_;
   const int mb = mail_blocks(nrecv_), sb = sum_blocks(p.n_rdof);
-  static const bool merged = !(std::getenv("PALACE_AMD_HALO_MERGED") && std::getenv("PALACE_AMD_HALO_MERGED")[0] == '0');
-  if (merged) {  // one launch for both halves (PALACE_AMD_HALO_MERGED=0: the two kernels of round 3)
-    // Every block of this kernel takes part in both phases: a block spinning in the second one waits for the FIRST phase of other
-    // ranks' grids, so each grid has to be resident as a whole -- also when the ranks share one device (rehearsals, CU-masked or
-    // partitioned devices).  Both loops are grid-stride: clamp the grid to this rank's share of what the device holds at once.
-    static const int resident = [] {
-      int per_cu = 0, dev = 0;
-      hipDeviceProp_t prop{};
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_peer_restrict_direct_t<true>, 256, 0) != hipSuccess || per_cu < 1) per_cu = 1;
-      if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess || prop.multiProcessorCount < 1)
-        prop.multiProcessorCount = 32;
-      return per_cu * prop.multiProcessorCount;
-    }();
-    // (this rank's share: the ranks on THIS device -- one per GPU on the target node, where nothing has to be shared; a
-    // rehearsal or a partitioned device puts several on one.  Determined at the plan's set-up, PeerSetup.)
-    const int cap = std::max(1, resident / std::max(1, p.ranks_on_device));
-    hipLaunchKernelGGL(k_peer_restrict_direct_t<false>, dim3(std::min(cap, std::max(mb, sb))), dim3(256), 0, s, p.d_nbr, p.nnbr, p.local, p.counters, nrecv_,
-                       GhostOut(), p.mb[1], nsend_, d_y, p.n_rdof, p.d_rinfo, p.d_rptr, p.d_rpos, p.d_err, d_mask, Step{});
-    PA_HIP(hipGetLastError());
-    return;
-  }
-  hipLaunchKernelGGL(k_peer_send<0>, dim3(mb), dim3(256), 0, s, p.d_nbr, p.nnbr, p.counters, 1, nrecv_, GhostOut(), nullptr, 0,
-                     nullptr, nullptr, 0, mb, nullptr, nullptr, 1);
-  hipLaunchKernelGGL(k_peer_consume_r<2>, dim3(sb), dim3(256), 0, s, p.d_nbr, p.nnbr, p.local, p.counters, p.mb[1], nsend_, d_y,
-                     p.n_rdof, p.d_rinfo, p.d_rptr, p.d_rpos, p.d_err, d_mask, nullptr, 0, nullptr, 0, sb);
+  const int cap = std::max(1, restrict_resident_blocks() / std::max(1, p.ranks_on_device));
+  hipLaunchKernelGGL(k_peer_restrict_direct_t<false>, dim3(std::min(cap, std::max(mb, sb))), dim3(256), 0, s, p.d_nbr, p.nnbr, p.local, p.counters, nrecv_,
+                     GhostOut(), p.mb[1], nsend_, d_y, p.n_rdof, p.d_rinfo, p.d_rptr, p.d_rpos, p.d_err, d_mask, Step{});
   PA_HIP(hipGetLastError());
 }
 

@@ -170,7 +170,6 @@ class Halo {
   // in-process group: pieces [off[k], off[k + 1]) of `sendbase` go to neighbour k, pieces of the same sizes as `recv_off` arrive
   void ExchangeLocal(const double *sendbase, const std::vector<int> &send_off, double *recvbase, const std::vector<int> &recv_off,
                      hipStream_t s) const;
-  std::vector<int32_t> iface_;  // every local dof that is sent or received (host copy, sorted, unique)
   // peer transport (Comm::PeerReady): device-side plan of this halo, see comm.hip
   struct PeerPlan;
   PeerPlan *peer_ = nullptr;
@@ -200,15 +199,13 @@ public:
   // The same with a smoother step consumed where the sum over the ranks is formed (round 6; linalg.hpp: Operator::MultChebyStep on
   // split vectors): for every owned dof with sharers t = t_iface[d] + the neighbours' rows (essential rows: t_iface[d] alone), then
   //   mode 1:  out[d] (+)= ek[d] + sd (ek[d] - ep[d]) + sr dinv[d] (r0[d] - t)      mode 2:  res[d] = r0[d] - t,  out[d] = sr dinv[d] (r0[d] - t)
-  // -- the line the local gather evaluates for the dofs no other rank shares (pa_op_mult_split_step).  Merged form of P^T only.
+  // -- the line the local gather evaluates for the dofs no other rank shares (pa_op_mult_split_step).
   using Step = HaloStep;
   bool StepOk() const;
   void RestrictAddDirectStep(const uint8_t *d_mask, const double *d_t_iface, const Step &st, hipStream_t s) const;
   Halo(Comm &comm, int nnbr, const int *nbr, const int *send_off, const int32_t *send_idx, const int *recv_off,
        const int32_t *recv_idx);
   ~Halo();
-  // the local dofs the exchange touches: elements without any of them do not depend on it
-  const std::vector<int32_t> &InterfaceDofs() const { return iface_; }
   // The plan against the vector it will be used on: owned dofs sent are true dofs, ghosts lie in [n_true, n_local) -- in
   // particular the contiguous ghost range received into / sent from in place.  Called by every operator that takes a plan.
   void Validate(int n_true, int n_local) const;

@@ -390,10 +390,9 @@ void ComplexWrapperOperator::Mult(const ComplexVector &x, ComplexVector &y) cons
     return;
   }
   // whether a pair of applies shares one pass over the element data is ParOperator::Mult2's decision (it does when the
-  // operator has no streaming form); PALACE_AMD_MULT2=0 forces separate applies for A/B runs
-  static const bool pair = !(getenv("PALACE_AMD_MULT2") && std::string(getenv("PALACE_AMD_MULT2")) == "0");
-  const auto *par_i = pair ? dynamic_cast<const ParOperator *>(Ai_) : nullptr;
-  const auto *par_r = pair ? dynamic_cast<const ParOperator *>(Ar_) : nullptr;
+  // operator has no streaming form)
+  const auto *par_i = dynamic_cast<const ParOperator *>(Ai_);
+  const auto *par_r = dynamic_cast<const ParOperator *>(Ar_);
   if (Ar_) {  // yr = Ar xr, yi = Ar xi
     if (par_r) {
       par_r->Mult2(x.Real(), x.Imag(), y.Real(), y.Imag());

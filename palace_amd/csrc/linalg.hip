@@ -45,21 +45,6 @@ Workspace::~Workspace() {
   if (h_) (void)hipHostFree(h_);
   if (gs_d_) (void)hipFree(gs_d_);
   if (gs_h_) (void)hipHostFree(gs_h_);
-  if (halo_stream_) (void)hipStreamDestroy(halo_stream_);
-  if (ev_ready_) (void)hipEventDestroy(ev_ready_);
-  if (ev_done_) (void)hipEventDestroy(ev_done_);
-}
-hipStream_t Workspace::HaloStream() {
-  if (!halo_stream_) PA_HIP(hipStreamCreateWithFlags(&halo_stream_, hipStreamNonBlocking));
-  return halo_stream_;
-}
-hipEvent_t Workspace::ReadyEvent() {
-  if (!ev_ready_) PA_HIP(hipEventCreateWithFlags(&ev_ready_, hipEventDisableTiming));
-  return ev_ready_;
-}
-hipEvent_t Workspace::DoneEvent() {
-  if (!ev_done_) PA_HIP(hipEventCreateWithFlags(&ev_done_, hipEventDisableTiming));
-  return ev_done_;
 }
 double *Workspace::Device(size_t n) {
   PA_REQUIRE(n <= kDeviceDoubles, "reduction scratch request exceeds the workspace");
@@ -963,13 +948,6 @@ void Operator::MultComplex(const Operator &Ar, const Operator &Ai, const Vector 
   if (pa_op_mult_complex(Ar.op_, Ai.op_, xr.Data(), xi.Data(), yr.Data(), yi.Data(), ess_policy, Ar.ctx_->stream))
     throw pa::Error(pa_last_error());
 }
-void Operator::SetInterfaceDofs(const std::vector<int32_t> &ldofs) {
-  StreamGraph::Invalidate();
-  if (pa_op_set_interface_dofs(op_, ldofs.data(), (int32_t)ldofs.size())) throw pa::Error(pa_last_error());
-}
-void Operator::MultAfter(const Vector &x, Vector &y, hipEvent_t after) const {
-  if (pa_op_mult_after(op_, x.Data(), y.Data(), ctx_->stream, after)) throw pa::Error(pa_last_error());
-}
 void Operator::SetEssential(const int32_t *ess_host, int n) {
   StreamGraph::Invalidate();
   check(pa_op_set_essential(op_, ess_host, n));
@@ -1147,20 +1125,6 @@ ParOperator::ParOperator(const Context &ctx, const Operator &A, int n_true, cons
       if (d < n_true) mask[d] |= 2;
     d_ess_mask_ = pa::dev_upload(mask.data(), mask.size(), ctx.stream);
   }
-  if (halo) {
-    // interior element batches can overlap with the exchange of the ghosts (PALACE_AMD_OVERLAP=1).  Off by default: on one GPU
-    // with the exchanges redirected to the rank itself (scripts/time_halo_mult.py, the 1/8 slab of the strong-scaling bench)
-    // the fork / join of the second stream costs 29 us per apply (104 us against 75 us), more than the transfer of the
-    // 0.57 MB interface it could hide behind the interior batches; it pays only for exchanges slower than that.
-    static const bool enabled = [] {
-      const char *e = std::getenv("PALACE_AMD_OVERLAP");
-      return e && e[0] == '1';
-    }();
-    if (auto *c = dynamic_cast<const ceed::Operator *>(&A); c && enabled) {
-      const_cast<ceed::Operator *>(c)->SetInterfaceDofs(halo->InterfaceDofs());
-      A_overlap_ = c;
-    }
-  }
   if (!halo) {
     if (auto *m = dynamic_cast<const CsrOperator *>(&A)) {
       d_csr_bc_ = m->EliminatedValues(d_ess_, n_ess, policy == DiagonalPolicy::DIAG_ONE);
@@ -1241,7 +1205,7 @@ void ParOperator::Mult(const Vector &x, Vector &y) const {
     halo_->RestrictAddDirect(d_ess_mask_, y.Data(), c.stream);
     return;
   }
-  if (halo_ && halo_->UsesPeerTransport() && d_ess_mask_ && x.Data() != y.Data() && !A_overlap_) {
+  if (halo_ && halo_->UsesPeerTransport() && d_ess_mask_ && x.Data() != y.Data()) {
     // peer transport: the copies x -> lx, ly -> y and the essential-dof handling ride in the exchange kernels
     halo_->ProlongateFused(x.Data(), d_ess_mask_, n_true_, lx_.Data(), c.stream);
     A_->Mult(lx_, ly_);
@@ -1256,19 +1220,8 @@ void ParOperator::Mult(const Vector &x, Vector &y) const {
     linalg::Copy(c, x, tx);
     if (n_ess_) linalg::SetSubVector(c, tx, d_ess_, n_ess_, 0.0);  // (before P: the ghost copies of essential dofs must be zero too)
   }
-  if (halo_ && A_overlap_ && !StreamGraph::Recording()) {
-    // P on a second stream: fork after tx is complete, the apply joins before its interface batches
-    Workspace &w = c.Work();
-    hipStream_t hs = w.HaloStream();
-    PA_HIP(hipEventRecord(w.ReadyEvent(), c.stream));
-    PA_HIP(hipStreamWaitEvent(hs, w.ReadyEvent(), 0));
-    halo_->Prolongate(lx_.Data(), hs);
-    PA_HIP(hipEventRecord(w.DoneEvent(), hs));
-    A_overlap_->MultAfter(lx_, ly_, w.DoneEvent());
-  } else {
-    if (halo_) halo_->Prolongate(lx_.Data(), c.stream);  // owners -> sharers (P)
-    A_->Mult(lx_, ly_);
-  }
+  if (halo_) halo_->Prolongate(lx_.Data(), c.stream);  // owners -> sharers (P)
+  A_->Mult(lx_, ly_);
   if (halo_) halo_->RestrictAdd(ly_.Data(), c.stream);  // sharers -> owners, summed (P^T)
   Vector ty(ly_.Data(), n_true_);
   if (one_launch) {
@@ -1401,42 +1354,14 @@ void ChebyshevSmoother::Mult2(const Vector &x, Vector &y, Vector &r) const {
   // further order  y += d, r -= A d, d = sd_k d + sr_k D^-1 r; finally y += d -- is carried here by the accumulated correction
   // e_k = d_0 + ... + d_{k-1} (d_{k-1} = e_k - e_{k-1}, r_k = r_0 - A e_k): the same polynomial, but r_0 is only read (with a
   // zero guess it is the right-hand side x itself: no copy), y is written once, and a step moves 48 instead of 64 bytes per entry
-  // (DESIGN.md 3.7).  PALACE_AMD_CHEBY_FORM=d selects the literal form.
+  // (DESIGN.md 3.7).
   const Context &c = *ctx_;
-  static const bool literal = [] {
-    const char *e = std::getenv("PALACE_AMD_CHEBY_FORM");
-    return e && e[0] == 'd';
-  }();
   const double lmax = lambda_max_, lmin = sf_min_ * lmax;
   const double theta = 0.5 * (lmax + lmin), delta = 0.5 * (lmax - lmin);
   // coefficients of order k (k = 0: the scale of the first direction)
   auto first = [&]() { return fourth_kind_ ? 4.0 / (3.0 * lmax) : 1.0 / theta; };
   for (int it = 0; it < pc_it_; it++) {
     const bool zero = !(initial_guess || it > 0);
-    if (literal) {
-      if (!zero) {
-        A_->Mult(y, r);
-        linalg::AXPBY(c, 1.0, x, -1.0, r);
-      } else {
-        linalg::Copy(c, x, r);
-        linalg::Fill(c, y, 0.0);
-      }
-      linalg::ChebyOrder0(c, first(), dinv_, r, d_);
-      double rhop = delta / theta;
-      for (int k = 1; k < order_; k++) {
-        double sd, sr;
-        if (fourth_kind_) {  // chebyshev.cpp:204-218
-          sd = (2.0 * k - 1.0) / (2.0 * k + 3.0), sr = (8.0 * k + 4.0) / ((2.0 * k + 3.0) * lmax);
-        } else {  // chebyshev.cpp:275-291
-          const double rho = 1.0 / (2.0 * theta / delta - rhop);
-          sd = rho * rhop, sr = 2.0 * rho / delta, rhop = rho;
-        }
-        A_->Mult(d_, t_);
-        linalg::ChebyStep(c, sd, sr, dinv_, t_, r, d_, y);  // y += d; r -= A d; d = sd d + sr D^-1 r
-      }
-      linalg::AXPY(c, 1.0, d_, y);
-      continue;
-    }
     const Vector *r0 = &x;
     bool have_e1 = false;
     if (!zero && fused_step_ && order_ > 1 && r.Data() != x.Data()) {

@@ -33,8 +33,6 @@ struct HaloStep;
 class Workspace {
   double *d_ = nullptr, *h_ = nullptr, *gs_d_ = nullptr, *gs_h_ = nullptr;
   size_t gs_dn_ = 0, gs_hn_ = 0;
-  hipStream_t halo_stream_ = nullptr;
-  hipEvent_t ev_ready_ = nullptr, ev_done_ = nullptr;
 
 public:
   static constexpr size_t kDeviceDoubles = 32768, kPinnedDoubles = 64;  // fixed: recorded graphs keep these addresses
@@ -48,11 +46,6 @@ public:
   // never part of a recorded sequence
   double *GsDevice(size_t n);
   double *GsPinned(size_t n);
-  // second stream for halo exchanges that overlap with interior element work, and the two events of the fork / join
-  // (ready: the vector to exchange is complete on the main stream; done: the ghosts have arrived on the halo stream)
-  hipStream_t HaloStream();
-  hipEvent_t ReadyEvent();
-  hipEvent_t DoneEvent();
 };
 
 // Execution context shared by the objects of one solve: the stream everything is enqueued on and
@@ -263,10 +256,6 @@ public:
   void AddMultTranspose(const Vector &x, Vector &y, double a = 1.0) const override;
   void AssembleDiagonal(Vector &diag) const override;
   bool IsSymmetric() const override;
-  // multi-rank applies: the local dofs that take part in the halo exchange; MultAfter computes y = A x where those entries
-  // of x are complete only once `after` has fired (interior element batches do not wait for it)
-  void SetInterfaceDofs(const std::vector<int32_t> &ldofs);
-  void MultAfter(const Vector &x, Vector &y, hipEvent_t after) const;
   // y = A (x with the essential entries read as zero), no copy of x (pa_op_mult_essential)
   void SetEssential(const int32_t *ess_host, int n);
   void MultEssential(const Vector &x, Vector &y) const;
@@ -395,7 +384,6 @@ private:
   const Context *ctx_;
   const Operator *A_;
   const ceed::Operator *A_fused_ = nullptr;  // single rank: BC masking fused into the local apply
-  const ceed::Operator *A_overlap_ = nullptr;  // with a halo: interior elements run while the ghosts are exchanged
   const ceed::Operator *A_split_ = nullptr;    // peer transport: the local operator applies to split vectors (no L-vector copies)
   const ceed::Operator *A_split_avail_ = nullptr;
   const CsrOperator *A_csr_split_ = nullptr, *A_csr_split_avail_ = nullptr;  // the same for an assembled local operator

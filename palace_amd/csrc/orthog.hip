@@ -253,7 +253,6 @@ struct ResArgs {
   const double *const *vr, *const *vi;
   int m, normalize;
   long long n;
-  int prefetch;     // 1: v_{j+1} travels to LDS while the grid barrier of step j is pending (PALACE_AMD_GS_PREFETCH=0: off)
   double *partial;  // [2 parities][2 components][kResMaxGrid]
   unsigned *bar;    // group counters at [16 g], g < 16 (one 64-byte line each); the top counter at [256]; zero at launch
   double *coef, *nrm2;
@@ -311,7 +310,6 @@ __global__ __launch_bounds__(kResBlk) void k_mgs_resident(const ResArgs A) {
   extern __shared__ __attribute__((aligned(16))) double2 pre[];  // [LS][NC][kResBlk]: every thread reads what it wrote itself
   __shared__ double sm[2][kResBlk / 64];
   __shared__ double hb[2];
-  const bool pf = A.prefetch != 0;
   const long long nv = A.n / 2, stride = (long long)gridDim.x * kResBlk;
   const long long i0 = (long long)blockIdx.x * kResBlk + threadIdx.x;
   const bool tail = (A.n & 1) && blockIdx.x == 0 && threadIdx.x == 0;  // the odd last entry
@@ -388,14 +386,14 @@ __global__ __launch_bounds__(kResBlk) void k_mgs_resident(const ResArgs A) {
       }
     }
   };
-  if (pf && A.m > 0) prefetch(0);
+  if (A.m > 0) prefetch(0);
   for (int j = 0; j < A.m; j++) {
     const double *pr = A.vr[j], *pi = CPLX ? A.vi[j] : nullptr;
     double2 c[R], d[R];
     double ct = 0.0, dt = 0.0;
 #pragma unroll
     for (int r = 0; r < R; r++) {
-      if (pf && r < LS) {  // (requested while the previous step's barrier was pending)
+      if (r < LS) {  // (requested while the previous step's barrier was pending)
         c[r] = pre[(r * NC) * kResBlk + threadIdx.x];
         d[r] = CPLX ? pre[(r * NC + 1) * kResBlk + threadIdx.x] : double2{0.0, 0.0};
       } else {
@@ -420,7 +418,7 @@ __global__ __launch_bounds__(kResBlk) void k_mgs_resident(const ResArgs A) {
       if (CPLX) v[0] += bt * dt, v[1] += bt * ct - at * dt;
     }
     arrive(v, j, CPLX);
-    if (pf && j + 1 < A.m) prefetch(j + 1);  // (v_j is in registers: the LDS words are free)
+    if (j + 1 < A.m) prefetch(j + 1);  // (v_j is in registers: the LDS words are free)
     complete(v, j, CPLX);
     const double hr = v[0], hi = v[1];
     if (blockIdx.x == 0 && threadIdx.x == 0) {
@@ -554,8 +552,7 @@ bool run_resident(const Context &c, const Column &col, bool normalize, const GsB
   const int m = col.m;
   for (int j = 0; j < m; j++) B.host_ptrs[j] = col.vr[j], B.host_ptrs[m + j] = CPLX ? col.vi[j] : nullptr;
   PA_HIP(hipMemcpyAsync(B.ptrs, B.host_ptrs, sizeof(double *) * 2 * (size_t)m, hipMemcpyHostToDevice, c.stream));
-  const char *pe = std::getenv("PALACE_AMD_GS_PREFETCH");
-  const ResArgs A{col.wr, col.wi, B.ptrs, B.ptrs + m, m, normalize ? 1 : 0, col.n, (pe && pe[0] == '0') ? 0 : 1, B.partial, B.bar, B.coef1, B.nrm2};
+  const ResArgs A{col.wr, col.wi, B.ptrs, B.ptrs + m, m, normalize ? 1 : 0, col.n, B.partial, B.bar, B.coef1, B.nrm2};
   const long long nv = col.n / 2;
   bool fits = false;
 #define PA_TRY_RESIDENT(R)                                       \

@@ -378,8 +378,6 @@ static void free_sub(SubOp *so) {
 
 // y (+)= A x.  overwrite: the first sub-operator writes y instead of accumulating (Mult without a
 // separate memset when E^T runs as a gather).
-// after: an event the entries of x that take part in the halo exchange wait for (multi-rank applies, pa_op_mult_after): a
-// streaming block with interface batch lists runs its interior batches first; everything else simply waits up front
 // timing experiments (scripts/price_evec_cache.py): 1 = element kernel only, 2 = E^T run gather only (of the streaming form)
 #ifdef PA_ABLATION  // (the ablation library only, `make ablate`: the product library has no such switch)
 static int g_debug_phase = 0;
@@ -389,7 +387,7 @@ constexpr int g_debug_phase = 0;
 #endif
 
 static void apply(pa_op *op, const double *x, double *y, bool overwrite, hipStream_t s, bool masked = false,
-                  int ess_policy = -1, hipEvent_t after = nullptr) {
+                  int ess_policy = -1) {
   PA_REQUIRE(op && x && y, "null argument");
   PA_REQUIRE(!op->subs.empty() || !op->dsubs.empty() || !op->msubs.empty(), "operator has no sub-operators");
   PA_REQUIRE(x != y, "in-place apply is not supported");
@@ -397,17 +395,9 @@ static void apply(pa_op *op, const double *x, double *y, bool overwrite, hipStre
   PA_REQUIRE(op->msubs.empty() || !TransposeScope::active() || (op->subs.empty() && op->dsubs.empty()),
              "transposed apply of an operator with two-space sub-operators: those only");
   bool first = true;
-  const bool split = after && op->subs.size() == 1 && op->dsubs.empty() && op->subs[0]->fe_type == PA_FE_HCURL &&
-                     op->subs[0]->d_idxc && op->subs[0]->has_blist && overwrite && (!masked || op->subs[0]->d_perm_s_bc);
-  if (after && !split) PA_HIP(hipStreamWaitEvent(s, after, 0));
   for (const SubOp *so : op->subs) {
     if (so->fe_type == PA_FE_HCURL) {
-      if (split) {
-        launch_nd_hex_stream(*so, x, y, masked, s, 0);  // batches that touch no exchanged dof
-        PA_HIP(hipStreamWaitEvent(s, after, 0));
-        launch_nd_hex_stream(*so, x, y, masked, s, 1);
-        launch_et_run_gather(*so, y, false, s, x, masked, ess_policy);
-      } else if (so->d_idxc && overwrite && first && (!masked || so->d_perm_s_bc)) {  // streaming kernel (y = A x) + E^T of the shared dofs by runs
+      if (so->d_idxc && overwrite && first && (!masked || so->d_perm_s_bc)) {  // streaming kernel (y = A x) + E^T of the shared dofs by runs
         if (g_debug_phase != 2) launch_nd_hex_stream(*so, x, y, masked, s);
         if (g_debug_phase != 1) launch_et_run_gather(*so, y, false, s, x, masked, ess_policy);
       } else if (so->d_ye) {
@@ -1023,14 +1013,8 @@ int pa_op_mult_complex(pa_op *op_r, pa_op *op_i, const double *xr, const double 
       if (!sr->d_ye2) sr->d_ye2 = dev_alloc<double>((size_t)((sr->ne + 3) & ~3) * sr->P);
       if (sr->qd->metric) stream_element_coefficients(*op_i->subs[0]);
       launch_nd_hex_stream_complex(*sr, *op_i->subs[0], xr, xi, yr, yi, sr->d_ye2, masked, s);
-      // (q1d = 5: the wide kernel's gather keeps its two launches)
-      static const bool one_gather = !(getenv("PALACE_AMD_CPLX_GATHER2") && atoi(getenv("PALACE_AMD_CPLX_GATHER2")) == 0);
-      if (one_gather) {  // both parts in one launch: headers and copy positions read once (round 6)
-        launch_et_run_gather2(*sr, yr, yi, s, xr, xi, masked, ess_policy, sr->d_ye2);
-      } else {
-        launch_et_run_gather(*sr, yr, false, s, xr, masked, ess_policy);
-        launch_et_run_gather(*sr, yi, false, s, xi, masked, ess_policy, sr->d_ye2);
-      }
+      // both parts in one launch: headers and copy positions read once (round 6)
+      launch_et_run_gather2(*sr, yr, yi, s, xr, xi, masked, ess_policy, sr->d_ye2);
     }
     // the remaining sub-operators (operator.cpp:98-134 term by term): B of the real part, yr += B xr, yi += B xi; B of the
     // imaginary part, yi += B xr, yr -= B xi; essential entries of x read as zero through B's own flagged index copy, essential
@@ -1108,22 +1092,6 @@ int pa_op_set_essential(pa_op *op, const int32_t *ess, int32_t n) {
     }
     op->has_essential = true;
   });
-}
-
-int pa_op_set_interface_dofs(pa_op *op, const int32_t *ldofs, int32_t n) {
-  return guarded([&] {
-    PA_REQUIRE(op && (ldofs || n == 0), "null argument");
-    std::vector<char> flag((size_t)op->width, 0);
-    for (int i = 0; i < n; i++) {
-      PA_REQUIRE(ldofs[i] >= 0 && ldofs[i] < op->width, "interface dof out of range");
-      flag[ldofs[i]] = 1;
-    }
-    for (SubOp *so : op->subs) stream_set_interface(*so, flag);
-  });
-}
-
-int pa_op_mult_after(pa_op *op, const double *x, double *y, void *stream, void *event) {
-  return guarded([&] { apply(op, x, y, true, (hipStream_t)stream, false, -1, (hipEvent_t)event); });
 }
 
 int pa_op_mult_essential(pa_op *op, const double *x, double *y, void *stream) {
@@ -1318,7 +1286,7 @@ int pa_op_mult_split(pa_op *op, const double *x, const double *xg0, const double
     if (so->fe_type == PA_FE_H1)
       launch_h1_hex_stream(*so, x, y, masked, s, &io);
     else
-      launch_nd_hex_stream(*so, x, y, masked, s, -1, &io);
+      launch_nd_hex_stream(*so, x, y, masked, s, &io);
     launch_et_run_gather(*so, y, false, s, x, masked, ess_policy, nullptr, &io);
   });
 }

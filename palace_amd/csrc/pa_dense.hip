@@ -1595,8 +1595,7 @@ DenseSub *make_dense_sub(pa_geom *geom, const pa_restriction_desc &r, const pa_d
     // the rows by element only cost the apply kernel its coalesced stores (+3 us of 186) -- an unstructured mesh (config 3's) reads
     // one 64-byte sector per 8-byte entry from the [dof] rows and a third of that from the rows by element (gather of 2.18M order-3
     // dofs: 64 -> 37 us).  The sums do not depend on the choice (same copies, same order): timing noise cannot change a result.
-    // PALACE_AMD_DENSE_ELAYOUT=rows | block overrides (read at every creation: A / B runs in one process); the run form of the
-    // gather is written for the [dof] rows.
+    // PALACE_AMD_DENSE_ELAYOUT=rows | block overrides (read at every creation: A / B runs in one process).
     std::vector<int32_t> tptr((size_t)r.lsize + 1, 0), tent((size_t)ne * P), ted((size_t)ne * P);
     for (size_t k = 0; k < (size_t)ne * P; k++) tptr[(size_t)r.offsets[k] + 1]++;
     for (int d = 0; d < r.lsize; d++) tptr[d + 1] += tptr[d];
@@ -1615,10 +1614,9 @@ DenseSub *make_dense_sub(pa_geom *geom, const pa_restriction_desc &r, const pa_d
     };
     ds->d_tptr = dev_upload(tptr.data(), tptr.size());
     ds->d_ye = dev_alloc<double>(nslot);
-    const char *gl = getenv("PALACE_AMD_DENSE_ELAYOUT"), *gg = getenv("PALACE_AMD_DENSE_GATHER");
-    const bool runs_form = gg && std::string(gg) == "runs";
+    const char *gl = getenv("PALACE_AMD_DENSE_ELAYOUT");
     if (gl && std::string(gl) == "rows") ds->ye_rows = true;
-    else if ((gl && std::string(gl) == "block") || runs_form || r.lsize < (1 << 17)) ds->ye_rows = false;
+    else if ((gl && std::string(gl) == "block") || r.lsize < (1 << 17)) ds->ye_rows = false;
     else {
       PA_HIP(hipMemset(ds->d_ye, 0, nslot * sizeof(double)));
       double t[2];
@@ -1644,20 +1642,6 @@ DenseSub *make_dense_sub(pa_geom *geom, const pa_restriction_desc &r, const pa_d
         if (tptr[d + 1] > tptr[d]) rows.push_back(d);
       ds->n_rows = (int)rows.size();
       ds->d_rows = dev_upload(rows.data(), std::max<size_t>(rows.size(), 1));
-    }
-    // ... and, on request (PALACE_AMD_DENSE_GATHER=runs), its run form.  Measured on 279 936 order-3 tetrahedra, alternating on one box:
-    // curl-curl 0.1857 / 0.1866 ms with the CSR form against 0.1839 / 0.1846 ms by runs, K + M 0.2631 / 0.2633 against 0.2613 / 0.2618
-    // (-1 %: the gather is bound by its scattered 8-byte E-vector reads, not by the position words), and SLOWER on small blocks
-    // (14 362 cubic H1 tetrahedra: 0.076 against 0.031 ms, four dofs per thread leave 65 workgroups) -- the CSR form stays the default.
-    static const bool runs = getenv("PALACE_AMD_DENSE_GATHER") && std::string(getenv("PALACE_AMD_DENSE_GATHER")) == "runs";
-    if (runs) {
-      std::vector<uint32_t> code, rpos;
-      std::vector<streamhost::RunHdr> hdr;
-      streamhost::build_runs_dense(ne, P, KP, r.lsize, r.offsets, r.orients, code, hdr, rpos);
-      const std::vector<streamhost::RunChunk> ch = streamhost::run_chunks(code);
-      ds->d_rchunk = dev_upload(reinterpret_cast<const uint32_t *>(ch.data()), 4 * ch.size());
-      ds->d_rhdr = dev_upload(reinterpret_cast<const int32_t *>(hdr.data()), 2 * hdr.size());
-      ds->d_rpos_run = dev_upload(rpos.data(), std::max<size_t>(rpos.size(), 1));
     }
   }
   ds->h_idx = std::move(idx);
@@ -1895,7 +1879,6 @@ void free_dense_sub(DenseSub *ds) {
   hipFree(ds->d_L), hipFree(ds->d_qdata);
   hipFree(ds->d_off), hipFree(ds->d_cor), hipFree(ds->d_ori);
   hipFree(ds->d_ye), hipFree(ds->d_tptr), hipFree(ds->d_tent);
-  hipFree(ds->d_rchunk), hipFree(ds->d_rhdr), hipFree(ds->d_rpos_run);
   hipFree(ds->c0.d_attr_mat), hipFree(ds->c0.d_mat), hipFree(ds->c0.d_mat_t);
   hipFree(ds->c1.d_attr_mat), hipFree(ds->c1.d_mat), hipFree(ds->c1.d_mat_t);
   pa_geom_destroy(static_cast<pa_geom *>(ds->geom));
@@ -2255,80 +2238,6 @@ double time_dense_gather(const DenseSub &ds, const int32_t *d_tent) {
   return ms / reps;
 }
 
-// E^T of the dense path by runs (pa_stream_host.hpp: build_runs_dense): one thread per L-dof, its run and offset from the chunk
-// masks (12 bytes per 64 dofs), ONE position word per run and copy instead of one per dof and copy -- the copies of the dofs of an
-// edge or a face sit 16 doubles apart in the element's E-vector column, forwards or backwards -- same copies in the same order as
-// the CSR form (et_gather_kernel), hence the same bits.  kDenseGatherILP dofs per thread, a block width apart, their loads side by
-// side.  Split vectors (rows >= nsplit to yg) and ParOperator's essential rows (ess flags + policy) as in et_gather_split_kernel.
-constexpr int kDenseGatherILP = 4;
-__global__ __launch_bounds__(256) void et_run_gather_dense_kernel(const int n, const streamhost::RunChunk *__restrict__ chunk,
-                                                                  const streamhost::RunHdr *__restrict__ hdr,
-                                                                  const uint32_t *__restrict__ rpos, const double *__restrict__ ye,
-                                                                  double *__restrict__ y, double *__restrict__ yg, const int nsplit,
-                                                                  const int accumulate, const uint8_t *__restrict__ ess,
-                                                                  const double *__restrict__ x, const int ess_policy) {
-  const int k0 = blockIdx.x * (256 * kDenseGatherILP) + threadIdx.x;
-  const int lane = threadIdx.x & 63;
-  int pb[kDenseGatherILP], pe[kDenseGatherILP], j[kDenseGatherILP], run[kDenseGatherILP];
-  bool live[kDenseGatherILP];
-  double s[kDenseGatherILP], yold[kDenseGatherILP];
-#pragma unroll
-  for (int u = 0; u < kDenseGatherILP; u++) {
-    const int k = k0 + 256 * u;
-    live[u] = k < n;
-    const streamhost::RunChunk c = chunk[live[u] ? (k >> 6) : 0];
-    const unsigned long long low = (c.starts & ~1ull) & ((2ull << lane) - 1ull);
-    const int nc = __popcll(low);
-    run[u] = (int)(c.first >> 4) + nc;
-    j[u] = nc ? lane - (63 - __clzll((long long)low)) : (int)(c.first & 15u) + lane;
-  }
-#pragma unroll
-  for (int u = 0; u < kDenseGatherILP; u++) {
-    pb[u] = hdr[live[u] ? run[u] : 0].ptr;
-    pe[u] = hdr[live[u] ? run[u] + 1 : 0].ptr;
-    s[u] = 0.0, yold[u] = 0.0;
-    if (live[u] && ess_policy >= 0 && ess && ess[k0 + 256 * u] && k0 + 256 * u < nsplit) {
-      s[u] = ess_policy ? x[k0 + 256 * u] : 0.0;  // essential row: no copies to sum
-      pe[u] = pb[u];
-    } else if (live[u] && accumulate) {
-      yold[u] = y[k0 + 256 * u];
-    }
-  }
-  unsigned r4[kDenseGatherILP][4];
-#pragma unroll
-  for (int u = 0; u < kDenseGatherILP; u++)
-#pragma unroll
-    for (int q = 0; q < 4; q++) r4[u][q] = (live[u] && pb[u] + q < pe[u]) ? rpos[pb[u] + q] : 0xffffffffu;
-  double v[kDenseGatherILP][4];
-#pragma unroll
-  for (int u = 0; u < kDenseGatherILP; u++)
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-      const unsigned r = r4[u][q];
-      const bool have = live[u] && pb[u] + q < pe[u];
-      const long long at = (long long)(r & streamhost::kDenseRunPosMask) + ((r & streamhost::kDenseRunBack) ? -16 * j[u] : 16 * j[u]);
-      const double w = have ? ye[at] : 0.0;
-      v[u][q] = (r & streamhost::kDenseRunNeg) ? -w : w;
-    }
-#pragma unroll
-  for (int u = 0; u < kDenseGatherILP; u++) {
-#pragma unroll
-    for (int q = 0; q < 4; q++)
-      if (live[u] && pb[u] + q < pe[u]) s[u] += v[u][q];
-    if (live[u])
-      for (int p = pb[u] + 4; p < pe[u]; p++) {
-        const unsigned r = rpos[p];
-        const double w = ye[(long long)(r & streamhost::kDenseRunPosMask) + ((r & streamhost::kDenseRunBack) ? -16 * j[u] : 16 * j[u])];
-        s[u] += (r & streamhost::kDenseRunNeg) ? -w : w;
-      }
-  }
-#pragma unroll
-  for (int u = 0; u < kDenseGatherILP; u++) {
-    const int d = k0 + 256 * u;
-    if (live[u]) (d < nsplit ? y : yg)[d] = yold[u] + s[u];  // (y + sum of the copies: the CSR form's order)
-  }
-}
-
 // y[d] += sign * sum of the copies of d (CSR form, the copies in element order), rows without copies and -- skip_ess -- essential rows
 // untouched: the small sub-operators added to a vector another operator has already written (pa_op_mult_complex)
 __global__ void et_gather_signed_kernel(const int n, const int32_t *__restrict__ rows, const int32_t *__restrict__ tptr,
@@ -2359,19 +2268,6 @@ void launch_dense_gather_signed(const DenseSub &ds, double *y, double sign, bool
 
 void launch_dense_gather(const DenseSub &ds, double *y, bool accumulate, hipStream_t s, const double *ye, const SplitIO *split,
                          const double *x, int ess_policy) {
-  if (ds.d_rchunk) {
-    PA_REQUIRE(!(split || ess_policy >= 0) || !accumulate, "split vectors / fused essential rows: y = A x only");
-    PA_REQUIRE(ess_policy < 0 || (ds.d_ess_flag && x), "essential rows fused into the gather: pa_op_set_essential first");
-    const int n = ds.lsize;
-    if (n == 0) return;
-    hipLaunchKernelGGL(et_run_gather_dense_kernel, dim3((n + 256 * kDenseGatherILP - 1) / (256 * kDenseGatherILP)), dim3(256), 0, s, n,
-                       reinterpret_cast<const streamhost::RunChunk *>(ds.d_rchunk),
-                       reinterpret_cast<const streamhost::RunHdr *>(ds.d_rhdr), ds.d_rpos_run, ye ? ye : ds.d_ye, y,
-                       split ? split->yg - split->n_true : y, split ? split->n_true : 0x7fffffff, accumulate ? 1 : 0,
-                       ess_policy >= 0 ? ds.d_ess_flag : nullptr, x, ess_policy);
-    PA_HIP(hipGetLastError());
-    return;
-  }
   // every overwriting gather takes the same kernel (plain, split vectors, essential rows fixed on the way): y = A x has the same bits
   // whichever entry point computed it (tests/test_split_gpu.py compares them with torch.equal); the accumulating forms below keep the
   // serial order of et_gather_kernel
@@ -2424,7 +2320,7 @@ void launch_surface_rows(const int32_t *rows, int n, const int32_t *row_ptr, con
   PA_HIP(hipGetLastError());
 }
 
-bool dense_fused_step_ok(const DenseSub &ds) { return ds.d_ess_flag && !ds.d_rchunk && ds.d_tptr && ds.d_tent && ds.d_ye; }
+bool dense_fused_step_ok(const DenseSub &ds) { return ds.d_ess_flag && ds.d_tptr && ds.d_tent && ds.d_ye; }
 void launch_dense_gather_step(const DenseSub &ds, const double *x, const GatherStep &step, int ess_policy, hipStream_t s,
                               const SplitIO *split) {
   PA_REQUIRE(dense_fused_step_ok(ds) && x, "dense fused step: essential list fused (pa_op_set_essential) and the CSR-form gather expected");

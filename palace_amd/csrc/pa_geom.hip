@@ -66,11 +66,10 @@ __global__ void geom_factor_kernel(int ne, int q1d, int m1, const int32_t *__res
 // Internal element order of a tensor hex block: Morton (Z) order of the element centroids.  The element kernels walk the
 // block in this order (eight contiguous ranges, one per XCD, a window of consecutive elements in flight on each), so the
 // x / y lines shared by neighbouring elements are re-used from L2 while they are still there; the caller's order (whatever
-// the mesh generator produced) only decides where an element's rows sit in the descriptors.  PALACE_AMD_REORDER=0 keeps it.
+// the mesh generator produced) only decides where an element's rows sit in the descriptors.
 static std::vector<int32_t> morton_order(const pa_mesh_desc &mesh, int npe) {
   const int ne = mesh.num_elem;
-  const char *env = getenv("PALACE_AMD_REORDER");
-  if ((env && atoi(env) == 0) || ne < 64) return {};
+  if (ne < 64) return {};
   std::vector<double> c((size_t)ne * 3, 0.0);
   double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
   for (int e = 0; e < ne; e++) {

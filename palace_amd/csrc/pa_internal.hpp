@@ -206,9 +206,6 @@ struct SubOp {
   // streaming form (pa_nd_hex_stream.hip): index words with the exclusive flag, byte slots, E^T of the shared dofs by runs
   uint32_t *d_idxc = nullptr;  // [ne][kIdxWords] run-compressed sorted element -> dof index (pa_stream_host.hpp)
   bool stream_default = true;  // false: the tables exist for the split-vector apply only, y = A x keeps the one-shot kernel (H1, p < 3)
-  int32_t *d_blist[2] = {nullptr, nullptr};  // batch lists of the interior / interface phases (stream_set_interface)
-  int n_blist[2] = {0, 0};
-  bool has_blist = false;
   uint32_t *d_perm_s_bc = nullptr;                      // flag words with the essential dofs taken off the direct path
   std::vector<uint32_t> h_perm_s;
   int32_t *d_rhdr_bc = nullptr, *d_rpos_bc = nullptr;   // run list that also owns the essential rows
@@ -273,9 +270,6 @@ struct DenseSub {
   uint8_t *d_ori = nullptr;
   double *d_ye = nullptr;      // E-vector [nb][4 KP][16]
   int32_t *d_tptr = nullptr, *d_tent = nullptr;
-  // run form of the same map (pa_stream_host.hpp: build_runs_dense): chunk masks, run headers, one position per run and copy
-  uint32_t *d_rchunk = nullptr, *d_rpos_run = nullptr;
-  int32_t *d_rhdr = nullptr;
   std::vector<uint8_t> ctx_blob;
   CoeffHost c0, c1;
 };
@@ -336,9 +330,7 @@ struct SplitIO {
   double *yg;
 };
 bool nd_hex_stream_split_ok(const SubOp &so);
-void launch_nd_hex_stream(const SubOp &so, const double *x, double *y, bool masked, hipStream_t s, int phase = -1,
-                          const SplitIO *split = nullptr);
-void stream_set_interface(SubOp &so, const std::vector<char> &flag);
+void launch_nd_hex_stream(const SubOp &so, const double *x, double *y, bool masked, hipStream_t s, const SplitIO *split = nullptr);
 // One step of a smoother recurrence consumed inside E^T (round 6): with t = (A x)[d] (the essential rows fixed as in the masked
 // apply) the run gather writes  out[d] (+)= x[d] + sd (x[d] - ep[d]) + sr dinv[d] (r0[d] - t)  for every dof and never stores t:
 // the Chebyshev step of chebyshev.cpp:204-218 in its accumulated form (linalg.hip: OpChebStep3) without the round trip of A x.
@@ -367,8 +359,8 @@ void launch_nd_hex_stream_all(const SubOp &so, const double *x, hipStream_t s, c
 void launch_et_run_gather_step(const SubOp &so, const double *x, const GatherStep &step, int ess_policy, hipStream_t s,
                                const SplitIO *split = nullptr);
 bool nd_hex_stream5_ok(const SubOp &so);
-void launch_nd_hex_stream5(const SubOp &so, const double *x, double *y, bool masked, hipStream_t s, int phase,
-                           const SplitIO *split = nullptr, bool all = false);
+void launch_nd_hex_stream5(const SubOp &so, const double *x, double *y, bool masked, hipStream_t s, const SplitIO *split = nullptr,
+                           bool all = false);
 void launch_nd_hex_stream5_complex(const SubOp &sr, const SubOp &si, const double *xr, const double *xi, double *yr, double *yi,
                                    double *ye_i, bool masked, hipStream_t s);
 void launch_et_run_gather(const SubOp &so, double *y, bool accumulate, hipStream_t s, const double *x, bool masked,

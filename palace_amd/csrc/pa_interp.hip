@@ -955,12 +955,11 @@ public:
       d_tptr_ = pa::dev_upload(tptr.data(), tptr.size(), ctx.stream);
       d_tent_ = pa::dev_upload(tent.data(), tent.size(), ctx.stream);
       d_ye_ = pa::dev_alloc<double>(nd);
-      // rows of very different lengths (simplices): several lanes per dof in the transposed gather (PALACE_AMD_INTERP_GATHER_GROUP=0: off)
+      // rows of very different lengths (simplices): several lanes per dof in the transposed gather
       int longest = 0;
       for (int d = 0; d < nl_d_; d++) longest = std::max(longest, tptr[d + 1] - tptr[d]);
       const double avg = nl_d_ > 0 ? (double)nd / nl_d_ : 1.0;
-      const char *ge = std::getenv("PALACE_AMD_INTERP_GATHER_GROUP");
-      if (longest >= 12 && !(ge && ge[0] == '0')) gather_group_ = avg < 2.5 ? 2 : avg < 5.0 ? 4 : 8;
+      if (longest >= 12) gather_group_ = avg < 2.5 ? 2 : avg < 5.0 ? 4 : 8;
     }
     d_off_d_ = pa::dev_upload(rd.offsets, nd, ctx.stream);
     d_off_r_ = pa::dev_upload(offr.data(), nr, ctx.stream);
@@ -970,9 +969,8 @@ public:
     d_M_ = pa::dev_upload(M, (size_t)nmat * Pr_ * Pd_, ctx.stream);
     nmat_ = nmat;
     if (mat_id) d_mat_id_ = pa::dev_upload(mat_id, (size_t)ne_, ctx.stream);
-    // the register form (read at creation: PALACE_AMD_DENSE_INTERP=lds keeps the strips in LDS)
-    const char *form = std::getenv("PALACE_AMD_DENSE_INTERP");
-    if (nmat == 1 && Pd_ <= 64 && Pr_ <= 64 && std::min(Pd_, Pr_) >= 1 && std::max(Pd_, Pr_) <= 48 && !(form && std::string(form) == "lds")) {
+    // the register form (else the strips stay in LDS)
+    if (nmat == 1 && Pd_ <= 64 && Pr_ <= 64 && std::min(Pd_, Pr_) >= 1 && std::max(Pd_, Pr_) <= 48) {
       auto pack = [&](const pa_restriction_desc &r, int P, bool columns) {
         std::vector<int32_t> pk((size_t)ne_ * P);
         for (int e = 0; e < ne_; e++)

@@ -386,8 +386,7 @@ static void launch_pq(const SubOp &so, const double *x, double *y, double *ye, b
 #endif
   const int epb = kWavesPerBlock * L::EPW;
   const int nblk = (so.ne + epb - 1) / epb;
-  static const bool xcd_map = !(getenv("PALACE_AMD_XCD") && atoi(getenv("PALACE_AMD_XCD")) == 0);
-  a.xcd_chunk = (xcd_map && nblk >= 64) ? (nblk + 7) / 8 : 0;
+  a.xcd_chunk = nblk >= 64 ? (nblk + 7) / 8 : 0;
   const dim3 grid(a.xcd_chunk > 0 ? 8 * a.xcd_chunk : nblk), block(64 * kWavesPerBlock);
   const size_t lds = sizeof(double) * (size_t)epb * L::ELEM_PAD;
   switch (so.qf) {

@@ -73,7 +73,6 @@ __host__ __device__ constexpr int stream_lds_elem(const int raw) { return (raw +
 template <int P1>
 struct NDStreamArgs {
   int ne, nbatch, chunk;  // chunk: batches per XCD (contiguous range)
-  const int32_t *blist;   // optional list of batches to process (nbatch entries, increasing); NULL: all of 0 .. nbatch - 1
   const uint32_t *idxc;   // [ne][kIdxWords] run-compressed sorted element -> dof index (pa_stream_host.hpp)
   const uint32_t *flagw;  // [ne][16]: bit 2 r = entry t + 16 r is flipped, bit 2 r + 1 = it is the only copy of its dof,
                           // bit 18 + r = essential (read as zero; set in the copy used by masked applies)
@@ -106,8 +105,8 @@ struct NDStreamArgs {
   NDTab<P1, 4> tab;
 };
 
-// GPOS: where x of the next batch is requested (0 before the transposed passes, 1 / 2 / 3 after their first / second /
-// third component).  Later = fewer live registers, shorter flight.
+// GPOS: where x of the next batch is requested (1 / 2 after the first / second transposed component).  Later = fewer live
+// registers, shorter flight.
 // CPLX (metric form only): y = (A_r + i A_i) x for two operators on the same space and geometry whose D differ by the scalar
 // coefficients of their elements only -- (a_r + i a_i)(u_r + i u_i) at every quadrature point.  A batch is two elements times
 // the two parts of x: the even 16-lane groups of a wave carry the real part, the odd ones the imaginary part of the same
@@ -167,10 +166,8 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, MINW) void nd_hex_stream_kerne
   const int xcd = blockIdx.x & 7;
   const int base = xcd * a.chunk, bend = min(base + a.chunk, a.nbatch);
   const int stride = (int)(gridDim.x >> 3) * kWavesPerBlock;
-  // (with a batch list -- the interior / interface phases of a multi-rank apply -- positions in the list are walked)
-  int k = base + (int)(blockIdx.x >> 3) * kWavesPerBlock + wave;
-  if (k >= bend) return;
-  int b = a.blist ? a.blist[k] : k;
+  int b = base + (int)(blockIdx.x >> 3) * kWavesPerBlock + wave;
+  if (b >= bend) return;
   // index words of a batch (every array is padded to a multiple of four elements; pad entries read as zero and are
   // stored to E-vector rows nobody gathers)
   // s[0 .. NPL): the slice words (the same word for the 16 lanes of an element), s[NPL], s[NPL + 1]: run starts t, 16 + t
@@ -330,9 +327,9 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, MINW) void nd_hex_stream_kerne
 
     // index words of the next batch (clamped: the last iteration re-reads its own); first use: the x gather below.
     // Requested here when the registers allow (p < 3), after the forward passes otherwise.
-    const int kn = k + stride;
+    const int kn = b + stride;
     const bool more = kn < bend;
-    const int bn = more ? (a.blist ? a.blist[kn] : kn) : b;
+    const int bn = more ? kn : b;
     int sB[NPL + 2];
     unsigned pB[NPK + 1];
     if (EARLY_IDX) {
@@ -548,12 +545,6 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, MINW) void nd_hex_stream_kerne
     }
     // x of the next batch: in flight during the transposed passes
     double xB[NPL];
-    if (GPOS == 0) {
-      __builtin_amdgcn_sched_barrier(0);
-      gather(sB, pB, xB, stab, t);
-      settle(pB);
-      __builtin_amdgcn_sched_barrier(0);
-    }
     nd_bwd_comp<0, P1, Q1, USE_U, USE_C, L>(a, e, true, true, ta, tb, lx, sm, uin[0], U, CU);
     PA_STAMP(6);  // first transposed component done
     if (GPOS == 1) {
@@ -571,12 +562,6 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, MINW) void nd_hex_stream_kerne
       __builtin_amdgcn_sched_barrier(0);
     }
     nd_bwd_comp<2, P1, Q1, USE_U, USE_C, L>(a, e, true, true, ta, tb, lx, sm, uin[2], U, CU);
-    if (GPOS == 3) {
-      __builtin_amdgcn_sched_barrier(0);
-      gather(sB, pB, xB, stab, t);
-      settle(pB);
-      __builtin_amdgcn_sched_barrier(0);
-    }
 
     PA_STAMP(8);  // transposed passes done
     // E^T: back to tensor order in LDS, out in sorted order, signed; exclusive dofs straight to y
@@ -610,14 +595,8 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, MINW) void nd_hex_stream_kerne
 #ifdef PA_STREAM_TRACE
     tr_b++;
 #endif
-    if (GPOS == 4) {
-      __builtin_amdgcn_sched_barrier(0);
-      gather(sB, pB, xB, stab, t);
-      settle(pB);
-      __builtin_amdgcn_sched_barrier(0);
-    }
     if (!more) break;
-    k = kn, b = bn;
+    b = bn;
 #pragma unroll
     for (int r = 0; r < NPL; r++) sA[r] = sB[r], xv[r] = xB[r];
 #pragma unroll
@@ -1052,30 +1031,7 @@ void stream_set_essential(SubOp &so, const std::vector<char> &flag) {
   so.n_runs_bc = (int)hdr.size() - 1;
 }
 
-// Interior / interface split for multi-rank applies: flag[d] != 0 marks the local dofs that take part in the halo exchange
-// (ghosts and the owned dofs other ranks hold as ghosts).  Batches (four consecutive elements) without any such dof form
-// list 0 and can run while the exchange is in flight; the others form list 1.
-void stream_set_interface(SubOp &so, const std::vector<char> &flag) {
-  if (!so.d_idxc) return;
-  const int epb = wide_form(so) ? 2 : 4;  // elements per batch (one wave)
-  const int nb = (so.ne + epb - 1) / epb, P = so.P;
-  std::vector<int32_t> lists[2];
-  for (int b = 0; b < nb; b++) {
-    bool iface = false;
-    for (int e = epb * b; e < std::min(epb * b + epb, so.ne) && !iface; e++)
-      for (int m = 0; m < P && !iface; m++) iface = flag[streamhost::dof_of(so.h_sidx[(size_t)e * P + m])] != 0;
-    lists[iface ? 1 : 0].push_back(b);
-  }
-  for (int ph = 0; ph < 2; ph++) {
-    hipFree(so.d_blist[ph]);
-    so.d_blist[ph] = lists[ph].empty() ? nullptr : dev_upload(lists[ph].data(), lists[ph].size());
-    so.n_blist[ph] = (int)lists[ph].size();
-  }
-  so.has_blist = true;
-}
-
 void free_stream(SubOp &so) {
-  hipFree(so.d_blist[0]), hipFree(so.d_blist[1]);
   hipFree(so.d_idxc), hipFree(so.d_perm_s), hipFree(so.d_perm_s_bc), hipFree(so.d_coef_s);
   hipFree(so.d_flagw), hipFree(so.d_flagw_bc), hipFree(so.d_slots);
   hipFree(so.d_flagw_all), hipFree(so.d_perm_s_all), hipFree(so.d_rchunk_all), hipFree(so.d_rhdr_all), hipFree(so.d_rpos_all);
@@ -1116,18 +1072,10 @@ static void launch_gpos(const SubOp &so, NDStreamArgs<P1> &a, hipStream_t s) {
   const int per_cu = wg_env > 0 ? wg_env : per_cu_query;
   const int per_xcd = std::max(1, device_cus() / 8) * per_cu;
   if (CPLX) a.nbatch = (so.ne + 1) / 2;  // two elements times two parts per batch
-  else if (!a.blist) a.nbatch = (so.ne + 3) / 4;  // (else: the length of the list, set by the caller)
+  else a.nbatch = (so.ne + 3) / 4;
   if (a.nbatch == 0) return;
   a.chunk = (a.nbatch + 7) / 8;
-  // Few rounds (the per-rank size of a strong-scaling run: 490 batches per XCD over 384 resident waves = 1.28 rounds): the grid can
-  // be sized so that every wave walks the SAME number of batches -- 245 waves x 2 instead of 106 x 2 + 278 x 1
-  // (PALACE_AMD_STREAM_BALANCE=N: balance up to N rounds).  Measured neutral on the 1/8 slab (round 5, profiles/r05_halo_proxy.log:
-  // local apply 29.0 against 29.1 us, ParOperator::Mult 45.3 both): the critical path is two batches either way.  Default off.
-  static const int balance = getenv("PALACE_AMD_STREAM_BALANCE") ? atoi(getenv("PALACE_AMD_STREAM_BALANCE")) : 0;
-  const int max_waves = per_xcd * kWavesPerBlock;
-  int waves = std::min(max_waves, a.chunk);
-  const int rounds = (a.chunk + max_waves - 1) / max_waves;
-  if (rounds >= 2 && rounds <= balance) waves = (a.chunk + rounds - 1) / rounds;
+  const int waves = std::min(per_xcd * kWavesPerBlock, a.chunk);
   const int wgx = std::max(1, (waves + kWavesPerBlock - 1) / kWavesPerBlock);
   hipLaunchKernelGGL((nd_hex_stream_kernel<P1, U, C, METRIC, MINW, GPOS, CPLX, SPLIT, GEOMN>), dim3(8 * wgx), dim3(64 * kWavesPerBlock),
                      lds, s, a);
@@ -1138,7 +1086,6 @@ static void launch_gpos(const SubOp &so, NDStreamArgs<P1> &a, hipStream_t s) {
 // for the kernels with a mass term (their index words are requested just before D and need time to arrive and to be
 // decoded; later = fewer live registers: 202 instead of 248 VGPRs for K + M at p = 3; measured on the 10M-dof case with the
 // run-compressed index: curl-curl 0.180 / 0.181 ms, K + M 0.187 / 0.185 ms, mass 0.168 / 0.156 ms for positions 1 / 2).
-// PALACE_AMD_STREAM_GPOS = 0 / 1 / 2 for A/B.
 template <int P1, bool U, bool C, bool METRIC, int MINW_>
 static void launch_variant(const SubOp &so, NDStreamArgs<P1> &a, hipStream_t s) {
 #ifdef PA_STREAM_MINW2  // experiment builds: two waves per SIMD everywhere
@@ -1146,19 +1093,14 @@ static void launch_variant(const SubOp &so, NDStreamArgs<P1> &a, hipStream_t s) 
 #else
   constexpr int MINW = MINW_;
 #endif
-  static const int gpos = getenv("PALACE_AMD_STREAM_GPOS") ? atoi(getenv("PALACE_AMD_STREAM_GPOS")) : (U ? 2 : 1);
-  if (a.nsplit >= 0)  // split vectors: the default gather position only (one more instantiation per operator kind)
-    return launch_gpos<P1, U, C, METRIC, MINW, (U ? 2 : 1), false, true>(so, a, s);
-  if (gpos == 0)
-    launch_gpos<P1, U, C, METRIC, MINW, 0>(so, a, s);
-  else if (gpos == 2)
-    launch_gpos<P1, U, C, METRIC, MINW, 2>(so, a, s);
-  else
-    launch_gpos<P1, U, C, METRIC, MINW, 1>(so, a, s);
+  constexpr int GPOS = U ? 2 : 1;
+  if (a.nsplit >= 0)  // split vectors (one more instantiation per operator kind)
+    return launch_gpos<P1, U, C, METRIC, MINW, GPOS, false, true>(so, a, s);
+  launch_gpos<P1, U, C, METRIC, MINW, GPOS>(so, a, s);
 }
 
 template <int P1>
-static void launch_p(const SubOp &so, const double *x, double *y, bool masked, hipStream_t s, int phase, const SplitIO *split,
+static void launch_p(const SubOp &so, const double *x, double *y, bool masked, hipStream_t s, const SplitIO *split,
                      bool all = false) {
   NDStreamArgs<P1> a{};  // (every field the chosen form does not use: zero)
   a.nsplit = -1, a.xg0 = a.xg1 = nullptr, a.xg_sel = nullptr, a.yg = nullptr;
@@ -1168,13 +1110,7 @@ static void launch_p(const SubOp &so, const double *x, double *y, bool masked, h
     a.xg0 = split->xg0 - split->n_true, a.xg1 = (split->xg1 ? split->xg1 : split->xg0) - split->n_true;
     a.xg_sel = split->sel, a.yg = split->yg - split->n_true;
   }
-  a.ne = so.ne;
-  a.blist = nullptr, a.nbatch = 0;
-  if (phase >= 0) {  // 0: batches without interface elements, 1: the others (stream_set_interface)
-    PA_REQUIRE(so.d_blist[phase] || so.n_blist[phase] == 0, "interface batch lists missing");
-    a.blist = so.d_blist[phase], a.nbatch = so.n_blist[phase];
-    if (a.nbatch == 0) return;
-  }
+  a.ne = so.ne, a.nbatch = 0;
   a.idxc = so.d_idxc;
   a.flagw = all ? so.d_flagw_all : (masked ? so.d_flagw_bc : so.d_flagw);
   a.slots = so.d_slots;
@@ -1223,11 +1159,11 @@ void launch_nd_hex_stream_all(const SubOp &so, const double *x, hipStream_t s, c
   PA_REQUIRE(so.n_all > 0, "stream_build_all has not been called");
   double *unused = so.d_ye;  // (no entry is exclusive in this form: y is never written)
   if (so.fe_type == PA_FE_H1) return launch_h1_hex_stream(so, x, unused, true, s, split, true);
-  if (wide_form(so)) return launch_nd_hex_stream5(so, x, unused, true, s, -1, split, true);
+  if (wide_form(so)) return launch_nd_hex_stream5(so, x, unused, true, s, split, true);
   switch (so.p) {
-    case 1: launch_p<1>(so, x, unused, true, s, -1, split, true); break;
-    case 2: launch_p<2>(so, x, unused, true, s, -1, split, true); break;
-    case 3: launch_p<3>(so, x, unused, true, s, -1, split, true); break;
+    case 1: launch_p<1>(so, x, unused, true, s, split, true); break;
+    case 2: launch_p<2>(so, x, unused, true, s, split, true); break;
+    case 3: launch_p<3>(so, x, unused, true, s, split, true); break;
     default: throw Error("no streaming H(curl) hex kernel for this order");
   }
 }
@@ -1236,12 +1172,12 @@ bool nd_hex_stream_split_ok(const SubOp &so) {
   return so.fe_type == PA_FE_HCURL && so.d_idxc && (so.q1d == 4 || (wide_form(so) && nd_hex_stream5_ok(so)));
 }
 
-void launch_nd_hex_stream(const SubOp &so, const double *x, double *y, bool masked, hipStream_t s, int phase, const SplitIO *split) {
-  if (wide_form(so)) return launch_nd_hex_stream5(so, x, y, masked, s, phase, split);
+void launch_nd_hex_stream(const SubOp &so, const double *x, double *y, bool masked, hipStream_t s, const SplitIO *split) {
+  if (wide_form(so)) return launch_nd_hex_stream5(so, x, y, masked, s, split);
   switch (so.p) {
-    case 1: launch_p<1>(so, x, y, masked, s, phase, split); break;
-    case 2: launch_p<2>(so, x, y, masked, s, phase, split); break;
-    case 3: launch_p<3>(so, x, y, masked, s, phase, split); break;
+    case 1: launch_p<1>(so, x, y, masked, s, split); break;
+    case 2: launch_p<2>(so, x, y, masked, s, split); break;
+    case 3: launch_p<3>(so, x, y, masked, s, split); break;
     default: throw Error("no streaming H(curl) hex kernel for this order");
   }
 }
@@ -1275,7 +1211,7 @@ template <int P1>
 static void launch_complex_p(const SubOp &sr, const SubOp &si, const double *xr, const double *xi, double *yr, double *yi,
                              double *ye_i, bool masked, hipStream_t s) {
   NDStreamArgs<P1> a{};  // (every field the chosen form does not use: zero)
-  a.ne = sr.ne, a.blist = nullptr, a.nbatch = 0;
+  a.ne = sr.ne, a.nbatch = 0;
   a.idxc = sr.d_idxc;
   a.flagw = masked ? sr.d_flagw_bc : sr.d_flagw;
   a.slots = sr.d_slots;
@@ -1295,13 +1231,8 @@ static void launch_complex_p(const SubOp &sr, const SubOp &si, const double *xr,
     a.qc[g] = qf == PA_QF_HDIV_33 ? 0 : (qf == PA_QF_HDIVMASS_33 ? 6 : -1);
   }
   a.qdata1 = si.qd->d;
-  // (where x of the next batch is requested: after the second transposed component, as in the real K + M kernel;
-  // PALACE_AMD_CPLX_GPOS=1 / 3 for A / B, read at every launch)
-  const char *ge = getenv("PALACE_AMD_CPLX_GPOS");
-  const int gpos = ge ? atoi(ge) : 2;
-  if (gpos == 1) launch_gpos<P1, true, true, false, 2, 1, true>(sr, a, s);
-  else if (gpos == 3) launch_gpos<P1, true, true, false, 2, 3, true>(sr, a, s);
-  else launch_gpos<P1, true, true, false, 2, 2, true>(sr, a, s);
+  // (where x of the next batch is requested: after the second transposed component, as in the real K + M kernel)
+  launch_gpos<P1, true, true, false, 2, 2, true>(sr, a, s);
 }
 
 void launch_nd_hex_stream_complex(const SubOp &sr, const SubOp &si, const double *xr, const double *xi, double *yr, double *yi,

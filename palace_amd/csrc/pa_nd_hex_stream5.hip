@@ -23,7 +23,6 @@ typedef double d2v5 __attribute__((ext_vector_type(2)));
 template <int P1>
 struct NDStream5Args {
   int ne, nbatch, chunk;  // chunk: batches per XCD (contiguous range)
-  const int32_t *blist;   // optional list of batches (interior / interface phases of a multi-rank apply)
   const uint32_t *idxw;   // [nep][kWideWords]
   const uint32_t *perm;   // [nep][NPK][32] slot half-words
   const double *qdata;    // [nep][NG][126]
@@ -40,7 +39,7 @@ struct NDStream5Args {
   NDTab<P1, 5> tab;
 };
 
-// QPOS: where the q-data of the batch is requested: 0 at the top of the batch, 1 / 2 after the first / second forward
+// QPOS: where the q-data of the batch is requested: 0 at the top of the batch, 2 after the second forward
 // component (later = shorter live range of its 60 - 70 registers; curl-curl + mass at p = 4 does not fit 256 otherwise)
 // CPLX: y = (A_r + i A_i)(x_r + i x_i) in one pass (pa_op_mult_complex; the complex form of the four-point kernel, DESIGN.md
 // 3.1c, carried over): ONE element per wave, its two 32-lane halves hold the real and the imaginary part of x / y; both read
@@ -76,9 +75,8 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, 2) void nd_hex_stream5_kernel(
   const int xcd = blockIdx.x & 7;
   const int base = xcd * a.chunk, bend = min(base + a.chunk, a.nbatch);
   const int stride = (int)(gridDim.x >> 3) * kWavesPerBlock;
-  int k = base + (int)(blockIdx.x >> 3) * kWavesPerBlock + wave;
-  if (k >= bend) return;
-  int b = a.blist ? a.blist[k] : k;
+  int b = base + (int)(blockIdx.x >> 3) * kWavesPerBlock + wave;
+  if (b >= bend) return;
 
   // index block and slot words of a batch (arrays padded to whole batches; pad entries read as zero)
   const double *xsel = (CPLX && (lane >> 5)) ? a.x1 : a.x;  // the part of x this half gathers
@@ -139,11 +137,10 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, 2) void nd_hex_stream5_kernel(
     int *stab_cur = spw + 2 * SPW_D + par * kWideWords;
     int *stab = spw + 2 * SPW_D + (par ^ 1) * kWideWords;  // of the next batch
     const int e = CPLX ? b : b * 2 + sub;
-    // the next batch (clamped: the last iteration re-reads its own).  Looked up first thing: a batch-list load issued
-    // behind the q-data loads would make its use wait for all of them (vmcnt retires in order)
-    const int kn = k + stride;
+    // the next batch (clamped: the last iteration re-reads its own)
+    const int kn = b + stride;
     const bool more = kn < bend;
-    const int bn = more ? (a.blist ? a.blist[kn] : kn) : b;
+    const int bn = more ? kn : b;
 
     // q-data of this batch: consumed after the forward contraction (read once: non-temporal)
     d2v5 gq[2 * NG];
@@ -214,11 +211,6 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, 2) void nd_hex_stream5_kernel(
     line_out(C, ul);                                                                                   \
   }
     PA_S5_FWD(0);
-    if (QPOS == 1) {
-      __builtin_amdgcn_sched_barrier(0);
-      load_qdata();
-      __builtin_amdgcn_sched_barrier(0);
-    }
     PA_S5_FWD(1);
     if (QPOS == 2) {
       __builtin_amdgcn_sched_barrier(0);
@@ -274,12 +266,6 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, 2) void nd_hex_stream5_kernel(
 
     // x of the next batch: in flight during the (rest of the) transposed passes
     double xB[NPL];
-    if (GPOS == 0) {
-      __builtin_amdgcn_sched_barrier(0);
-      gather(wB, xB, stab, t);
-      settle(pB);
-      __builtin_amdgcn_sched_barrier(0);
-    }
     PA_S5_BWD(0);
     if (GPOS == 1) {
       __builtin_amdgcn_sched_barrier(0);
@@ -315,7 +301,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, 2) void nd_hex_stream5_kernel(
     }
     wave_sync();  // the LDS strip is reused by the next batch
     if (!more) break;
-    k = kn, b = bn, par ^= 1;
+    b = bn, par ^= 1;
 #pragma unroll
     for (int r = 0; r < NPL; r++) xv[r] = xB[r];
 #pragma unroll
@@ -361,7 +347,7 @@ static void launch5_gpos(const SubOp &so, NDStream5Args<P1> &a, hipStream_t s) {
   }();
   const int per_cu = wg_env > 0 ? wg_env : per_cu_query;
   const int per_xcd = std::max(1, device_cus5() / 8) * per_cu;
-  if (!a.blist) a.nbatch = CPLX ? so.ne : (so.ne + 1) / 2;  // (complex form: one element per wave)
+  a.nbatch = CPLX ? so.ne : (so.ne + 1) / 2;  // (complex form: one element per wave)
   if (a.nbatch == 0) return;
   a.chunk = (a.nbatch + 7) / 8;
   int wgx = std::max(1, std::min(per_xcd, (a.chunk + kWavesPerBlock - 1) / kWavesPerBlock));
@@ -373,29 +359,14 @@ static void launch5_gpos(const SubOp &so, NDStream5Args<P1> &a, hipStream_t s) {
 
 template <int P1, bool U, bool C, bool METRIC>
 static void launch5_variant(const SubOp &so, NDStream5Args<P1> &a, hipStream_t s) {
-  auto env = [](const char *name, int dflt) { return getenv(name) ? atoi(getenv(name)) : dflt; };
-  const int gpos = env("PALACE_AMD_STREAM5_GPOS", U ? 2 : 1);
-  if (a.nsplit >= 0) {  // split vectors: the default positions only
-    if constexpr (P1 == 4)
-      return launch5_gpos<P1, U, C, METRIC, (U ? 2 : 1), ((U && C) ? 2 : 0), false, true>(so, a, s);
-    else
-      return launch5_gpos<P1, U, C, METRIC, (U ? 2 : 1), 0, false, true>(so, a, s);
-  }
-  if constexpr (P1 == 4) {  // A/B switches of the order-4 kernels (scripts/time_p4.py)
-    const int qpos = env("PALACE_AMD_STREAM5_QPOS", (U && C) ? 2 : 0);
-#define PA_S5_LAUNCH(G, Q) launch5_gpos<P1, U, C, METRIC, G, Q>(so, a, s)
-#define PA_S5_Q(G) (qpos == 0 ? PA_S5_LAUNCH(G, 0) : qpos == 1 ? PA_S5_LAUNCH(G, 1) : PA_S5_LAUNCH(G, 2))
-    gpos == 2 ? PA_S5_Q(2) : PA_S5_Q(1);
-  } else {
-    if (gpos == 2)
-      launch5_gpos<P1, U, C, METRIC, 2, 0>(so, a, s);
-    else
-      launch5_gpos<P1, U, C, METRIC, 1, 0>(so, a, s);
-  }
+  constexpr int GPOS = U ? 2 : 1, QPOS = (P1 == 4 && U && C) ? 2 : 0;
+  if (a.nsplit >= 0)  // split vectors
+    return launch5_gpos<P1, U, C, METRIC, GPOS, QPOS, false, true>(so, a, s);
+  launch5_gpos<P1, U, C, METRIC, GPOS, QPOS>(so, a, s);
 }
 
 template <int P1>
-static void launch5_p(const SubOp &so, const double *x, double *y, bool masked, hipStream_t s, int phase, const SplitIO *split,
+static void launch5_p(const SubOp &so, const double *x, double *y, bool masked, hipStream_t s, const SplitIO *split,
                       bool all = false) {
   NDStream5Args<P1> a;
   a.nsplit = -1, a.xg0 = a.xg1 = nullptr, a.xg_sel = nullptr, a.yg = nullptr;
@@ -405,13 +376,7 @@ static void launch5_p(const SubOp &so, const double *x, double *y, bool masked, 
     a.xg0 = split->xg0 - split->n_true, a.xg1 = (split->xg1 ? split->xg1 : split->xg0) - split->n_true;
     a.xg_sel = split->sel, a.yg = split->yg - split->n_true;
   }
-  a.ne = so.ne;
-  a.blist = nullptr, a.nbatch = 0;
-  if (phase >= 0) {
-    PA_REQUIRE(so.d_blist[phase] || so.n_blist[phase] == 0, "interface batch lists missing");
-    a.blist = so.d_blist[phase], a.nbatch = so.n_blist[phase];
-    if (a.nbatch == 0) return;
-  }
+  a.ne = so.ne, a.nbatch = 0;
   a.idxw = so.d_idxc;
   a.perm = all ? so.d_perm_s_all : (masked ? so.d_perm_s_bc : so.d_perm_s);  // (all: no entry exclusive -- the fused smoother step)
   a.qdata = so.qd->d;
@@ -434,13 +399,13 @@ static void launch5_p(const SubOp &so, const double *x, double *y, bool masked, 
   }
 }
 
-void launch_nd_hex_stream5(const SubOp &so, const double *x, double *y, bool masked, hipStream_t s, int phase, const SplitIO *split,
+void launch_nd_hex_stream5(const SubOp &so, const double *x, double *y, bool masked, hipStream_t s, const SplitIO *split,
                            bool all) {
   switch (so.p) {
-    case 1: launch5_p<1>(so, x, y, masked, s, phase, split, all); break;
-    case 2: launch5_p<2>(so, x, y, masked, s, phase, split, all); break;
-    case 3: launch5_p<3>(so, x, y, masked, s, phase, split, all); break;
-    case 4: launch5_p<4>(so, x, y, masked, s, phase, split, all); break;
+    case 1: launch5_p<1>(so, x, y, masked, s, split, all); break;
+    case 2: launch5_p<2>(so, x, y, masked, s, split, all); break;
+    case 3: launch5_p<3>(so, x, y, masked, s, split, all); break;
+    case 4: launch5_p<4>(so, x, y, masked, s, split, all); break;
     default: throw Error("no five-point streaming H(curl) hex kernel for this order");
   }
 }
@@ -448,7 +413,7 @@ template <int P1>
 static void launch5_complex_p(const SubOp &sr, const SubOp &si, const double *xr, const double *xi, double *yr, double *yi,
                               double *ye_i, bool masked, hipStream_t s) {
   NDStream5Args<P1> a;
-  a.ne = sr.ne, a.blist = nullptr, a.nbatch = 0;
+  a.ne = sr.ne, a.nbatch = 0;
   a.idxw = sr.d_idxc;
   a.perm = masked ? sr.d_perm_s_bc : sr.d_perm_s;
   a.qdata = sr.qd->d;

@@ -246,14 +246,16 @@ inline void chunk_decode(const std::vector<RunChunk> &ch, size_t k, int &run, in
   off = nc ? lane - top : (int)(c.first & 15u) + lane;
 }
 
-// ---- run form of the transpose map of the dense-table path (pa_dense.hip) ------------------------------------------------------
+// ---- run form of the transpose map of the dense-table path ------------------------------------------------------------------
+// (round 4; the device gather by runs was measured no faster than the CSR form and removed after round 6 -- the builder stays,
+// checked on the CPU model by tests/cpu/stream_host_check.cpp)
 // E-vector position of local dof l of element e: ((e / 16) 4 KP + l) 16 + e % 16 -- consecutive local dofs of an element are 16
 // doubles apart.  A run = up to 16 consecutive L-dofs (ALL dofs: the dense gather owns every row) with the same number of copies,
 // each copy in the same element with local dofs that step by +1 or -1 (an edge seen against its orientation) and the same sign.
 //   hdr[run]  = {first dof | length - 1, first entry in rpos}
 //   rpos      = per run and copy (element order: the summation order of the CSR form): position of the run's FIRST dof in that copy
 //               | bit 30: the following dofs step backwards | bit 31: the copy enters with a minus sign
-//   code[d]   = run << 4 | offset (host checks; the device reads run_chunks(code))
+//   code[d]   = run << 4 | offset (host checks; a device gather would read run_chunks(code))
 constexpr uint32_t kDenseRunBack = 1u << 30, kDenseRunNeg = 1u << 31, kDenseRunPosMask = kDenseRunBack - 1u;
 inline void build_runs_dense(int ne, int P, int KP, int lsize, const int32_t *offsets, const uint8_t *orients,
                              std::vector<uint32_t> &code, std::vector<RunHdr> &hdr, std::vector<uint32_t> &rpos) {

@@ -108,25 +108,6 @@ def test_slab_ranks_with_the_replicated_ams_coarse_solve():
             assert abs(many[k] - one[k]) < 1e-6 * abs(one[k]), (world, k, many[k], one[k])
 
 
-def test_ranks_as_threads_with_halo_stream_overlap():
-    """The same with PALACE_AMD_OVERLAP=1: ghosts exchanged on the second stream while the interior element batches run."""
-    import os
-    import subprocess
-    import sys
-
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    code = ("import sys; sys.path.insert(0, %r)\n"
-            "from tests.test_multirank_local_gpu import _run\n"
-            "one, four = _run(1, 3, True), _run(4, 3, True)\n"
-            "assert four['converged'] and four['n'] == one['n'] and abs(four['iterations'] - one['iterations']) <= 1\n"
-            "for k in ('bb', 'bAb', 'zz'):\n"
-            "    assert abs(four[k] - one[k]) < 1e-11 * abs(one[k]), (k, four[k], one[k])\n"
-            "print('OK')\n") % root
-    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=600,
-                       env=dict(os.environ, PALACE_AMD_OVERLAP="1"))
-    assert r.returncode == 0 and "OK" in r.stdout, r.stdout + r.stderr
-
-
 # ---- tetrahedra under a general (recursive coordinate bisection) element partition -------------------------------------------
 
 def _tet_rank_main(group, rank, world, hiptmair, out, errors, coarse="cg"):
