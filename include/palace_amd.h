@@ -363,7 +363,7 @@ int pa_op_is_symmetric(const pa_op *op);
 /* SURVEY.md 8(f)-1, ComplexWrapperOperator::Mult (linalg/operator.cpp:98-134) for A = A_r + i A_i: y_r = A_r x_r - A_i x_i,
  * y_i = A_i x_r + A_r x_i in ONE pass over the element data instead of four applies.  Available (pa_op_complex_fused = 1) when both
  * operators are single H(curl) tensor-hexahedron blocks on the same space and geometry in the streaming metric form (isotropic
- * materials, Q1 = 4) -- e.g. op_r from pa_op_add_sub_sum for K - w^2 M and op_i = w C: they then share index arrays and
+ * materials; Q1 = 4 with p <= 3, Q1 = 5 with p <= 4) -- e.g. op_r from pa_op_add_sub_sum for K - w^2 M and op_i = w C: they then share index arrays and
  * quadrature data and differ by per-element scalar coefficients, so the kernel carries the real and the imaginary part of x in
  * neighbouring lane groups and multiplies by (a_r + i a_i) at the quadrature points.  ess_policy: -1 plain; 0 / 1: with the
  * essential list fused into op_r (pa_op_set_essential), entries read as zero and rows set to 0 / x (the real ParOperator's
@@ -373,7 +373,8 @@ int pa_op_is_symmetric(const pa_op *op);
  * the matrix-core products carry 8 elements x {real, imaginary} part; meshes mixing straight and curved elements and the essential
  * list too (round 5).
  * Round 5, hexahedra with ANISOTROPIC materials (return value 1 as well): both operators in the packed form (symmetric D of each
- * term at every point, 6 or 12 doubles, Q1 = 4, p <= 3) -- the even lane groups load the real operator's D, the odd ones the
+ * term at every point, 6 or 12 doubles; Q1 = 4 with p <= 3, and Q1 = 5 with p <= 4: order 4 and the p-coarsened levels of an
+ * order-4 problem) -- the lane groups (Q1 = 5: the wave halves) of the real part load the real operator's D, the others the
  * imaginary operator's, each applies its D to both parts of the quadrature values and hands over the product that belongs to the
  * other part; every byte of both operators' D read once.
  * Return values 2 and 3 (3: hexahedral form): the FIRST sub-operators of op_r and op_i pair up in the one pass; every further
@@ -382,7 +383,8 @@ int pa_op_is_symmetric(const pa_op *op);
 int pa_op_complex_fused(const pa_op *op_r, const pa_op *op_i);
 int pa_op_mult_complex(pa_op *op_r, pa_op *op_i, const double *xr, const double *xi, double *yr, double *yi, int ess_policy,
                        void *stream);
-/* 1 if y = A x runs on the streaming kernels (single tensor-product block, Q1 = 4, packed q-data): callers choosing between
+/* 1 if y = A x runs on the streaming kernels (single tensor-product block; H(curl): Q1 = 4 with p <= 3 or Q1 = 5 with p <= 4, metric
+ * form or packed symmetric q-data -- one term, or curl-curl + mass with twelve doubles per point): callers choosing between
  * pa_op_mult2 and two pa_op_mult calls prefer the latter then */
 int pa_op_streams(const pa_op *op);
 /* Affine-element compression of the streaming H(curl) hex kernel (round 6): an element with a constant Jacobian has

@@ -1198,9 +1198,11 @@ bool nd_hex_stream_complex_ok(const SubOp &sr, const SubOp &si) {
     return so.iso && ((so.q1d == 4 && so.p <= 3) || (so.q1d == 5 && so.p <= 4 && nd_hex_stream5_ok(so))) && !so.geom->h_attr.empty();
   };
   const bool metric = iso_ok(sr) && iso_ok(si) && sr.d_idxc && sr.d_coef_s && sr.qd && sr.qd->metric;
-  // packed form (anisotropic materials, four points per direction; round 5): each operator's own packed symmetric D, 6 or 12 per point
+  // packed form (anisotropic materials; four points per direction: round 5, five: pa_nd_hex_stream5.hip): each operator's own packed
+  // symmetric D, 6 or 12 per point
   auto packed_ok = [](const SubOp &so) {
-    return so.q1d == 4 && so.p <= 3 && so.qd && !so.qd->metric && so.qd->ncomp == (so.qf == PA_QF_HDIVMASS_33 ? 12 : 6);
+    return ((so.q1d == 4 && so.p <= 3) || (so.q1d == 5 && so.p <= 4 && nd_hex_stream5_ok(so))) && so.qd && !so.qd->metric &&
+           so.qd->ncomp == (so.qf == PA_QF_HDIVMASS_33 ? 12 : 6);
   };
   const bool packed = packed_ok(sr) && packed_ok(si) && sr.d_idxc;
   if (!metric && !packed) return false;

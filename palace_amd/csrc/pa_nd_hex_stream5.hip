@@ -13,6 +13,7 @@
 //   * the run-compressed index block (48 words) is fetched with two loads per lane and decoded from LDS;
 //   * q-data [ncomp][126] per element: a lane reads its column as two 16-byte pairs and one double (nd_qd_offset).
 #include <algorithm>
+#include <type_traits>
 
 #include "pa_nd_hex_core.hpp"
 
@@ -37,17 +38,32 @@ struct NDStream5Args {
   const unsigned long long *xg_sel;
   double *yg;
   NDTab<P1, 5> tab;
+  // complex form on packed D (anisotropic materials): q-data of the imaginary operator, and where the mass / curl-curl rows of each
+  // operator start in its packed block (-1: the operator has no such term), rows per point (6 or 12); as NDStreamArgs,
+  // pa_nd_hex_stream.hip.  (Behind the tables: the kernel arguments of the other forms stay where they were.)
+  const double *qdata1;
+  int qm[2], qc[2], qn[2];
 };
 
 // QPOS: where the q-data of the batch is requested: 0 at the top of the batch, 2 after the second forward
 // component (later = shorter live range of its 60 - 70 registers; curl-curl + mass at p = 4 does not fit 256 otherwise)
+// Packed D of BOTH terms (!METRIC && USE_U && USE_C; anisotropic materials): twelve rows, 120 registers per lane.  They arrive as
+// two blocks of six: the MASS rows are requested at QPOS and are in flight during the forward passes, the CURL-CURL rows right
+// behind the last forward pass, and the D stage multiplies U by the mass block at all five points first and CU by the curl-curl
+// block after it, so the second request has the first block's products (and the other wave of the SIMD) in front of it.  The real
+// kernel (not the complex one, 250 - 256 registers) has room to request some or all curl-curl rows with the mass rows; measured:
+// no gain at p = 4, 1.5 - 9 % slower at p < 4.
 // CPLX: y = (A_r + i A_i)(x_r + i x_i) in one pass (pa_op_mult_complex; the complex form of the four-point kernel, DESIGN.md
 // 3.1c, carried over): ONE element per wave, its two 32-lane halves hold the real and the imaginary part of x / y; both read
 // the same index block and q-data, the parts meet at the D stage (the coefficients are per-element scalars in the metric
 // form: the half's own values times the real coefficient -/+ the other half's times the imaginary one).
+// CPLX on packed D (!METRIC): the two operators' symmetric D share no geometric factor, so the lower half loads the REAL operator's
+// blocks and the upper half the IMAGINARY operator's (a.qdata / a.qdata1, rows a.qm / a.qc of a.qn: every byte of both read once);
+// each half applies its D to BOTH parts of the quadrature values, keeps the product with the real part and hands the product with
+// the imaginary part across: y_r = D_r u_r - D_i u_i, y_i = D_i u_r + D_r u_i (the round-5 construction of the four-point kernel).
 template <int P1, bool USE_U, bool USE_C, bool METRIC, int GPOS, int QPOS, bool CPLX = false, bool SPLIT = false>
 __global__ __launch_bounds__(64 * kWavesPerBlock, 2) void nd_hex_stream5_kernel(const NDStream5Args<P1> a) {
-  static_assert(!CPLX || (USE_U && USE_C && METRIC), "the complex form is the metric curl-curl + mass kernel");
+  static_assert(!CPLX || (USE_U && USE_C), "the complex form is built on the curl-curl + mass kernels");
   static_assert(!(CPLX && SPLIT), "no split-vector form of the complex kernel");
   constexpr int Q1 = 5;
   using L = NDLayoutInPlace<P1, Q1>;  // (LDS limits the resident waves here)
@@ -60,6 +76,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, 2) void nd_hex_stream5_kernel(
   constexpr int NC = P1 + 1, PP = 3 * P1 * NC * NC, NPL = (PP + 31) / 32, NPK = (NPL + 1) / 2;
   constexpr int NG = METRIC ? (USE_U ? 7 : 6) : 6 * ((USE_U ? 1 : 0) + (USE_C ? 1 : 0));
   constexpr int CS = 126;  // nd_qd_cstride(5)
+  constexpr bool PK2 = !METRIC && USE_U && USE_C;  // packed D of both terms: two blocks of six rows
   constexpr bool EARLY_IDX = P1 < 4;
   // LDS per element (doubles): contraction buffers | element dofs in tensor order (E / E^T staging; its own strip, so that a
   // component's dofs are read just before its forward passes and written back right after its transposed ones instead of
@@ -158,7 +175,25 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, 2) void nd_hex_stream5_kernel(
       if (METRIC) ce = reinterpret_cast<const d2v5 *>(a.coef)[e];
       if (CPLX) ci = reinterpret_cast<const d2v5 *>(a.coef1)[e];
     };
-    if (QPOS == 0) load_qdata();
+    // packed D of both terms: block f (0: mass rows, 1: curl-curl rows) of this half's operator into gq / g4 [6 f, 6 f + 6)
+    auto load_block = [&](auto fc) {
+      constexpr int f = decltype(fc)::value;
+      const bool im = CPLX && sub;
+      const int qn = CPLX ? (im ? a.qn[1] : a.qn[0]) : 12;
+      const int o = CPLX ? (f ? (im ? a.qc[1] : a.qc[0]) : (im ? a.qm[1] : a.qm[0])) : 6 * f;
+      const double *g = (im ? a.qdata1 : a.qdata) + ((size_t)e * qn + (o >= 0 ? o : 0)) * CS;
+      const d2v5 zero = {0.0, 0.0};
+#pragma unroll
+      for (int c = 0; c < 6; c++) {
+        const d2v5 *gp = reinterpret_cast<const d2v5 *>(g + c * CS) + tc;
+        gq[2 * (6 * f + c)] = (!CPLX || o >= 0) ? __builtin_nontemporal_load(&gp[0]) : zero;
+        gq[2 * (6 * f + c) + 1] = (!CPLX || o >= 0) ? __builtin_nontemporal_load(&gp[25]) : zero;
+        g4[6 * f + c] = (!CPLX || o >= 0) ? __builtin_nontemporal_load(&g[c * CS + 100 + tc]) : 0.0;
+      }
+    };
+    if (QPOS == 0) {
+      if constexpr (PK2) load_block(std::integral_constant<int, 0>{}); else load_qdata();
+    }
 
     // E: sorted entries into their tensor-order slots (x of this batch was requested during the previous one)
 #pragma unroll
@@ -214,10 +249,15 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, 2) void nd_hex_stream5_kernel(
     PA_S5_FWD(1);
     if (QPOS == 2) {
       __builtin_amdgcn_sched_barrier(0);
-      load_qdata();
+      if constexpr (PK2) load_block(std::integral_constant<int, 0>{}); else load_qdata();
       __builtin_amdgcn_sched_barrier(0);
     }
     PA_S5_FWD(2);
+    if constexpr (PK2) {
+      __builtin_amdgcn_sched_barrier(0);
+      load_block(std::integral_constant<int, 1>{});
+      __builtin_amdgcn_sched_barrier(0);
+    }
 
     if (!EARLY_IDX) {
       __builtin_amdgcn_sched_barrier(0);
@@ -226,8 +266,43 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, 2) void nd_hex_stream5_kernel(
     }
 
     // D at the five points of this lane's column
+    if constexpr (PK2) {
+      // block by block: the mass rows on U at the five points, then the curl-curl rows (requested last) on CU
 #pragma unroll
-    for (int qz = 0; qz < Q1; qz++) {
+      for (int f = 0; f < 2; f++) {
+        double(&W)[3][Q1] = f ? CU : U;
+#pragma unroll
+        for (int qz = 0; qz < Q1; qz++) {
+          double H[6];
+#pragma unroll
+          for (int c = 0; c < 6; c++) H[c] = qz < 4 ? gq[2 * (6 * f + c) + (qz >> 1)][qz & 1] : g4[6 * f + c];
+          if (CPLX) {
+            // this half's D on both parts: the product with the real part stays (D_r u_r for y_r, D_i u_r for y_i), the product
+            // with the imaginary part goes to the other half (D_i u_i, subtracted from y_r; D_r u_i, added to y_i)
+            const bool im = sub;
+            double ur[3], ui[3], ar[3], ai[3];
+#pragma unroll
+            for (int c = 0; c < 3; c++) {
+              const double pv = __shfl_xor(W[c][qz], 32, 64);
+              ur[c] = im ? pv : W[c][qz], ui[c] = im ? W[c][qz] : pv;
+            }
+            sym_mv(H, ur[0], ur[1], ur[2], ar[0], ar[1], ar[2]);
+            sym_mv(H, ui[0], ui[1], ui[2], ai[0], ai[1], ai[2]);
+#pragma unroll
+            for (int c = 0; c < 3; c++) {
+              const double got = __shfl_xor(ai[c], 32, 64);
+              W[c][qz] = im ? ar[c] + got : ar[c] - got;
+            }
+            __builtin_amdgcn_sched_barrier(0);  // one point at a time: short live ranges
+          } else {
+            sym_mv(H, W[0][qz], W[1][qz], W[2][qz], W[0][qz], W[1][qz], W[2][qz]);
+          }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    }
+#pragma unroll
+    for (int qz = 0; qz < (PK2 ? 0 : Q1); qz++) {
       double H[NG];
 #pragma unroll
       for (int c = 0; c < NG; c++) H[c] = qz < 4 ? gq[2 * c + (qz >> 1)][qz & 1] : g4[c];
@@ -315,7 +390,8 @@ bool nd_hex_stream5_ok(const SubOp &so) {
   // (read at every operator creation, not cached: tests build both forms in one process)
   if (getenv("PALACE_AMD_STREAM5") && atoi(getenv("PALACE_AMD_STREAM5")) == 0) return false;
   if (so.fe_type != PA_FE_HCURL || so.q1d != 5 || so.p > 4 || !so.qd || !so.d_ye || !so.d_perm_x) return false;
-  return so.qd->metric || so.qd->ncomp == 6;
+  // (packed D of both terms -- anisotropic materials, twelve rows per point -- for the curl-curl + mass QFunction only)
+  return so.qd->metric || so.qd->ncomp == 6 || (so.qd->ncomp == 12 && so.qf == PA_QF_HDIVMASS_33);
 }
 
 static int device_cus5() {
@@ -380,6 +456,8 @@ static void launch5_p(const SubOp &so, const double *x, double *y, bool masked, 
   a.idxw = so.d_idxc;
   a.perm = all ? so.d_perm_s_all : (masked ? so.d_perm_s_bc : so.d_perm_s);  // (all: no entry exclusive -- the fused smoother step)
   a.qdata = so.qd->d;
+  a.qdata1 = nullptr;
+  for (int g = 0; g < 2; g++) a.qm[g] = a.qc[g] = -1, a.qn[g] = 0;
   a.coef = so.d_coef_s, a.coef1 = nullptr;
   a.x = x, a.y = y, a.ye = so.d_ye;
   a.x1 = nullptr, a.y1 = nullptr, a.ye1 = nullptr;
@@ -392,8 +470,8 @@ static void launch5_p(const SubOp &so, const double *x, double *y, bool masked, 
       if (m) launch5_variant<P1, true, false, true>(so, a, s); else launch5_variant<P1, true, false, false>(so, a, s);
       break;
     case PA_QF_HDIVMASS_33:
-      PA_REQUIRE(m, "streaming curl-curl + mass kernel needs the metric form");
-      launch5_variant<P1, true, true, true>(so, a, s);
+      // (packed D of both terms, anisotropic materials: the mass rows at QPOS, the curl-curl rows behind the forward passes)
+      if (m) launch5_variant<P1, true, true, true>(so, a, s); else launch5_variant<P1, true, true, false>(so, a, s);
       break;
     default: throw Error("QFunction not available for H(curl) hexahedra");
   }
@@ -420,10 +498,19 @@ static void launch5_complex_p(const SubOp &sr, const SubOp &si, const double *xr
   a.coef = sr.d_coef_s, a.coef1 = si.d_coef_s;
   a.x = xr, a.x1 = xi, a.y = yr, a.y1 = yi, a.ye = sr.d_ye, a.ye1 = ye_i;
   a.nsplit = -1, a.xg0 = a.xg1 = nullptr, a.xg_sel = nullptr, a.yg = nullptr;
-  if constexpr (P1 == 4)
-    launch5_gpos<P1, true, true, true, 2, 2, true>(sr, a, s);
-  else
-    launch5_gpos<P1, true, true, true, 2, 0, true>(sr, a, s);
+  a.qdata1 = nullptr;
+  const SubOp *ops[2] = {&sr, &si};
+  for (int g = 0; g < 2; g++) {  // (pa_nd_hex.hip: packed q-data holds the mass block first, then the curl-curl block)
+    const int qf = ops[g]->qf;
+    a.qn[g] = ops[g]->qd->ncomp;
+    a.qm[g] = (qf == PA_QF_HCURL_33 || qf == PA_QF_HDIVMASS_33) ? 0 : -1;
+    a.qc[g] = qf == PA_QF_HDIV_33 ? 0 : (qf == PA_QF_HDIVMASS_33 ? 6 : -1);
+  }
+  constexpr int QPOS = P1 == 4 ? 2 : 0;
+  if (sr.qd->metric) return launch5_gpos<P1, true, true, true, 2, QPOS, true>(sr, a, s);
+  // packed D (anisotropic materials): each half of the wave reads its own operator's blocks
+  a.qdata1 = si.qd->d;
+  launch5_gpos<P1, true, true, false, 2, QPOS, true>(sr, a, s);
 }
 
 // the complex form at five points per direction (pa_op_mult_complex; eligibility: nd_hex_stream_complex_ok)
