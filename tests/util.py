@@ -92,6 +92,101 @@ class FastParOperatorOracle(po.ParOperatorOracle):
         return self._diag
 
 
+def hex_rotations():
+    """The 24 proper rotations of the reference cube as permutations of the 27 lattice nodes i + 3 j + 9 k (rotation about
+    the centre node): returns (R [24, 3, 3] signed permutation matrices with determinant +1, perm [24, 27]) where the rotated
+    element's node at lattice position n' = R (n - 1) + 1 is the original element's node at n: elem_nodes' = elem_nodes[perm]."""
+    import itertools
+
+    mats, perms = [], []
+    n = np.array([[i, j, k] for k in range(3) for j in range(3) for i in range(3)])  # row l = i + 3 j + 9 k
+    for axes in itertools.permutations(range(3)):
+        for signs in itertools.product((1, -1), repeat=3):
+            R = np.zeros((3, 3), dtype=np.int64)
+            for r in range(3):
+                R[r, axes[r]] = signs[r]
+            if round(np.linalg.det(R)) != 1:
+                continue
+            new = (n - 1) @ R.T + 1
+            perm = np.empty(27, dtype=np.int64)
+            perm[new[:, 0] + 3 * new[:, 1] + 9 * new[:, 2]] = np.arange(27)
+            mats.append(R)
+            perms.append(perm)
+    assert len(mats) == 24 and len({tuple(q) for q in perms}) == 24
+    return np.array(mats), np.array(perms)
+
+
+def rotate_elements(mesh, rot_ids):
+    """The same mesh with element e handed over in its rotation rot_ids[e] (an index into hex_rotations()): same nodes, same
+    attributes, the 27 node ids of every element permuted.  Vertices, edges and faces are numbered from the node ids alone, so
+    they keep their numbers; only the element's own frame (and with it the order and sign of its interior dofs, the local
+    position of every edge and face, and the class (ou, ov, swap) of every face) changes."""
+    from palace_amd.fem.mesh import HexMesh
+
+    _, perms = hex_rotations()
+    rot_ids = np.broadcast_to(np.asarray(rot_ids, dtype=np.int64), (mesh.ne,))
+    nodes = np.take_along_axis(mesh.elem_nodes, perms[rot_ids], axis=1)
+    out = HexMesh(x=mesh.x, elem_nodes=nodes, attr=mesh.attr, bdr_faces=mesh.bdr_faces, bdr_attr=mesh.bdr_attr)
+    out.check()
+    assert out.nv == mesh.nv and np.array_equal(out.edge_verts, mesh.edge_verts) and np.array_equal(out.face_verts, mesh.face_verts)
+    return out
+
+
+def element_runs(elem_dof):
+    """Number of maximal runs of consecutive dofs in every element's sorted dof list [NE]: what pack_index / pack_index_wide
+    (palace_amd/csrc/pa_stream_host.hpp) count against the capacity of the streaming index."""
+    d = np.sort(np.asarray(elem_dof, dtype=np.int64), axis=1)
+    return 1 + (np.diff(d, axis=1) != 1).sum(axis=1)
+
+
+def renumbered(space, perm):
+    """The same space with dof d renamed perm[d] (a permutation of range(ndofs)): native_restriction() and ess_dofs() read
+    elem_dof_lex and follow; a vector x of the original numbering becomes x' with x'[perm] = x."""
+    import copy
+
+    perm = np.asarray(perm)
+    assert perm.shape == (space.ndofs,) and np.array_equal(np.sort(perm), np.arange(space.ndofs))
+    out = copy.copy(space)
+    out.elem_dof_lex = perm[space.elem_dof_lex].astype(np.int32)
+    return out
+
+
+def seeded_rotations(ne, seed):
+    """A rotation per element: every one of the 24 as often as ne admits, in a seeded random order."""
+    return np.random.default_rng(seed).permutation(np.arange(ne) % 24)
+
+
+def fragmenting_permutation(space, where, target):
+    """A renumbering that breaks the dof runs of an element until the largest run count on the mesh is `target`: single dofs at
+    offsets 1, 3, 5, ... (each splits a run in three) are exchanged between two blocks of the natural numbering that lie far
+    apart -- where = "interior": the interior blocks of the element with the most runs, e0, and of the element 40 further on
+    (exclusive dofs: the direct store of the streaming kernels); where = "faces": the blocks of interior faces of e0 and of faces
+    of that other element (shared dofs: the E-vector and the run gather).  Returns (perm, runs per element after it)."""
+    mesh = space.mesh
+    e0 = int(np.argmax(element_runs(space.elem_dof_lex)))
+    e1 = (e0 + 40) % mesh.ne
+    if where == "interior":
+        n = (space.ndofs - space.int_base) // mesh.ne
+        pairs = [(space.int_base + e0 * n, space.int_base + e1 * n)]
+    else:
+        n = (space.int_base - space.face_base) // mesh.nfaces
+        inner = lambda e: [int(f) for f in mesh.elem_faces[e] if not mesh.boundary_face_mask[f]]  # noqa: E731
+        theirs = [f for f in inner(e1) if f not in set(mesh.elem_faces[e0])]
+        pairs = [(space.face_base + a * n, space.face_base + b * n) for a, b in zip(inner(e0), theirs)]
+    perm = np.arange(space.ndofs)
+    runs = element_runs(space.elem_dof_lex)
+    for a, b in pairs:
+        for i in range(1, n - 1, 2):
+            if runs.max() >= target:
+                break
+            trial = perm.copy()
+            trial[a + i], trial[b + i] = perm[b + i], perm[a + i]
+            r = element_runs(trial[space.elem_dof_lex])
+            if r.max() <= target:
+                perm, runs = trial, r
+    return perm, runs
+
+
 def nd_interpolate(space, F):
     """Nodal interpolant of a smooth vector field F(x) -> [.., 3] in an NDHexSpace-like space:
     dof = F(x_node) . (J e_c) (covariant Piola), written through the signed element->dof map.
