@@ -114,9 +114,11 @@ enum pa_qfunction {
 enum pa_fe_type {
   PA_FE_H1 = 0,
   PA_FE_HCURL = 1,
-  PA_FE_HDIV = 2 /* dense path only: RT mass (Interp + PA_QF_HDIV_33 | _22 | _32 | _21 | _31 by the geometry data, interp = values
-                    [dim Q][P]), div-div (Div | Weight + PA_QF_L2_1, fem/integ/divdiv.cpp; deriv = divergence [Q][P]), both in
-                    one pass (Interp | Div | Weight + PA_QF_L2MASS_*, fem/integ/divdivmass.cpp); mixed mass with an H(curl) space */
+  PA_FE_HDIV = 2 /* RT mass (Interp + PA_QF_HDIV_33 | _22 | _32 | _21 | _31 by the geometry data, interp = values [dim Q][P]),
+                    div-div (Div | Weight + PA_QF_L2_1, fem/integ/divdiv.cpp; deriv = divergence [Q][P]), both in one pass
+                    (Interp | Div | Weight + PA_QF_L2MASS_*, fem/integ/divdivmass.cpp).  Dense path (pa_dense_basis_desc): every
+                    geometry, and the mixed mass with an H(curl) space.  Tensor path (pa_basis_desc, pa_op_add_sub): hexahedra,
+                    the three 3-D operators PA_QF_HDIV_33, PA_QF_L2_1 and PA_QF_L2MASS_33, sum-factorised (pa_rt_hex.hip) */
 };
 
 /*
@@ -158,6 +160,19 @@ typedef struct {
  *   Tensor index of HCURL dofs: x-block i + p (j + (p+1) k), then y-block i + (p+1)(j + p k), then
  *   z-block i + (p+1)(j + (p+1) k), the open direction having p entries.
  *   interp     optional dense [qcomp*Q][P] (native dof order), deriv optional dense curl/grad [3*Q][P]
+ *
+ * HDIV (Raviart-Thomas hexahedra, MFEM's RT_HexahedronElement of order p - 1): P = 3 p^2 (p+1).  Bc, Gc and Bo are the fields
+ * above; component c is closed along c and open along the other two directions, its divergence takes Gc along c.
+ *   Tensor index of HDIV dofs: x-block (cb_i ob_j ob_k e_x) i + (p+1)(j + p k), then y-block (ob_i cb_j ob_k e_y)
+ *   p^2 (p+1) + i + p (j + (p+1) k), then z-block (ob_i ob_j cb_k e_z) 2 p^2 (p+1) + i + p (j + p k).
+ *   dof_map    as for HCURL: signed tensor -> native map (RT_HexahedronElement::GetDofMap() has negative entries);
+ *              `orients` of the restriction are the sign flips of the oriented restriction, in native order
+ *   interp     optional dense values [3*Q][P], deriv optional dense DIVERGENCE [Q][P]; both checked like the others
+ *   QFunctions PA_QF_HDIV_33 (VectorFEMassIntegrator; Interp; 3 x 3 context), PA_QF_L2_1 (DivDivIntegrator; Div; scalar
+ *              context), PA_QF_L2MASS_33 (DivDivMassIntegrator; Interp | Div; pair context: the 3 x 3 mass first, then the
+ *              scalar); PA_EVAL_WEIGHT is ignored on either side.  (order, q1d): the pairs of the H(curl) kernels.
+ *   No streaming, split-vector, complex, fused-step or coarsened form: pa_op_streams / pa_op_supports_split /
+ *   pa_op_complex_fused answer 0, pa_op_prepare_fused_step reports none, pa_op_coarsen and pa_op_add_sub_sum refuse.
  */
 typedef struct {
   int32_t fe_type;

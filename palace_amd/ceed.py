@@ -18,6 +18,7 @@ from . import lib as _lib
 from .fem.basis1d import Tables1D
 from .fem.fespace import H1HexSpace, NDHexSpace
 from .fem.mesh import HexMesh, _q2_1d
+from .fem.rthex import RTHexSpace
 
 QF_HDIV_33, QF_HCURL_33, QF_HDIVMASS_33, QF_HCURLMASS_33, QF_H1_1, QF_HCURL_22, QF_L2_1, QF_HDIVMASS_22, QF_HCURL_32 = range(9)
 QF_HCURLHDIV_ERROR_33, QF_HDIVHCURL_ERROR_33 = 11, 12
@@ -224,7 +225,7 @@ class DenseBlock:
         return r, b
 
 
-def _basis_desc(space, q1d, dense=None):
+def _basis_desc(space, q1d, dense=None, dof_map=None):
     p = space.p
     t = Tables1D(p, q1d)
     keep = dict(Bc=np.ascontiguousarray(t.Bc), Gc=np.ascontiguousarray(t.Gc),
@@ -232,9 +233,14 @@ def _basis_desc(space, q1d, dense=None):
     if isinstance(space, NDHexSpace):
         keep["dof_map"] = np.ascontiguousarray(space.dof_map_native(), dtype=np.int32)
         fe = FE_HCURL
+    elif isinstance(space, RTHexSpace):  # lexicographic restriction; dense = (values [3, Q, P], divergence [Q, P])
+        keep["dof_map"] = None
+        fe = FE_HDIV
     else:
         keep["dof_map"] = None
         fe = FE_H1
+    if dof_map is not None:
+        keep["dof_map"] = np.ascontiguousarray(dof_map, dtype=np.int32)
     interp = deriv = None
     if dense is not None:
         keep["interp"] = interp = np.ascontiguousarray(dense[0])
@@ -244,11 +250,23 @@ def _basis_desc(space, q1d, dense=None):
     return desc, keep
 
 
-def _restriction_desc(space):
-    if isinstance(space, NDHexSpace):
+def _restriction_desc(space, dof_map=None, orients=None):
+    if dof_map is not None:
+        # add_integrator's dof_map= / orients= override: tensor entry l of the element is native entry |dof_map[l]| -- the
+        # space's lexicographic offsets move there; the orientation flags are the caller's, in that native order
+        nat = np.asarray(dof_map, dtype=np.int64)
+        nat = np.where(nat < 0, -1 - nat, nat)
+        off = np.empty_like(space.elem_dof_lex)
+        off[:, nat] = space.elem_dof_lex
+        keep = dict(off=np.ascontiguousarray(off, dtype=np.int32),
+                    ori=None if orients is None else np.ascontiguousarray(orients, dtype=np.uint8))
+    elif isinstance(space, NDHexSpace):
         off, ori = space.native_restriction()
         keep = dict(off=np.ascontiguousarray(off, dtype=np.int32),
                     ori=np.ascontiguousarray(ori, dtype=np.uint8))
+    elif isinstance(space, RTHexSpace):
+        keep = dict(off=np.ascontiguousarray(space.elem_dof_lex, dtype=np.int32),
+                    ori=np.ascontiguousarray(space.elem_sign_lex < 0, dtype=np.uint8))
     else:
         keep = dict(off=np.ascontiguousarray(space.elem_dof_lex, dtype=np.int32), ori=None)
     desc = _lib.RestrictionDesc(space.mesh.ne, space.P, space.ndofs, _ptr(keep["off"]), _ptr(keep["ori"]))
@@ -287,9 +305,11 @@ class Operator:
         if handle is None:
             _lib.check(_lib.load().pa_op_create(height, width, C.byref(self.handle)))
 
-    def add_integrator(self, geom: GeomFactorData, space, qf, ctx_blob, ops, dense=None, test_ops=None):
-        r, k1 = _restriction_desc(space)
-        b, k2 = _basis_desc(space, geom.q1d, dense)
+    def add_integrator(self, geom: GeomFactorData, space, qf, ctx_blob, ops, dense=None, test_ops=None, dof_map=None, orients=None):
+        """dof_map / orients: hand the elements of a lexicographic space over in another native order -- a signed tensor ->
+        native map [P] and the orientation flags [NE, P] in that order (the default is the space's own order and flags)."""
+        r, k1 = _restriction_desc(space, dof_map, orients)
+        b, k2 = _basis_desc(space, geom.q1d, dense, dof_map)
         ctx = np.ascontiguousarray(ctx_blob)
         _lib.check(_lib.load().pa_op_add_sub(self.handle, geom.handle, C.byref(r), C.byref(b),
                                              C.c_int32(qf), _ptr(ctx), C.c_size_t(ctx.nbytes),
@@ -549,3 +569,23 @@ def diffusionmass_operator(geom, h1: H1HexSpace, ctx_mass1, ctx_diff, dense=None
     ctx = np.concatenate([ctx_mass1, ctx_diff])
     return Operator(h1.ndofs, h1.ndofs).add_integrator(
         geom, h1, QF_HCURLMASS_33, ctx, EVAL_GRAD | EVAL_INTERP, dense).finalize()
+
+
+def rtmass_operator(geom, rt: RTHexSpace, ctx, dense=None):
+    """VectorFEMassIntegrator on an H(div) space (fem/integ/vecfemass.cpp): f_apply_hdiv_33, Interp/Interp; sum-factorised
+    (pa_rt_hex.hip).  dense = (values [3, Q, P], divergence [Q, P]): checked against the 1-D tables."""
+    return Operator(rt.ndofs, rt.ndofs).add_integrator(geom, rt, QF_HDIV_33, ctx, EVAL_INTERP, dense).finalize()
+
+
+def divdiv_operator(geom, rt: RTHexSpace, ctx1, dense=None):
+    """DivDivIntegrator (fem/integ/divdiv.cpp): f_apply_l2_1 on the divergence, Div | Weight, scalar (dim-1) context."""
+    return Operator(rt.ndofs, rt.ndofs).add_integrator(geom, rt, QF_L2_1, ctx1, EVAL_DIV | EVAL_WEIGHT, dense,
+                                                       test_ops=EVAL_DIV).finalize()
+
+
+def divdivmass_operator(geom, rt: RTHexSpace, ctx_mass, ctx1, dense=None):
+    """DivDivMassIntegrator (fem/integ/divdivmass.cpp): f_apply_l2mass_33, Interp | Div | Weight; the paired context is the
+    3 x 3 mass first, then the scalar of the divergence term."""
+    ctx = np.concatenate([ctx_mass, ctx1])
+    return Operator(rt.ndofs, rt.ndofs).add_integrator(geom, rt, QF_L2MASS_33, ctx, EVAL_INTERP | EVAL_DIV | EVAL_WEIGHT, dense,
+                                                       test_ops=EVAL_INTERP | EVAL_DIV).finalize()

@@ -382,9 +382,12 @@ FiniteElementSpace::FiniteElementSpace(const Context &ctx, const Mesh &mesh, int
                                        const Halo *halo)
     : ctx_(&ctx), mesh_(&mesh), fe_type_(fe_type), order_(order), vsize_(vsize), true_vsize_(n_true < 0 ? vsize : n_true),
       halo_(halo) {
-  PA_REQUIRE(fe_type == PA_FE_HCURL || fe_type == PA_FE_H1, "H(curl) or H1 space expected");
+  PA_REQUIRE(fe_type == PA_FE_HCURL || fe_type == PA_FE_H1 || fe_type == PA_FE_HDIV, "H(curl), H1 or H(div) space expected");
   PA_REQUIRE(order >= 1 && offsets, "invalid finite element space description");
-  elem_size_ = fe_type == PA_FE_HCURL ? 3 * order * (order + 1) * (order + 1) : (order + 1) * (order + 1) * (order + 1);
+  // (Raviart-Thomas hexahedra: closed along the component, open along the other two directions -- the same 1-D tables)
+  elem_size_ = fe_type == PA_FE_HCURL  ? 3 * order * (order + 1) * (order + 1)
+               : fe_type == PA_FE_HDIV ? 3 * order * order * (order + 1)
+                                       : (order + 1) * (order + 1) * (order + 1);
   const size_t n = (size_t)mesh.GetNE() * elem_size_;
   offsets_.assign(offsets, offsets + n);
   if (orients) orients_.assign(orients, orients + n);
@@ -501,6 +504,9 @@ const Operator &FiniteElementSpaceHierarchy::BuildProlongationAtLevel(std::size_
       // tensor elements: child = an axis-aligned box o + s x of the parent's reference cube (corners in lexicographic order);
       // closed directions: parent basis at the child's nodes; open direction (H(curl)): the same times the tangent's scale s
       PA_REQUIRE(mf.GetNumCorners() == 8 && mf.Dimension() == 3, "tensor blocks of hexahedra expected");
+      PA_REQUIRE(f.GetFEType() == PA_FE_HCURL || f.GetFEType() == PA_FE_H1,
+                 "refinement transfer of tensor spaces: H(curl) and H1 hexahedra only (a Raviart-Thomas space has no multigrid "
+                 "hierarchy here: its operators are assembled on one level)");
       const bool hcurl = f.GetFEType() == PA_FE_HCURL;
       const std::vector<double> cp = fem::GaussLobatto(p + 1);
       std::vector<double> op, ow;
@@ -566,6 +572,9 @@ const Operator &FiniteElementSpaceHierarchy::BuildProlongationAtLevel(std::size_
                                            mid.data()));
     return *P_[l];
   }
+  PA_REQUIRE(c.IsDense() || ((c.GetFEType() == PA_FE_HCURL || c.GetFEType() == PA_FE_H1) && c.GetFEType() == f.GetFEType()),
+             "p-prolongation of tensor spaces: two H(curl) or two H1 spaces (a Raviart-Thomas space has no multigrid hierarchy "
+             "here: its operators are assembled on one level)");
   std::vector<double> Ic, Io, tmp, xc, wc, xf, wf;
   fem::LagrangeEval(fem::GaussLobatto(c.GetMaxElementOrder() + 1), fem::GaussLobatto(f.GetMaxElementOrder() + 1), Ic, tmp);
   fem::GaussLegendre(c.GetMaxElementOrder(), xc, wc);

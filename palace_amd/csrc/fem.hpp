@@ -159,8 +159,10 @@ class FiniteElementSpace {
   mutable std::map<const FiniteElementSpace *, std::unique_ptr<Operator>> G_;
 
 public:
-  // fe_type PA_FE_HCURL | PA_FE_H1; offsets [ne][P] into the local (L-) vector, orients (HCURL) the sign flips,
-  // dof_map the tensor -> native local ordering (NULL: lexicographic).  n_true < 0: one rank, every dof is a true dof
+  // fe_type PA_FE_HCURL | PA_FE_H1 | PA_FE_HDIV (Raviart-Thomas hexahedra, P = 3 p^2 (p + 1): VectorFEMassIntegrator,
+  // DivDivIntegrator and DivDivMassIntegrator run sum-factorised on them); offsets [ne][P] into the local (L-) vector, orients
+  // (HCURL, HDIV) the sign flips, dof_map the tensor -> native local ordering (NULL: lexicographic).  n_true < 0: one rank,
+  // every dof is a true dof
   FiniteElementSpace(const Context &ctx, const Mesh &mesh, int fe_type, int order, int vsize, const int32_t *offsets,
                      const uint8_t *orients, const int32_t *dof_map, int n_true = -1, const Halo *halo = nullptr);
   // The same for a space given by dense tables on a dense Mesh (fem/libceed/basis.cpp:40-85, restriction.cpp:207-385):

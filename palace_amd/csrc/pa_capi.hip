@@ -72,6 +72,7 @@ CoeffDev CoeffHost::dev() const {
 }
 
 static int expected_P(int fe_type, int p) {
+  if (fe_type == PA_FE_HDIV) return 3 * p * p * (p + 1);
   return fe_type == PA_FE_HCURL ? 3 * p * (p + 1) * (p + 1) : (p + 1) * (p + 1) * (p + 1);
 }
 
@@ -117,6 +118,30 @@ static void check_dense_tables(const pa_basis_desc &b, int P, int Q) {
                 }
           }
     }
+  } else if (b.fe_type == PA_FE_HDIV) {  // interp [3 Q][P] values, deriv [Q][P] divergence (fem/rthex.py: rt_hex_tables)
+    for (int C = 0; C < 3; C++) {
+      const int ni = C == 0 ? nc : p, nj = C == 1 ? nc : p, nk = C == 2 ? nc : p;
+      const double *TX = C == 0 ? b.Bc : b.Bo, *TY = C == 1 ? b.Bc : b.Bo, *TZ = C == 2 ? b.Bc : b.Bo;
+      for (int k = 0; k < nk; k++)
+        for (int j = 0; j < nj; j++)
+          for (int i = 0; i < ni; i++) {
+            double sgn;
+            const int n = nat(C * p * p * nc + i + ni * (j + nj * k), sgn);
+            for (int qz = 0; qz < q1; qz++)
+              for (int qy = 0; qy < q1; qy++)
+                for (int qx = 0; qx < q1; qx++) {
+                  const int q = qx + q1 * (qy + q1 * qz);
+                  const double bx = TX[qx * ni + i], by = TY[qy * nj + j], bz = TZ[qz * nk + k];
+                  const double f = sgn * bx * by * bz;
+                  const double dv = sgn * (C == 0 ? b.Gc[qx * nc + i] * by * bz
+                                                  : C == 1 ? bx * b.Gc[qy * nc + j] * bz : bx * by * b.Gc[qz * nc + k]);
+                  if (b.interp)
+                    for (int d = 0; d < 3; d++)
+                      worst = std::fmax(worst, std::fabs(b.interp[((size_t)d * Q + q) * P + n] - (d == C ? f : 0.0)));
+                  if (b.deriv) worst = std::fmax(worst, std::fabs(b.deriv[(size_t)q * P + n] - dv));
+                }
+          }
+    }
   } else {
     for (int k = 0; k < nc; k++)
       for (int j = 0; j < nc; j++)
@@ -150,7 +175,7 @@ static SubOp *make_sub(pa_geom *geom, const pa_restriction_desc &r, const pa_bas
   PA_REQUIRE(geom && geom->d_geom, "geometry data missing");
   PA_REQUIRE(geom->eb == 0, "geometry data of a dense element block: use pa_op_add_sub_dense");
   PA_REQUIRE(!r.curl_orients, "the curl-oriented restriction needs the dense-table path (pa_op_add_sub_dense)");
-  PA_REQUIRE(b.fe_type == PA_FE_HCURL || b.fe_type == PA_FE_H1, "unknown finite element type");
+  PA_REQUIRE(b.fe_type == PA_FE_HCURL || b.fe_type == PA_FE_H1 || b.fe_type == PA_FE_HDIV, "unknown finite element type");
   PA_REQUIRE(b.order >= 1 && b.order + 1 <= kMaxP1 + 1, "unsupported element order");
   PA_REQUIRE(b.q1d == geom->q1d, "basis and geometry data use different quadrature rules");
   PA_REQUIRE(b.Bc && b.Gc && (b.fe_type == PA_FE_H1 || b.Bo), "1-D basis tables missing");
@@ -158,8 +183,22 @@ static SubOp *make_sub(pa_geom *geom, const pa_restriction_desc &r, const pa_bas
   const int P = expected_P(b.fe_type, b.order);
   PA_REQUIRE(r.elem_size == P, "restriction element size does not match the basis");
   PA_REQUIRE(r.offsets, "restriction offsets missing");
-  const bool cross = qf == PA_QF_HCURLHDIV_33 || qf == PA_QF_HDIVHCURL_33;
-  if (cross) {  // integ/mixedveccurl.cpp:21-120 on one H(curl) space
+  const bool cross = b.fe_type != PA_FE_HDIV && (qf == PA_QF_HCURLHDIV_33 || qf == PA_QF_HDIVHCURL_33);
+  const bool rt = b.fe_type == PA_FE_HDIV;
+  if (rt) {
+    // the three integrators make_dense_sub accepts for H(div) blocks in 3-D; the quadrature weight is no table of its own here
+    trial_ops &= ~(uint32_t)PA_EVAL_WEIGHT, test_ops &= ~(uint32_t)PA_EVAL_WEIGHT;
+    const uint32_t need = qf == PA_QF_HDIV_33 ? (uint32_t)PA_EVAL_INTERP
+                          : qf == PA_QF_L2_1  ? (uint32_t)PA_EVAL_DIV
+                          : qf == PA_QF_L2MASS_33 ? (uint32_t)(PA_EVAL_INTERP | PA_EVAL_DIV) : 0u;
+    PA_REQUIRE(need != 0 && trial_ops == need && test_ops == need,
+               "H(div) hexahedra: the mass operator (PA_QF_HDIV_33, Interp), div-div (PA_QF_L2_1, Div) and div-div + mass "
+               "(PA_QF_L2MASS_33, Interp | Div) are supported");
+    if (!rt_hex_supported(b.order, b.q1d))
+      throw Error("no H(div) hex kernel for order " + std::to_string(b.order) + " with " + std::to_string(b.q1d) +
+                  " points per direction");
+    PA_REQUIRE(!shared_qd, "H(div) blocks have no coarsened form");
+  } else if (cross) {  // integ/mixedveccurl.cpp:21-120 on one H(curl) space
     PA_REQUIRE(b.fe_type == PA_FE_HCURL, "the mixed curl QFunctions need an H(curl) space");
     const uint32_t ti = qf == PA_QF_HCURLHDIV_33 ? PA_EVAL_INTERP : PA_EVAL_CURL;
     const uint32_t te = qf == PA_QF_HCURLHDIV_33 ? PA_EVAL_CURL : PA_EVAL_INTERP;
@@ -168,7 +207,8 @@ static SubOp *make_sub(pa_geom *geom, const pa_restriction_desc &r, const pa_bas
     PA_REQUIRE(trial_ops == test_ops, "trial and test evaluation modes differ only for the mixed curl QFunctions");
   }
   uint32_t want = 0;
-  switch (qf) {
+  if (rt) want = trial_ops;
+  else switch (qf) {
     case PA_QF_HCURLHDIV_33:
     case PA_QF_HDIVHCURL_33: want = trial_ops; break;
     case PA_QF_HDIV_33: want = PA_EVAL_CURL; break;
@@ -181,7 +221,7 @@ static SubOp *make_sub(pa_geom *geom, const pa_restriction_desc &r, const pa_bas
   PA_REQUIRE(trial_ops == want, "evaluation modes do not match the QFunction's inputs");
   const bool nd_qf = qf == PA_QF_HDIV_33 || qf == PA_QF_HDIVMASS_33 || cross ||
                      (qf == PA_QF_HCURL_33 && b.fe_type == PA_FE_HCURL);
-  PA_REQUIRE(nd_qf == (b.fe_type == PA_FE_HCURL), "QFunction does not match the element type");
+  PA_REQUIRE(rt || nd_qf == (b.fe_type == PA_FE_HCURL), "QFunction does not match the element type");
 
   auto *so = new SubOp;
   so->geom = geom;
@@ -270,7 +310,7 @@ static SubOp *make_sub(pa_geom *geom, const pa_restriction_desc &r, const pa_bas
   // transpose map for the gather form of E^T (counting sort by dof; element order preserved, so the
   // summation order of every dof is fixed) unless PALACE_AMD_SCATTER=atomic asks for the atomic form
   const char *mode = getenv("PALACE_AMD_SCATTER");
-  if (!(mode && std::string(mode) == "atomic") || b.fe_type == PA_FE_H1) {
+  if (!(mode && std::string(mode) == "atomic") || b.fe_type != PA_FE_HCURL) {
     std::vector<int32_t> tptr((size_t)r.lsize + 1, 0), tent(nnz);
     for (size_t k = 0; k < nnz; k++) {
       const int32_t s = sidx[k];
@@ -297,6 +337,13 @@ static SubOp *make_sub(pa_geom *geom, const pa_restriction_desc &r, const pa_bas
     case PA_QF_HCURLHDIV_33:
     case PA_QF_HDIVHCURL_33:
       parse_coeff(ctx, ctx_size, 3, so->c0, 0);
+      break;
+    case PA_QF_L2_1:  // (H(div) blocks) scalar
+      parse_coeff(ctx, ctx_size, 1, so->c0, 0);
+      break;
+    case PA_QF_L2MASS_33:  // pair: 3 x 3 mass first, then the scalar of the divergence term
+      parse_coeff(ctx, ctx_size, 3, so->c0, 0);
+      parse_coeff(ctx, ctx_size, 1, so->c1, so->c0.slots);
       break;
     case PA_QF_HDIVMASS_33:
       parse_coeff(ctx, ctx_size, 3, so->c0, 0);
@@ -352,6 +399,8 @@ static SubOp *make_sub(pa_geom *geom, const pa_restriction_desc &r, const pa_bas
   } else if (want_qd) {
     if (b.fe_type == PA_FE_HCURL)
       launch_nd_hex_qdata(*so, nullptr);
+    else if (b.fe_type == PA_FE_HDIV)
+      launch_rt_hex_qdata(*so, nullptr);
     else
       launch_h1_hex_qdata(*so, nullptr);
     PA_HIP(hipStreamSynchronize(nullptr));
@@ -407,6 +456,12 @@ static void apply(pa_op *op, const double *x, double *y, bool overwrite, hipStre
         if (overwrite && first) PA_HIP(hipMemsetAsync(y, 0, sizeof(double) * (size_t)op->height, s));
         launch_nd_hex_apply(*so, x, y, nullptr, masked, s);
       }
+    } else if (so->fe_type == PA_FE_HDIV) {  // masked: essential entries read as zero (d_sidx_bc), the rows fixed by the gather
+      launch_rt_hex_apply(*so, x, masked, s);
+      if (masked && ess_policy >= 0 && so->d_shared_bc)
+        launch_et_gather_raw(so->lsize, so->d_tptr, so->d_tent, so->d_ye, y, !(overwrite && first), s, so->d_shared_bc, x, ess_policy);
+      else
+        launch_et_gather(*so, y, !(overwrite && first), s);
     } else if (so->d_idxc && so->stream_default && overwrite && first && (!masked || so->d_perm_s_bc)) {  // streaming form, see above
       launch_h1_hex_stream(*so, x, y, masked, s);
       launch_et_run_gather(*so, y, false, s, x, masked, ess_policy);
@@ -856,7 +911,7 @@ int pa_op_add_sub_sum(pa_op *op, pa_geom *geom, const pa_restriction_desc *restr
                       const double *coeffs) {
   int rc = guarded([&] {
     PA_REQUIRE(op && geom && restr && basis, "null argument");
-    PA_REQUIRE(basis->fe_type == PA_FE_HCURL, "fused sums are built for H(curl) spaces");
+    PA_REQUIRE(basis->fe_type == PA_FE_HCURL, "fused sums are built for H(curl) spaces (H1 and H(div) blocks: one pa_op_add_sub per integrator)");
   });
   if (rc) return rc;
   int qf = 0;
@@ -903,6 +958,8 @@ int pa_op_coarsen(const pa_op *fine, const pa_restriction_desc *restr, const pa_
     o->height = o->width = restr->lsize;
     try {
       for (const SubOp *fs : fine->subs) {
+        PA_REQUIRE(fs->fe_type != PA_FE_HDIV && basis->fe_type != PA_FE_HDIV,
+                   "p-coarsening is built for H(curl) and H1 hexahedra: an H(div) operator is assembled at its own order");
         PA_REQUIRE(fs->ne == restr->num_elem, "coarsening needs one element block (same elements)");
         o->subs.push_back(make_sub(static_cast<pa_geom *>(fs->geom), *restr, *basis, fs->qf,
                                    fs->ctx_blob.data(), fs->ctx_blob.size(), fs->trial_ops,
@@ -977,6 +1034,7 @@ int pa_op_complex_fused(const pa_op *op_r, const pa_op *op_i) {
   if (!op_r || !op_i || !op_r->msubs.empty() || !op_i->msubs.empty() || op_r->height != op_i->height || op_r->width != op_i->width)
     return 0;
   const bool hex = op_r->subs.size() == 1 && op_i->subs.size() == 1;
+  if (hex && (op_r->subs[0]->fe_type == PA_FE_HDIV || op_i->subs[0]->fe_type == PA_FE_HDIV)) return 0;  // no complex form
   const bool dense = op_r->dsubs.size() >= 1 && op_i->dsubs.size() >= 1 && op_r->subs.empty() && op_i->subs.empty();
   if (!hex && !dense) return 0;
   // (the check compares the two restrictions on the host: once per pair)
@@ -1089,6 +1147,12 @@ int pa_op_set_essential(pa_op *op, const int32_t *ess, int32_t n) {
         so->d_shared_bc = dev_upload(lb.data(), lb.size());
       }
       if (so->d_idxc) stream_set_essential(*so, flag);
+      if (so->fe_type == PA_FE_HDIV) {  // every dof goes through the gather: its list with the essential rows flagged
+        std::vector<int32_t> lb((size_t)so->lsize);
+        for (int d = 0; d < so->lsize; d++) lb[d] = flag[d] ? (d | kEssBit) : d;
+        hipFree(so->d_shared_bc);
+        so->d_shared_bc = dev_upload(lb.data(), lb.size());
+      }
     }
     op->has_essential = true;
   });
@@ -1113,9 +1177,11 @@ int pa_op_mult_essential_diag(pa_op *op, const double *x, double *y, int diag_po
       *handled = 1;
       return;
     }
-    const bool fuse = op->subs.size() == 1 && op->dsubs.empty() &&
-                      (op->subs[0]->fe_type == PA_FE_HCURL ? nd_hex_fuses_essential(*op->subs[0])
-                                                           : (op->subs[0]->d_idxc && op->subs[0]->stream_default && op->subs[0]->d_perm_s_bc));
+    const SubOp *s0 = op->subs.size() == 1 ? op->subs[0] : nullptr;
+    const bool fuse = s0 && op->dsubs.empty() && op->msubs.empty() &&
+                      (s0->fe_type == PA_FE_HCURL  ? nd_hex_fuses_essential(*s0)
+                       : s0->fe_type == PA_FE_HDIV ? s0->d_shared_bc != nullptr  // (the plain gather over the flagged dof list)
+                                                   : (s0->d_idxc && s0->stream_default && s0->d_perm_s_bc));
     apply(op, x, y, true, (hipStream_t)stream, true, fuse ? (diag_policy ? 1 : 0) : -1);
     *handled = fuse ? 1 : 0;
   });
@@ -1337,6 +1403,8 @@ int pa_op_assemble_diagonal(pa_op *op, double *diag, void *stream) {
     for (const SubOp *so : op->subs) {
       if (so->fe_type == PA_FE_HCURL)
         launch_nd_hex_diag(*so, diag, (hipStream_t)stream);
+      else if (so->fe_type == PA_FE_HDIV)
+        launch_rt_hex_diag(*so, diag, (hipStream_t)stream);
       else
         launch_h1_hex_diag(*so, diag, (hipStream_t)stream);
     }
@@ -1373,7 +1441,17 @@ double pa_op_algorithmic_bytes(const pa_op *op) {
   if (!op) return 0.0;
   double bytes = 0.0;
   // (o = 1 orientation byte per entry for the oriented restriction of H(curl) blocks, none for H1: SURVEY.md 8d)
-  for (const SubOp *so : op->subs) bytes += (double)so->ne * ((double)so->Q * 11 * 8 + (double)so->P * (so->fe_type == PA_FE_H1 ? 4 : 5));
+  for (const SubOp *so : op->subs) {
+    if (so->fe_type == PA_FE_HDIV) {
+      // what pa_rt_hex.hip streams per element: the packed D rows (6 mass + 1 divergence), or of the geometry rows {attr, w detJ}
+      // and, with a mass term, the nine of adj(J)^T / detJ; per entry the sorted index (4 B) and its tensor-order slot (2 B)
+      const bool use_v = so->qf != PA_QF_L2_1;
+      const int rows = so->qd ? so->qd->ncomp : (use_v ? 11 : 2);
+      bytes += (double)so->ne * ((double)so->Q * rows * 8 + (double)so->P * 6);
+      continue;
+    }
+    bytes += (double)so->ne * ((double)so->Q * 11 * 8 + (double)so->P * (so->fe_type == PA_FE_H1 ? 4 : 5));
+  }
   for (const DenseSub *ds : op->dsubs)  // o = 3 for the curl-oriented restriction; G = 11 (3-D) or 6 (2-D)
     bytes += (double)ds->ne * ((double)ds->Q * ds->geom->nrows * 8 + (double)ds->P * (ds->d_co ? 7 : 5));
   return bytes + 16.0 * op->height;

@@ -372,6 +372,11 @@ void launch_nd_hex_stream_complex(const SubOp &sr, const SubOp &si, const double
 void launch_h1_hex_apply(const SubOp &so, const double *x, bool masked, hipStream_t s);
 void launch_h1_hex_qdata(SubOp &so, hipStream_t s);
 void launch_h1_hex_diag(const SubOp &so, double *diag, hipStream_t s);
+// pa_rt_hex.hip: Raviart-Thomas hexahedra (mass, div-div, div-div + mass); the E-vector + gather form of E^T only
+bool rt_hex_supported(int p, int q1d);
+void launch_rt_hex_apply(const SubOp &so, const double *x, bool masked, hipStream_t s);
+void launch_rt_hex_qdata(SubOp &so, hipStream_t s);
+void launch_rt_hex_diag(const SubOp &so, double *diag, hipStream_t s);
 
 // pa_dense.hip
 void launch_geom_dense(const pa_mesh_dense_desc &mesh, Geom &g, hipStream_t s);
