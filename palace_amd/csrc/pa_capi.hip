@@ -6,7 +6,7 @@
 #include <cstdlib>
 #include <cstring>
 
-#include "pa_internal.hpp"
+#include "pa_hex_core.hpp"
 
 namespace pa {
 
@@ -194,9 +194,7 @@ static SubOp *make_sub(pa_geom *geom, const pa_restriction_desc &r, const pa_bas
     PA_REQUIRE(need != 0 && trial_ops == need && test_ops == need,
                "H(div) hexahedra: the mass operator (PA_QF_HDIV_33, Interp), div-div (PA_QF_L2_1, Div) and div-div + mass "
                "(PA_QF_L2MASS_33, Interp | Div) are supported");
-    if (!rt_hex_supported(b.order, b.q1d))
-      throw Error("no H(div) hex kernel for order " + std::to_string(b.order) + " with " + std::to_string(b.q1d) +
-                  " points per direction");
+    if (!hex_pq_supported(b.order, b.q1d)) throw hex_pq_error("H(div)", b.order, b.q1d);
     PA_REQUIRE(!shared_qd, "H(div) blocks have no coarsened form");
   } else if (cross) {  // integ/mixedveccurl.cpp:21-120 on one H(curl) space
     PA_REQUIRE(b.fe_type == PA_FE_HCURL, "the mixed curl QFunctions need an H(curl) space");

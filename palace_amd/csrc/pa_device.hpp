@@ -64,15 +64,29 @@ __device__ __forceinline__ void sym_mv(const double m[6], const double x0, const
   y2 = m[2] * x0 + m[4] * x1 + m[5] * x2;
 }
 
+// The six stored entries {00, 01, 02, 11, 12, 22} of a column-major 3x3 that is symmetric by construction when the
+// coefficient is: the off-diagonal pairs are averaged against rounding drift.  store(i, value) puts entry i where the
+// caller's q-data layout has it.
+template <class Store>
+__device__ __forceinline__ void sym_pack(const double M[9], Store &&store) {
+  store(0, M[0]);
+  store(1, 0.5 * (M[3] + M[1]));
+  store(2, 0.5 * (M[6] + M[2]));
+  store(3, M[4]);
+  store(4, 0.5 * (M[7] + M[5]));
+  store(5, M[8]);
+}
+
 // coeff_3_qf.h:9-24
-__device__ __forceinline__ int coeff_index(const CoeffDev &c, int attr) {
+__device__ __forceinline__ int coeff_index(const CoeffDev c, int attr) {
   return (c.nattr > 0) ? c.attr_mat[attr - 1] : 0;
 }
-__device__ __forceinline__ void coeff_unpack3(const CoeffDev &c, int attr, double C[9]) {
+__device__ __forceinline__ void coeff_unpack3(const CoeffDev c, int attr, double C[9]) {
   const int k = coeff_index(c, attr);
 #pragma unroll
   for (int i = 0; i < 9; i++) C[i] = c.mat[9 * k + i];
 }
-
+// coeff_1_qf.h
+__device__ __forceinline__ double coeff_unpack1(const CoeffDev c, int attr) { return c.mat[coeff_index(c, attr)]; }
 
 }  // namespace pa

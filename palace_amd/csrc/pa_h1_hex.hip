@@ -6,25 +6,16 @@
 //
 // Same mapping as pa_nd_hex.hip: Q1^2 lanes per element, passes X -> Y -> Z through LDS inside the
 // wave, lane (qx,qy) ends with its qz column of u and grad u; E^T is the E-vector + gather form.
-#include "pa_internal.hpp"
+#include "pa_hex_core.hpp"
 
 namespace pa {
 
 template <int P1, int Q1>
 struct H1Tab {
-  static constexpr int QH = (Q1 + 1) / 2;  // mirror symmetry, see pa_nd_hex.hip
+  static constexpr int QH = (Q1 + 1) / 2;  // mirror symmetry: whole half rows, pa_hex_core.hpp
   double Bc[QH * (P1 + 1)];
   double Gc[QH * (P1 + 1)];
 };
-
-template <int N, int Q1>
-__device__ __forceinline__ double h1_even(const double *H, const int q, const int i) {
-  return (q < (Q1 + 1) / 2) ? H[q * N + i] : H[(Q1 - 1 - q) * N + (N - 1 - i)];
-}
-template <int N, int Q1>
-__device__ __forceinline__ double h1_odd(const double *H, const int q, const int i) {
-  return (q < (Q1 + 1) / 2) ? H[q * N + i] : -H[(Q1 - 1 - q) * N + (N - 1 - i)];
-}
 
 template <int P1, int Q1>
 struct H1Args {
@@ -37,42 +28,6 @@ struct H1Args {
   double *ye;
   CoeffDev c_mass, c_diff;
   H1Tab<P1, Q1> tab;
-};
-
-__device__ __forceinline__ void h1_wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// utils_33_qf.h:64-84: y = s A^T B C x
-__device__ __forceinline__ void h1_AtBCx33(const double A[9], const double B[9], const double C[9], const double x0,
-                                           const double x1, const double x2, const double s, double &y0, double &y1,
-                                           double &y2) {
-  const double t0 = C[0] * x0 + C[3] * x1 + C[6] * x2;
-  const double t1 = C[1] * x0 + C[4] * x1 + C[7] * x2;
-  const double t2 = C[2] * x0 + C[5] * x1 + C[8] * x2;
-  const double z0 = B[0] * t0 + B[3] * t1 + B[6] * t2;
-  const double z1 = B[1] * t0 + B[4] * t1 + B[7] * t2;
-  const double z2 = B[2] * t0 + B[5] * t1 + B[8] * t2;
-  y0 = s * (A[0] * z0 + A[1] * z1 + A[2] * z2);
-  y1 = s * (A[3] * z0 + A[4] * z1 + A[5] * z2);
-  y2 = s * (A[6] * z0 + A[7] * z1 + A[8] * z2);
-}
-
-template <int P1, int Q1>
-struct H1Layout {
-  static constexpr int NC = P1 + 1;
-  static constexpr int T = Q1 * Q1;
-  static constexpr int EPW = 64 / T;
-  static constexpr int A_FIELD = Q1 * NC * NC;
-  static constexpr int B_FIELD = Q1 * Q1 * NC;
-  static constexpr int ELEM = 2 * A_FIELD + 3 * B_FIELD;
-  static constexpr int ELEM_PAD = ((ELEM + 15) / 16 * 16) | 16;
-  __device__ static __forceinline__ int ia(int f, int qx, int j, int k) { return f * A_FIELD + (qx * NC + j) * NC + k; }
-  __device__ static __forceinline__ int ib(int f, int qx, int qy, int k) {
-    return 2 * A_FIELD + f * B_FIELD + (qx * Q1 + qy) * NC + k;
-  }
 };
 
 constexpr int kH1Waves = 4;
@@ -128,14 +83,14 @@ __global__ __launch_bounds__(64 * kH1Waves, 2) void h1_hex_apply_kernel(const H1
       sm[lp[r]] = (s & kEssBit) ? 0.0 : a.x[s & ~kEssBit];
     }
   }
-  h1_wave_sync();
+  wave_sync();
   double u[NC];
   {
     const bool act = ta < NC && tb < NC;
 #pragma unroll
     for (int i = 0; i < NC; i++) u[i] = act ? sm[i + NC * (ta + NC * tb)] : 0.0;
   }
-  h1_wave_sync();
+  wave_sync();
 
   double V[Q1], GV[3][Q1];
   // ---- forward: pass X, lane (j, k)
@@ -146,8 +101,8 @@ __global__ __launch_bounds__(64 * kH1Waves, 2) void h1_hex_apply_kernel(const H1
       double v = 0.0, d = 0.0;
 #pragma unroll
       for (int i = 0; i < NC; i++) {
-        v += h1_even<NC, Q1>(Bc, qx, i) * u[i];
-        if (USE_G) d += h1_odd<NC, Q1>(Gc, qx, i) * u[i];
+        v += half_even<NC, Q1>(Bc, qx, i) * u[i];
+        if (USE_G) d += half_odd<NC, Q1>(Gc, qx, i) * u[i];
       }
       if (lane_ok && act) {
         sm[L::ia(0, qx, ta, tb)] = v;
@@ -155,7 +110,7 @@ __global__ __launch_bounds__(64 * kH1Waves, 2) void h1_hex_apply_kernel(const H1
       }
     }
   }
-  h1_wave_sync();
+  wave_sync();
   // pass Y, lane (qx, k)
   {
     const bool act = tb < NC;
@@ -170,9 +125,9 @@ __global__ __launch_bounds__(64 * kH1Waves, 2) void h1_hex_apply_kernel(const H1
       double vv = 0.0, vd = 0.0, dv = 0.0;
 #pragma unroll
       for (int j = 0; j < NC; j++) {
-        vv += h1_even<NC, Q1>(Bc, qy, j) * v[j];
-        if (USE_G) vd += h1_odd<NC, Q1>(Gc, qy, j) * v[j];
-        if (USE_G) dv += h1_even<NC, Q1>(Bc, qy, j) * d[j];
+        vv += half_even<NC, Q1>(Bc, qy, j) * v[j];
+        if (USE_G) vd += half_odd<NC, Q1>(Gc, qy, j) * v[j];
+        if (USE_G) dv += half_even<NC, Q1>(Bc, qy, j) * d[j];
       }
       if (lane_ok && act) {
         sm[L::ib(0, ta, qy, tb)] = vv;
@@ -180,7 +135,7 @@ __global__ __launch_bounds__(64 * kH1Waves, 2) void h1_hex_apply_kernel(const H1
       }
     }
   }
-  h1_wave_sync();
+  wave_sync();
   // pass Z, lane (qx, qy)
   {
     double vv[NC], vd[NC], dv[NC];
@@ -194,17 +149,17 @@ __global__ __launch_bounds__(64 * kH1Waves, 2) void h1_hex_apply_kernel(const H1
       double val = 0.0, dz = 0.0, dy = 0.0, dx = 0.0;
 #pragma unroll
       for (int k = 0; k < NC; k++) {
-        if (USE_V) val += h1_even<NC, Q1>(Bc, qz, k) * vv[k];
+        if (USE_V) val += half_even<NC, Q1>(Bc, qz, k) * vv[k];
         if (USE_G) {
-          dz += h1_odd<NC, Q1>(Gc, qz, k) * vv[k];
-          dy += h1_even<NC, Q1>(Bc, qz, k) * vd[k];
-          dx += h1_even<NC, Q1>(Bc, qz, k) * dv[k];
+          dz += half_odd<NC, Q1>(Gc, qz, k) * vv[k];
+          dy += half_even<NC, Q1>(Bc, qz, k) * vd[k];
+          dx += half_even<NC, Q1>(Bc, qz, k) * dv[k];
         }
       }
       V[qz] = val, GV[0][qz] = dx, GV[1][qz] = dy, GV[2][qz] = dz;
     }
   }
-  h1_wave_sync();
+  wave_sync();
 
   // ---- D (h1_1 / hcurl_33 on grad u / hcurlmass_33)
 #pragma unroll
@@ -212,25 +167,22 @@ __global__ __launch_bounds__(64 * kH1Waves, 2) void h1_hex_apply_kernel(const H1
     if (QD) {
       if (USE_V) V[qz] *= gd[qz][0];
       if (USE_G) {
-        const double *m = &gd[qz][USE_V ? 1 : 0];
-        const double x0 = GV[0][qz], x1 = GV[1][qz], x2 = GV[2][qz];
-        GV[0][qz] = m[0] * x0 + m[1] * x1 + m[2] * x2;
-        GV[1][qz] = m[1] * x0 + m[3] * x1 + m[4] * x2;
-        GV[2][qz] = m[2] * x0 + m[4] * x1 + m[5] * x2;
+        sym_mv(&gd[qz][USE_V ? 1 : 0], GV[0][qz], GV[1][qz], GV[2][qz], GV[0][qz], GV[1][qz], GV[2][qz]);
       }
     } else {
       const double wdetJ = gd[qz][0];
       const double *adj = &gd[qz][1];
       if (USE_V) {
+        // coeff_unpack1 spelled out: through the helper the <4, 5> mass-only instantiation is scheduled differently
         const int k = (a.c_mass.nattr > 0) ? a.c_mass.attr_mat[attr[qz] - 1] : 0;
-        V[qz] *= a.c_mass.mat[k] * wdetJ;  // CoeffUnpack1, coeff_1_qf.h
+        V[qz] *= a.c_mass.mat[k] * wdetJ;
       }
       if (USE_G) {
         double Cm[9];
-        const int k = (a.c_diff.nattr > 0) ? a.c_diff.attr_mat[attr[qz] - 1] : 0;
+        const int k = coeff_index(a.c_diff, attr[qz]);  // (coeff_unpack3 written out, for the same reason; so below)
 #pragma unroll
         for (int i = 0; i < 9; i++) Cm[i] = a.c_diff.mat[9 * k + i];
-        h1_AtBCx33(adj, Cm, adj, GV[0][qz], GV[1][qz], GV[2][qz], wdetJ, GV[0][qz], GV[1][qz], GV[2][qz]);
+        mult_AtBCx33(adj, Cm, adj, GV[0][qz], GV[1][qz], GV[2][qz], wdetJ, GV[0][qz], GV[1][qz], GV[2][qz]);
       }
     }
   }
@@ -242,11 +194,11 @@ __global__ __launch_bounds__(64 * kH1Waves, 2) void h1_hex_apply_kernel(const H1
       double vv = 0.0, vd = 0.0, dv = 0.0;
 #pragma unroll
       for (int qz = 0; qz < Q1; qz++) {
-        if (USE_V) vv += h1_even<NC, Q1>(Bc, qz, k) * V[qz];
+        if (USE_V) vv += half_even<NC, Q1>(Bc, qz, k) * V[qz];
         if (USE_G) {
-          vv += h1_odd<NC, Q1>(Gc, qz, k) * GV[2][qz];
-          vd += h1_even<NC, Q1>(Bc, qz, k) * GV[1][qz];
-          dv += h1_even<NC, Q1>(Bc, qz, k) * GV[0][qz];
+          vv += half_odd<NC, Q1>(Gc, qz, k) * GV[2][qz];
+          vd += half_even<NC, Q1>(Bc, qz, k) * GV[1][qz];
+          dv += half_even<NC, Q1>(Bc, qz, k) * GV[0][qz];
         }
       }
       if (lane_ok) {
@@ -255,7 +207,7 @@ __global__ __launch_bounds__(64 * kH1Waves, 2) void h1_hex_apply_kernel(const H1
       }
     }
   }
-  h1_wave_sync();
+  wave_sync();
   // Y^T lane (qx, k)
   {
     const bool act = tb < NC;
@@ -270,9 +222,9 @@ __global__ __launch_bounds__(64 * kH1Waves, 2) void h1_hex_apply_kernel(const H1
       double v = 0.0, d = 0.0;
 #pragma unroll
       for (int qy = 0; qy < Q1; qy++) {
-        v += h1_even<NC, Q1>(Bc, qy, j) * vv[qy];
-        if (USE_G) v += h1_odd<NC, Q1>(Gc, qy, j) * vd[qy];
-        if (USE_G) d += h1_even<NC, Q1>(Bc, qy, j) * dv[qy];
+        v += half_even<NC, Q1>(Bc, qy, j) * vv[qy];
+        if (USE_G) v += half_odd<NC, Q1>(Gc, qy, j) * vd[qy];
+        if (USE_G) d += half_even<NC, Q1>(Bc, qy, j) * dv[qy];
       }
       if (lane_ok && act) {
         sm[L::ia(0, ta, j, tb)] = v;
@@ -280,7 +232,7 @@ __global__ __launch_bounds__(64 * kH1Waves, 2) void h1_hex_apply_kernel(const H1
       }
     }
   }
-  h1_wave_sync();
+  wave_sync();
   // X^T lane (j, k) -> E-vector [i][j + NC k]
   {
     const bool act = ta < NC && tb < NC;
@@ -295,13 +247,13 @@ __global__ __launch_bounds__(64 * kH1Waves, 2) void h1_hex_apply_kernel(const H1
       double r = 0.0;
 #pragma unroll
       for (int qx = 0; qx < Q1; qx++) {
-        r += h1_even<NC, Q1>(Bc, qx, i) * v[qx];
-        if (USE_G) r += h1_odd<NC, Q1>(Gc, qx, i) * d[qx];
+        r += half_even<NC, Q1>(Bc, qx, i) * v[qx];
+        if (USE_G) r += half_odd<NC, Q1>(Gc, qx, i) * d[qx];
       }
       u[i] = r;
     }
   }
-  h1_wave_sync();
+  wave_sync();
   // E^T, first half: results into tensor order in LDS, then out in sorted order (coalesced)
   {
     const bool act = lane_ok && ta < NC && tb < NC;
@@ -309,12 +261,21 @@ __global__ __launch_bounds__(64 * kH1Waves, 2) void h1_hex_apply_kernel(const H1
     for (int i = 0; i < NC; i++)
       if (act) sm[i + NC * (ta + NC * tb)] = u[i];
   }
-  h1_wave_sync();
+  wave_sync();
 #pragma unroll
   for (int r = 0; r < NPL; r++) {
     const int m = t + L::T * r;
     if (active && m < P) a.ye[(size_t)e * P + m] = sm[lp[r]];
   }
+}
+
+// QFunction id -> the terms (mass: values, diffusion: gradient) and their coefficients
+static void h1_terms(const SubOp &so, bool &use_v, bool &use_g, CoeffDev &cm, CoeffDev &cd) {
+  use_v = so.qf == PA_QF_H1_1 || so.qf == PA_QF_HCURLMASS_33;
+  use_g = so.qf == PA_QF_HCURL_33 || so.qf == PA_QF_HCURLMASS_33;
+  if (!use_v && !use_g) throw Error("QFunction not available for H1 hexahedra");
+  cm = use_v ? so.c0.dev() : CoeffDev{};
+  cd = use_g ? (use_v ? so.c1 : so.c0).dev() : CoeffDev{};
 }
 
 template <int P1, int Q1>
@@ -339,48 +300,23 @@ static void h1_launch_pq(const SubOp &so, const double *x, bool masked, hipStrea
     hipLaunchKernelGGL((h1_hex_apply_kernel<P1, Q1, V, G, true>), grid, block, lds, s, a);    \
   else                                                                                        \
     hipLaunchKernelGGL((h1_hex_apply_kernel<P1, Q1, V, G, false>), grid, block, lds, s, a);
-  switch (so.qf) {
-    case PA_QF_HCURL_33:
-      a.c_diff = so.c0.dev();
-      PA_H1_LAUNCH(false, true)
-      break;
-    case PA_QF_H1_1:
-      a.c_mass = so.c0.dev();
-      PA_H1_LAUNCH(true, false)
-      break;
-    case PA_QF_HCURLMASS_33:
-      a.c_mass = so.c0.dev();
-      a.c_diff = so.c1.dev();
-      PA_H1_LAUNCH(true, true)
-      break;
-    default:
-      throw Error("QFunction not available for H1 hexahedra");
+  bool use_v, use_g;
+  h1_terms(so, use_v, use_g, a.c_mass, a.c_diff);
+  if (!use_v) {
+    PA_H1_LAUNCH(false, true)
+  } else if (!use_g) {
+    PA_H1_LAUNCH(true, false)
+  } else {
+    PA_H1_LAUNCH(true, true)
   }
 #undef PA_H1_LAUNCH
   PA_HIP(hipGetLastError());
 }
 
-#define PA_H1_DISPATCH(FN, ...)                                                           \
-  switch (so.p * 16 + so.q1d) {                                                            \
-    case 1 * 16 + 2: FN<1, 2>(__VA_ARGS__); break;                                         \
-    case 1 * 16 + 3: FN<1, 3>(__VA_ARGS__); break;                                         \
-    case 2 * 16 + 3: FN<2, 3>(__VA_ARGS__); break;                                         \
-    case 1 * 16 + 4: FN<1, 4>(__VA_ARGS__); break;                                         \
-    case 2 * 16 + 4: FN<2, 4>(__VA_ARGS__); break;                                         \
-    case 3 * 16 + 4: FN<3, 4>(__VA_ARGS__); break;                                         \
-    case 1 * 16 + 5: FN<1, 5>(__VA_ARGS__); break;                                         \
-    case 2 * 16 + 5: FN<2, 5>(__VA_ARGS__); break;                                         \
-    case 3 * 16 + 5: FN<3, 5>(__VA_ARGS__); break;                                         \
-    case 4 * 16 + 5: FN<4, 5>(__VA_ARGS__); break;                                         \
-    default:                                                                               \
-      throw Error("no H1 hex kernel for order " + std::to_string(so.p) + " with " +        \
-                  std::to_string(so.q1d) + " points per direction");                       \
-  }
-
 // writes the E-vector so.d_ye; the caller follows with launch_et_gather
 void launch_h1_hex_apply(const SubOp &so, const double *x, bool masked, hipStream_t s) {
   PA_REQUIRE(so.d_ye, "H1 blocks use the gather form of E^T");
-  PA_H1_DISPATCH(h1_launch_pq, so, x, masked, s)
+  PA_HEX_DISPATCH(h1_launch_pq, "H1", so, x, masked, s)
 }
 
 // ---- packed q-data and diagonal (set-up) ----------------------------------------------------------
@@ -397,29 +333,24 @@ __global__ void h1_hex_qdata_kernel(const int ne, const int Q, const double *__r
   const double w = g[Q + q];
   int o = 0;
   if (use_v) {
-    const int k = (c_mass.nattr > 0) ? c_mass.attr_mat[attr - 1] : 0;
-    out[0] = c_mass.mat[k] * w;
+    out[0] = coeff_unpack1(c_mass, attr) * w;
     o = 1;
   }
   if (use_g) {
     double adj[9], Cm[9], M[9];
     for (int c = 0; c < 9; c++) adj[c] = g[(2 + c) * Q + q];
-    const int k = (c_diff.nattr > 0) ? c_diff.attr_mat[attr - 1] : 0;
+    const int k = coeff_index(c_diff, attr);
     for (int i = 0; i < 9; i++) Cm[i] = c_diff.mat[9 * k + i];
     for (int col = 0; col < 3; col++)
-      h1_AtBCx33(adj, Cm, adj, col == 0, col == 1, col == 2, w, M[0 + 3 * col], M[1 + 3 * col], M[2 + 3 * col]);
-    out[(o + 0) * Q] = M[0];
-    out[(o + 1) * Q] = 0.5 * (M[3] + M[1]);
-    out[(o + 2) * Q] = 0.5 * (M[6] + M[2]);
-    out[(o + 3) * Q] = M[4];
-    out[(o + 4) * Q] = 0.5 * (M[7] + M[5]);
-    out[(o + 5) * Q] = M[8];
+      mult_AtBCx33(adj, Cm, adj, col == 0, col == 1, col == 2, w, M[0 + 3 * col], M[1 + 3 * col], M[2 + 3 * col]);
+    sym_pack(M, [&](const int i, const double v) { out[(o + i) * Q] = v; });
   }
 }
 
 void launch_h1_hex_qdata(SubOp &so, hipStream_t s) {
-  const bool use_v = so.qf == PA_QF_H1_1 || so.qf == PA_QF_HCURLMASS_33;
-  const bool use_g = so.qf == PA_QF_HCURL_33 || so.qf == PA_QF_HCURLMASS_33;
+  bool use_v, use_g;
+  CoeffDev cm, cd;
+  h1_terms(so, use_v, use_g, cm, cd);
   auto *qd = new QData;
   qd->ncomp = (int)use_v + 6 * (int)use_g;
   {  // padded to whole batches of four elements (the streaming kernel reads them), pad = 0
@@ -427,10 +358,6 @@ void launch_h1_hex_qdata(SubOp &so, hipStream_t s) {
     qd->d = dev_alloc<double>(nq);
     PA_HIP(hipMemsetAsync(qd->d, 0, nq * sizeof(double), s));
   }
-  CoeffDev cm{}, cd{};
-  if (so.qf == PA_QF_H1_1) cm = so.c0.dev();
-  if (so.qf == PA_QF_HCURL_33) cd = so.c0.dev();
-  if (so.qf == PA_QF_HCURLMASS_33) cm = so.c0.dev(), cd = so.c1.dev();
   const long long n = (long long)so.ne * so.Q;
   hipLaunchKernelGGL(h1_hex_qdata_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, so.ne, so.Q,
                      so.geom->d_geom, cm, cd, (int)use_v, (int)use_g, qd->d);
@@ -462,17 +389,14 @@ __global__ void h1_hex_diag_kernel(const H1DiagArgs a) {
     const double w = g[Q + q];
     for (int c = 0; c < 9; c++) adj[c] = g[(2 + c) * Q + q];
     double mv = 0.0;
-    if (a.use_v) {
-      const int k = (a.c_mass.nattr > 0) ? a.c_mass.attr_mat[attr - 1] : 0;
-      mv = a.c_mass.mat[k] * w;
-    }
+    if (a.use_v) mv = coeff_unpack1(a.c_mass, attr) * w;
     Mv[q] = mv;
     for (int col = 0; col < 3; col++) {
       double y0 = 0, y1 = 0, y2 = 0;
       if (a.use_g) {
-        const int k = (a.c_diff.nattr > 0) ? a.c_diff.attr_mat[attr - 1] : 0;
+        const int k = coeff_index(a.c_diff, attr);
         for (int i = 0; i < 9; i++) Cm[i] = a.c_diff.mat[9 * k + i];
-        h1_AtBCx33(adj, Cm, adj, col == 0, col == 1, col == 2, w, y0, y1, y2);
+        mult_AtBCx33(adj, Cm, adj, col == 0, col == 1, col == 2, w, y0, y1, y2);
       }
       Mg[9 * q + 0 + 3 * col] = y0, Mg[9 * q + 1 + 3 * col] = y1, Mg[9 * q + 2 + 3 * col] = y2;
     }
@@ -509,13 +433,7 @@ void launch_h1_hex_diag(const SubOp &so, double *diag, hipStream_t s) {
   a.y = diag;
   const int nc = so.p + 1;
   a.Bc = so.d_tab + so.q1d * so.p, a.Gc = a.Bc + so.q1d * nc;
-  a.use_v = a.use_g = false;
-  switch (so.qf) {
-    case PA_QF_HCURL_33: a.c_diff = so.c0.dev(), a.use_g = true; break;
-    case PA_QF_H1_1: a.c_mass = so.c0.dev(), a.use_v = true; break;
-    case PA_QF_HCURLMASS_33: a.c_mass = so.c0.dev(), a.c_diff = so.c1.dev(), a.use_v = a.use_g = true; break;
-    default: throw Error("QFunction not available for H1 hexahedra");
-  }
+  h1_terms(so, a.use_v, a.use_g, a.c_mass, a.c_diff);
   const size_t lds = sizeof(double) * 10 * (size_t)so.Q;
   hipLaunchKernelGGL(h1_hex_diag_kernel, dim3(so.ne), dim3(128), lds, s, a);
   PA_HIP(hipGetLastError());

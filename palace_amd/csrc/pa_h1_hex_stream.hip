@@ -7,7 +7,7 @@
 // y += A x, matrix-free D and the other quadrature sizes.
 #include <string>
 
-#include "pa_internal.hpp"
+#include "pa_hex_core.hpp"
 
 namespace pa {
 
@@ -19,19 +19,10 @@ constexpr int kIdxStart0 = streamhost::kIdxStart0H1;  // 28 run starts (27 entit
 constexpr int kH1StreamWaves = 2;
 
 template <int P1>
-struct H1StreamTab {  // first two rows of the mirror-symmetric 1-D tables (Q1 = 4)
+struct H1StreamTab {  // first two rows of the mirror-symmetric 1-D tables (Q1 = 4; whole half rows, pa_hex_core.hpp)
   double Bc[2 * (P1 + 1)];
   double Gc[2 * (P1 + 1)];
 };
-
-template <int N>
-__device__ __forceinline__ double hs_even(const double *H, const int q, const int i) {
-  return (q < 2) ? H[q * N + i] : H[(3 - q) * N + (N - 1 - i)];
-}
-template <int N>
-__device__ __forceinline__ double hs_odd(const double *H, const int q, const int i) {
-  return (q < 2) ? H[q * N + i] : -H[(3 - q) * N + (N - 1 - i)];
-}
 
 template <int P1>
 struct H1StreamArgs {
@@ -50,25 +41,9 @@ struct H1StreamArgs {
   H1StreamTab<P1> tab;
 };
 
-__device__ __forceinline__ void hs_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-template <int P1>
-struct H1SLayout {  // H1Layout<P1, 4> of pa_h1_hex.hip
-  static constexpr int NC = P1 + 1, Q1 = 4;
-  static constexpr int A_FIELD = Q1 * NC * NC, B_FIELD = Q1 * Q1 * NC;
-  static constexpr int ELEM = 2 * A_FIELD + 3 * B_FIELD;
-  static constexpr int ELEM_PAD = ((ELEM + 15) / 16 * 16) | 16;
-  __device__ static __forceinline__ int ia(int f, int qx, int j, int k) { return f * A_FIELD + (qx * NC + j) * NC + k; }
-  __device__ static __forceinline__ int ib(int f, int qx, int qy, int k) { return 2 * A_FIELD + f * B_FIELD + (qx * Q1 + qy) * NC + k; }
-};
-
 template <int P1, bool USE_V, bool USE_G, int MINW, bool SPLIT = false>
 __global__ __launch_bounds__(64 * kH1StreamWaves, MINW) void h1_hex_stream_kernel(const H1StreamArgs<P1> a) {
-  using L = H1SLayout<P1>;
+  using L = H1Layout<P1, 4>;
   constexpr int Q1 = 4, NC = P1 + 1, PP = NC * NC * NC, NPL = (PP + 15) / 16, NPK = (NPL + 3) / 4;
   constexpr int NG = (USE_V ? 1 : 0) + (USE_G ? 6 : 0);
   constexpr int LDS_SIDE = (PP + 1) / 2 + (NPK + 1) * 8;
@@ -102,7 +77,7 @@ __global__ __launch_bounds__(64 * kH1StreamWaves, MINW) void h1_hex_stream_kerne
   auto gather = [&](int (&s)[NPL + 2], const unsigned (&p)[NPK + 1], double (&xv)[NPL], int *stab, const int t) {
     stab[t] = s[NPL];
     if (t < 12) stab[16 + t] = s[NPL + 1];
-    hs_sync();
+    wave_sync();
     const unsigned fw = p[NPK];
 #pragma unroll
     for (int r = 0; r < NPL; r++) {
@@ -165,14 +140,14 @@ __global__ __launch_bounds__(64 * kH1StreamWaves, MINW) void h1_hex_stream_kerne
     }
 #pragma unroll
     for (int k = 0; k <= NPK; k++) side[2 * ((PP + 1) / 2) + 16 * k + t] = (int)pA[k];
-    hs_sync();
+    wave_sync();
     double u[NC];
     {
       const bool act = ta < NC && tb < NC;
 #pragma unroll
       for (int i = 0; i < NC; i++) u[i] = act ? sm[i + NC * (ta + NC * tb)] : 0.0;
     }
-    hs_sync();
+    wave_sync();
 
     double V[Q1], GV[3][Q1];
     // ---- forward: pass X, lane (j, k)
@@ -183,8 +158,8 @@ __global__ __launch_bounds__(64 * kH1StreamWaves, MINW) void h1_hex_stream_kerne
         double v = 0.0, d = 0.0;
 #pragma unroll
         for (int i = 0; i < NC; i++) {
-          v += hs_even<NC>(Bc, qx, i) * u[i];
-          if (USE_G) d += hs_odd<NC>(Gc, qx, i) * u[i];
+          v += half_even<NC, Q1>(Bc, qx, i) * u[i];
+          if (USE_G) d += half_odd<NC, Q1>(Gc, qx, i) * u[i];
         }
         if (act) {
           sm[L::ia(0, qx, ta, tb)] = v;
@@ -192,7 +167,7 @@ __global__ __launch_bounds__(64 * kH1StreamWaves, MINW) void h1_hex_stream_kerne
         }
       }
     }
-    hs_sync();
+    wave_sync();
     // pass Y, lane (qx, k)
     {
       const bool act = tb < NC;
@@ -207,9 +182,9 @@ __global__ __launch_bounds__(64 * kH1StreamWaves, MINW) void h1_hex_stream_kerne
         double vv = 0.0, vd = 0.0, dv = 0.0;
 #pragma unroll
         for (int j = 0; j < NC; j++) {
-          vv += hs_even<NC>(Bc, qy, j) * v[j];
-          if (USE_G) vd += hs_odd<NC>(Gc, qy, j) * v[j];
-          if (USE_G) dv += hs_even<NC>(Bc, qy, j) * d[j];
+          vv += half_even<NC, Q1>(Bc, qy, j) * v[j];
+          if (USE_G) vd += half_odd<NC, Q1>(Gc, qy, j) * v[j];
+          if (USE_G) dv += half_even<NC, Q1>(Bc, qy, j) * d[j];
         }
         if (act) {
           sm[L::ib(0, ta, qy, tb)] = vv;
@@ -217,7 +192,7 @@ __global__ __launch_bounds__(64 * kH1StreamWaves, MINW) void h1_hex_stream_kerne
         }
       }
     }
-    hs_sync();
+    wave_sync();
     // pass Z, lane (qx, qy)
     {
       double vv[NC], vd[NC], dv[NC];
@@ -231,29 +206,23 @@ __global__ __launch_bounds__(64 * kH1StreamWaves, MINW) void h1_hex_stream_kerne
         double val = 0.0, dz = 0.0, dy = 0.0, dx = 0.0;
 #pragma unroll
         for (int k = 0; k < NC; k++) {
-          if (USE_V) val += hs_even<NC>(Bc, qz, k) * vv[k];
+          if (USE_V) val += half_even<NC, Q1>(Bc, qz, k) * vv[k];
           if (USE_G) {
-            dz += hs_odd<NC>(Gc, qz, k) * vv[k];
-            dy += hs_even<NC>(Bc, qz, k) * vd[k];
-            dx += hs_even<NC>(Bc, qz, k) * dv[k];
+            dz += half_odd<NC, Q1>(Gc, qz, k) * vv[k];
+            dy += half_even<NC, Q1>(Bc, qz, k) * vd[k];
+            dx += half_even<NC, Q1>(Bc, qz, k) * dv[k];
           }
         }
         V[qz] = val, GV[0][qz] = dx, GV[1][qz] = dy, GV[2][qz] = dz;
       }
     }
-    hs_sync();
+    wave_sync();
 
     // ---- D: packed pre-assembled h1_1 / hcurl_33 on grad u / hcurlmass_33
 #pragma unroll
     for (int qz = 0; qz < Q1; qz++) {
       if (USE_V) V[qz] *= gd[qz][0];
-      if (USE_G) {
-        const double *m = &gd[qz][USE_V ? 1 : 0];
-        const double x0 = GV[0][qz], x1 = GV[1][qz], x2 = GV[2][qz];
-        GV[0][qz] = m[0] * x0 + m[1] * x1 + m[2] * x2;
-        GV[1][qz] = m[1] * x0 + m[3] * x1 + m[4] * x2;
-        GV[2][qz] = m[2] * x0 + m[4] * x1 + m[5] * x2;
-      }
+      if (USE_G) sym_mv(&gd[qz][USE_V ? 1 : 0], GV[0][qz], GV[1][qz], GV[2][qz], GV[0][qz], GV[1][qz], GV[2][qz]);
     }
 
     // ---- transposed passes: Z^T lane (qx, qy)
@@ -263,18 +232,18 @@ __global__ __launch_bounds__(64 * kH1StreamWaves, MINW) void h1_hex_stream_kerne
         double vv = 0.0, vd = 0.0, dv = 0.0;
 #pragma unroll
         for (int qz = 0; qz < Q1; qz++) {
-          if (USE_V) vv += hs_even<NC>(Bc, qz, k) * V[qz];
+          if (USE_V) vv += half_even<NC, Q1>(Bc, qz, k) * V[qz];
           if (USE_G) {
-            vv += hs_odd<NC>(Gc, qz, k) * GV[2][qz];
-            vd += hs_even<NC>(Bc, qz, k) * GV[1][qz];
-            dv += hs_even<NC>(Bc, qz, k) * GV[0][qz];
+            vv += half_odd<NC, Q1>(Gc, qz, k) * GV[2][qz];
+            vd += half_even<NC, Q1>(Bc, qz, k) * GV[1][qz];
+            dv += half_even<NC, Q1>(Bc, qz, k) * GV[0][qz];
           }
         }
         sm[L::ib(0, ta, tb, k)] = vv;
         if (USE_G) sm[L::ib(1, ta, tb, k)] = vd, sm[L::ib(2, ta, tb, k)] = dv;
       }
     }
-    hs_sync();
+    wave_sync();
     // x of the next batch: in flight during the remaining transposed passes
     double xB[NPL];
     __builtin_amdgcn_sched_barrier(0);
@@ -295,9 +264,9 @@ __global__ __launch_bounds__(64 * kH1StreamWaves, MINW) void h1_hex_stream_kerne
         double v = 0.0, d = 0.0;
 #pragma unroll
         for (int qy = 0; qy < Q1; qy++) {
-          v += hs_even<NC>(Bc, qy, j) * vv[qy];
-          if (USE_G) v += hs_odd<NC>(Gc, qy, j) * vd[qy];
-          if (USE_G) d += hs_even<NC>(Bc, qy, j) * dv[qy];
+          v += half_even<NC, Q1>(Bc, qy, j) * vv[qy];
+          if (USE_G) v += half_odd<NC, Q1>(Gc, qy, j) * vd[qy];
+          if (USE_G) d += half_even<NC, Q1>(Bc, qy, j) * dv[qy];
         }
         if (act) {
           sm[L::ia(0, ta, j, tb)] = v;
@@ -305,7 +274,7 @@ __global__ __launch_bounds__(64 * kH1StreamWaves, MINW) void h1_hex_stream_kerne
         }
       }
     }
-    hs_sync();
+    wave_sync();
     // X^T lane (j, k)
     {
       const bool act = ta < NC && tb < NC;
@@ -320,13 +289,13 @@ __global__ __launch_bounds__(64 * kH1StreamWaves, MINW) void h1_hex_stream_kerne
         double r = 0.0;
 #pragma unroll
         for (int qx = 0; qx < Q1; qx++) {
-          r += hs_even<NC>(Bc, qx, i) * v[qx];
-          if (USE_G) r += hs_odd<NC>(Gc, qx, i) * d[qx];
+          r += half_even<NC, Q1>(Bc, qx, i) * v[qx];
+          if (USE_G) r += half_odd<NC, Q1>(Gc, qx, i) * d[qx];
         }
         u[i] = r;
       }
     }
-    hs_sync();
+    wave_sync();
     // E^T: results into tensor order in LDS, out in sorted order; one unconditional store per entry
     {
       const bool act = ta < NC && tb < NC;
@@ -334,7 +303,7 @@ __global__ __launch_bounds__(64 * kH1StreamWaves, MINW) void h1_hex_stream_kerne
       for (int i = 0; i < NC; i++)
         if (act) sm[i + NC * (ta + NC * tb)] = u[i];
     }
-    hs_sync();
+    wave_sync();
 #pragma unroll
     for (int r = 0; r < NPL; r++) {
       const int m = (16 * r + 15 < PP) ? t + 16 * r : min(t + 16 * r, PP - 1), mt = m & 15, mr = m >> 4;
@@ -346,7 +315,7 @@ __global__ __launch_bounds__(64 * kH1StreamWaves, MINW) void h1_hex_stream_kerne
       double *dst = (fl & 2u) ? yd + d : a.ye + ((size_t)e * PP + m);
       *dst = v;
     }
-    hs_sync();
+    wave_sync();
     if (!more) break;
     b = bn;
 #pragma unroll
@@ -368,7 +337,7 @@ int device_cus_h1() {
 
 template <int P1, bool V, bool G, bool SPLIT = false>
 void launch_vg(const SubOp &so, H1StreamArgs<P1> &a, hipStream_t s) {
-  using L = H1SLayout<P1>;
+  using L = H1Layout<P1, 4>;
   constexpr int MINW = 3;
   constexpr int NC = P1 + 1, PP = NC * NC * NC, NPL = (PP + 15) / 16, NPK = (NPL + 3) / 4;
   for (int i = 0; i < 2 * NC; i++) a.tab.Bc[i] = so.Bc[i], a.tab.Gc[i] = so.Gc[i];

@@ -373,7 +373,6 @@ void launch_h1_hex_apply(const SubOp &so, const double *x, bool masked, hipStrea
 void launch_h1_hex_qdata(SubOp &so, hipStream_t s);
 void launch_h1_hex_diag(const SubOp &so, double *diag, hipStream_t s);
 // pa_rt_hex.hip: Raviart-Thomas hexahedra (mass, div-div, div-div + mass); the E-vector + gather form of E^T only
-bool rt_hex_supported(int p, int q1d);
 void launch_rt_hex_apply(const SubOp &so, const double *x, bool masked, hipStream_t s);
 void launch_rt_hex_qdata(SubOp &so, hipStream_t s);
 void launch_rt_hex_diag(const SubOp &so, double *diag, hipStream_t s);

@@ -10,6 +10,7 @@
 
 #include "linalg.hpp"
 #include "comm.hpp"
+#include "pa_device.hpp"
 
 namespace palace {
 
@@ -36,11 +37,7 @@ struct InterpArgs {
 // transpose of that operator.
 constexpr int kOwnBit = 1 << 29;
 
-__device__ __forceinline__ void wsync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
+using pa::wave_sync;
 
 // One component block: coarse dims (nc[0..2]) -> fine dims (nf[0..2]); M[d] the 1-D matrix
 // [nf[d]][nc[d]] of direction d.  TRANSPOSE applies the transposed element matrix.
@@ -73,7 +70,7 @@ __device__ void interp_block(const InterpArgs &a, const int e, const bool active
         if (lane_ok && act) sA[(fi * nc1 + ta) * nc2 + tb] = v;
       }
     }
-    wsync();
+    wave_sync();
     // pass Y: lane (i_f, k_c) -> fine j
     {
       const bool act = ta < nf0 && tb < nc2;
@@ -85,7 +82,7 @@ __device__ void interp_block(const InterpArgs &a, const int e, const bool active
         if (lane_ok && act) sB[(ta * nf1 + fj) * nc2 + tb] = v;
       }
     }
-    wsync();
+    wave_sync();
     // pass Z: lane (i_f, j_f) -> fine k, scale by 1/multiplicity, scatter-add
     {
       const bool act = ta < nf0 && tb < nf1;
@@ -101,7 +98,7 @@ __device__ void interp_block(const InterpArgs &a, const int e, const bool active
         }
       }
     }
-    wsync();
+    wave_sync();
   } else {
     // pass Z^T: lane (i_f, j_f): gather fine (scaled), contract fine k -> coarse k
     {
@@ -123,7 +120,7 @@ __device__ void interp_block(const InterpArgs &a, const int e, const bool active
         if (lane_ok && act) sB[(ta * nf1 + tb) * nc2 + k] = v;
       }
     }
-    wsync();
+    wave_sync();
     // pass Y^T: lane (i_f, k_c): contract fine j -> coarse j
     {
       const bool act = ta < nf0 && tb < nc2;
@@ -135,7 +132,7 @@ __device__ void interp_block(const InterpArgs &a, const int e, const bool active
         if (lane_ok && act) sA[(ta * nc1 + j) * nc2 + tb] = v;
       }
     }
-    wsync();
+    wave_sync();
     // pass X^T: lane (j_c, k_c): contract fine i -> coarse i, scatter-add
     {
       const bool act = ta < nc1 && tb < nc2;
@@ -152,7 +149,7 @@ __device__ void interp_block(const InterpArgs &a, const int e, const bool active
         }
       }
     }
-    wsync();
+    wave_sync();
   }
 }
 
@@ -250,7 +247,7 @@ __device__ __forceinline__ void blk_apply_fwd(const InterpArgs &a, const bool ac
       if (lane_ok && act) sA[(fi * NC1 + ta) * NC2 + tb] = v;
     }
   }
-  wsync();
+  wave_sync();
   {
     const bool act = ta < NF0 && tb < NC2;
     double u[NC1];
@@ -264,7 +261,7 @@ __device__ __forceinline__ void blk_apply_fwd(const InterpArgs &a, const bool ac
       if (lane_ok && act) sB[(ta * NF1 + fj) * NC2 + tb] = v;
     }
   }
-  wsync();
+  wave_sync();
   {
     const bool act = ta < NF0 && tb < NF1;
     double u[NC2];
@@ -282,7 +279,7 @@ __device__ __forceinline__ void blk_apply_fwd(const InterpArgs &a, const bool ac
       }
     }
   }
-  wsync();
+  wave_sync();
 }
 // (A) transpose: the fine index words of the lane's line; (B) the owner-masked fine values
 template <class D>
@@ -321,7 +318,7 @@ __device__ __forceinline__ void blk_apply_tr(const bool lane_ok, const int ta, c
       if (lane_ok && act) sB[(ta * NF1 + tb) * NC2 + k] = v;
     }
   }
-  wsync();
+  wave_sync();
   {
     const bool act = ta < NF0 && tb < NC2;
     double u[NF1];
@@ -335,7 +332,7 @@ __device__ __forceinline__ void blk_apply_tr(const bool lane_ok, const int ta, c
       if (lane_ok && act) sA[(ta * NC1 + j) * NC2 + tb] = v;
     }
   }
-  wsync();
+  wave_sync();
   {
     const bool act = ta < NC1 && tb < NC2;
     double u[NF0];
@@ -349,7 +346,7 @@ __device__ __forceinline__ void blk_apply_tr(const bool lane_ok, const int ta, c
       out[i] = accumulate ? out[i] + v : v;
     }
   }
-  wsync();
+  wave_sync();
 }
 template <class D>
 __device__ __forceinline__ void blk_store_tr(const InterpArgs &a, const int e, const bool active, const int ta, const int tb, const int off_c,
@@ -598,7 +595,7 @@ __global__ __launch_bounds__(64 * kDenseInterpWaves) void dense_interp_kernel(co
             s0[i] = v;
           }
       }
-      wsync();
+      wave_sync();
       if (a.T_d) {  // u = T x_e
 #pragma unroll
         for (int h = 0; h < kDenseInterpEPW; h++) {
@@ -610,14 +607,14 @@ __global__ __launch_bounds__(64 * kDenseInterpWaves) void dense_interp_kernel(co
               s1[i] = (double)T[3 * i] * s0[max(i - 1, 0)] + (double)T[3 * i + 1] * s0[i] + (double)T[3 * i + 2] * s0[min(i + 1, a.Pd - 1)];
           }
         }
-        wsync();
+        wave_sync();
 #pragma unroll
         for (int h = 0; h < kDenseInterpEPW; h++) {
           double *s0 = strip + (2 * h) * pmax, *s1 = s0 + pmax;
           if (e0 + h < a.ne)
             for (int i = lane; i < a.Pd; i += 64) s0[i] = s1[i];
         }
-        wsync();
+        wave_sync();
       }
       if (NR > 0) {  // v = M u: the lane's row from registers, u broadcast from the strips
         double v[kDenseInterpEPW];
@@ -650,7 +647,7 @@ __global__ __launch_bounds__(64 * kDenseInterpWaves) void dense_interp_kernel(co
           }
         }
       }
-      wsync();
+      wave_sync();
 #pragma unroll
       for (int h = 0; h < kDenseInterpEPW; h++) {
         const int e = e0 + h;
@@ -685,7 +682,7 @@ __global__ __launch_bounds__(64 * kDenseInterpWaves) void dense_interp_kernel(co
             s0[j] = v;
           }
       }
-      wsync();
+      wave_sync();
       if (a.B_r) {  // v = B z
 #pragma unroll
         for (int h = 0; h < kDenseInterpEPW; h++) {
@@ -697,14 +694,14 @@ __global__ __launch_bounds__(64 * kDenseInterpWaves) void dense_interp_kernel(co
               s1[j] = (double)B[3 * j] * s0[max(j - 1, 0)] + (double)B[3 * j + 1] * s0[j] + (double)B[3 * j + 2] * s0[min(j + 1, a.Pr - 1)];
           }
         }
-        wsync();
+        wave_sync();
 #pragma unroll
         for (int h = 0; h < kDenseInterpEPW; h++) {
           double *s0 = strip + (2 * h) * pmax, *s1 = s0 + pmax;
           if (e0 + h < a.ne)
             for (int j = lane; j < a.Pr; j += 64) s0[j] = s1[j];
         }
-        wsync();
+        wave_sync();
       }
       if (NR > 0) {  // u = M^T v: the lane's column from registers
         double v[kDenseInterpEPW];
@@ -736,7 +733,7 @@ __global__ __launch_bounds__(64 * kDenseInterpWaves) void dense_interp_kernel(co
           }
         }
       }
-      wsync();
+      wave_sync();
 #pragma unroll
       for (int h = 0; h < kDenseInterpEPW; h++) {
         const int e = e0 + h;
@@ -756,7 +753,7 @@ __global__ __launch_bounds__(64 * kDenseInterpWaves) void dense_interp_kernel(co
         }
       }
     }
-    wsync();  // (the wave's strips are reused by its next group)
+    wave_sync();  // (the wave's strips are reused by its next group)
   }
 }
 

@@ -360,6 +360,18 @@ static void launch_iso(const NDArgs<P1, Q1> &a, bool iso, dim3 grid, dim3 block,
     hipLaunchKernelGGL((nd_hex_apply_kernel<P1, Q1, U, C, false, false, false>), grid, block, lds, s, a);
 }
 
+// QFunction id -> the terms (mass: values, curl-curl: curls) and their coefficients; the mixed curl forms of
+// hcurlhdiv_33_qf.h set neither flag but cross = 1 (f_apply_hcurlhdiv_33: values in, curl test functions out) / 2
+// (f_apply_hdivhcurl_33), with their coefficient in cm
+static void nd_terms(const SubOp &so, bool &use_u, bool &use_c, CoeffDev &cm, CoeffDev &cc, int &cross) {
+  use_u = so.qf == PA_QF_HCURL_33 || so.qf == PA_QF_HDIVMASS_33;
+  use_c = so.qf == PA_QF_HDIV_33 || so.qf == PA_QF_HDIVMASS_33;
+  cross = so.qf == PA_QF_HCURLHDIV_33 ? 1 : so.qf == PA_QF_HDIVHCURL_33 ? 2 : 0;
+  if (!use_u && !use_c && !cross) throw Error("QFunction not available for H(curl) hexahedra");
+  cm = (use_u || cross) ? so.c0.dev() : CoeffDev{};
+  cc = use_c ? (use_u ? so.c1 : so.c0).dev() : CoeffDev{};
+}
+
 template <int P1, int Q1>
 static void launch_pq(const SubOp &so, const double *x, double *y, double *ye, bool masked, hipStream_t s,
                       bool accumulate, int ess_policy, const double *x1, double *y1, double *ye1) {
@@ -389,50 +401,23 @@ static void launch_pq(const SubOp &so, const double *x, double *y, double *ye, b
   a.xcd_chunk = nblk >= 64 ? (nblk + 7) / 8 : 0;
   const dim3 grid(a.xcd_chunk > 0 ? 8 * a.xcd_chunk : nblk), block(64 * kWavesPerBlock);
   const size_t lds = sizeof(double) * (size_t)epb * L::ELEM_PAD;
-  switch (so.qf) {
-    case PA_QF_HDIV_33:
-      a.c_curl = so.c0.dev();
-      launch_iso<P1, Q1, false, true>(a, so.iso, grid, block, lds, s);
-      break;
-    case PA_QF_HCURL_33:
-      a.c_mass = so.c0.dev();
-      launch_iso<P1, Q1, true, false>(a, so.iso, grid, block, lds, s);
-      break;
-    case PA_QF_HDIVMASS_33:
-      a.c_mass = so.c0.dev();
-      a.c_curl = so.c1.dev();
-      launch_iso<P1, Q1, true, true>(a, so.iso, grid, block, lds, s);
-      break;
-    case PA_QF_HCURLHDIV_33:
-    case PA_QF_HDIVHCURL_33:
-      // both fields are evaluated, D couples values and curls (matrix-free, general 3 x 3 coefficient); the transposed
-      // operator of one form is the other one with the transposed coefficient (TransposeScope swaps the latter)
-      a.c_mass = a.c_curl = so.c0.dev();
-      a.cross = ((so.qf == PA_QF_HCURLHDIV_33) != TransposeScope::active()) ? 1 : 2;
-      launch_iso<P1, Q1, true, true>(a, false, grid, block, lds, s);
-      break;
-    default:
-      throw Error("QFunction not available for H(curl) hexahedra");
+  bool use_u, use_c;
+  nd_terms(so, use_u, use_c, a.c_mass, a.c_curl, a.cross);
+  if (a.cross) {
+    // both fields are evaluated, D couples values and curls (matrix-free, general 3 x 3 coefficient); the transposed
+    // operator of one form is the other one with the transposed coefficient (TransposeScope swaps the latter)
+    a.c_curl = a.c_mass;
+    if (TransposeScope::active()) a.cross = 3 - a.cross;
   }
+  const bool both = a.cross || (use_u && use_c);
+  if (!both && use_c)
+    launch_iso<P1, Q1, false, true>(a, so.iso, grid, block, lds, s);
+  else if (!both)
+    launch_iso<P1, Q1, true, false>(a, so.iso, grid, block, lds, s);
+  else
+    launch_iso<P1, Q1, true, true>(a, so.iso && !a.cross, grid, block, lds, s);
   PA_HIP(hipGetLastError());
 }
-
-#define PA_ND_DISPATCH(FN, ...)                                                           \
-  switch (so.p * 16 + so.q1d) {                                                            \
-    case 1 * 16 + 2: FN<1, 2>(__VA_ARGS__); break;                                         \
-    case 1 * 16 + 3: FN<1, 3>(__VA_ARGS__); break;                                         \
-    case 2 * 16 + 3: FN<2, 3>(__VA_ARGS__); break;                                         \
-    case 1 * 16 + 4: FN<1, 4>(__VA_ARGS__); break;                                         \
-    case 2 * 16 + 4: FN<2, 4>(__VA_ARGS__); break;                                         \
-    case 3 * 16 + 4: FN<3, 4>(__VA_ARGS__); break;                                         \
-    case 1 * 16 + 5: FN<1, 5>(__VA_ARGS__); break;                                         \
-    case 2 * 16 + 5: FN<2, 5>(__VA_ARGS__); break;                                         \
-    case 3 * 16 + 5: FN<3, 5>(__VA_ARGS__); break;                                         \
-    case 4 * 16 + 5: FN<4, 5>(__VA_ARGS__); break;                                         \
-    default:                                                                               \
-      throw Error("no H(curl) hex kernel for order " + std::to_string(so.p) + " with " +   \
-                  std::to_string(so.q1d) + " points per direction");                       \
-  }
 
 // ye != nullptr: write the element-local results (E-vector) instead of scattering atomically into y
 // masked: gather through the essential-dof-flagged index array (pa_op_set_essential)
@@ -440,7 +425,7 @@ bool nd_hex_supports_two_rhs(const SubOp &so) { return so.fe_type == PA_FE_HCURL
 
 void launch_nd_hex_apply(const SubOp &so, const double *x, double *y, double *ye, bool masked, hipStream_t s,
                          bool accumulate, int ess_policy, const double *x1, double *y1, double *ye1) {
-  PA_ND_DISPATCH(launch_pq, so, x, y, ye, masked, s, accumulate, ess_policy, x1, y1, ye1)
+  PA_HEX_DISPATCH(launch_pq, "H(curl)", so, x, y, ye, masked, s, accumulate, ess_policy, x1, y1, ye1)
 }
 
 // ---- E^T as a gather: y_d (+)= sum over the element-local copies of dof d -----------------------
@@ -573,30 +558,22 @@ __global__ void nd_hex_qdata_kernel(const int ne, const int Q, const int q1d, co
     }
     for (int col = 0; col < 3; col++)
       mult_AtBCx33(Jl, Cm, Jl, col == 0, col == 1, col == 2, w, M[0 + 3 * col], M[1 + 3 * col], M[2 + 3 * col]);
-    // symmetric by construction when C is; average the off-diagonal pairs against rounding drift
-    out[nd_qd_offset(q1d, o + 0, q)] = M[0];
-    out[nd_qd_offset(q1d, o + 1, q)] = 0.5 * (M[3] + M[1]);
-    out[nd_qd_offset(q1d, o + 2, q)] = 0.5 * (M[6] + M[2]);
-    out[nd_qd_offset(q1d, o + 3, q)] = M[4];
-    out[nd_qd_offset(q1d, o + 4, q)] = 0.5 * (M[7] + M[5]);
-    out[nd_qd_offset(q1d, o + 5, q)] = M[8];
+    sym_pack(M, [&](const int i, const double v) { out[nd_qd_offset(q1d, o + i, q)] = v; });
     o += 6;
   }
 }
 
 void launch_nd_hex_qdata(SubOp &so, hipStream_t s) {
-  const bool use_u = so.qf == PA_QF_HCURL_33 || so.qf == PA_QF_HDIVMASS_33;
-  const bool use_c = so.qf == PA_QF_HDIV_33 || so.qf == PA_QF_HDIVMASS_33;
+  bool use_u, use_c;
+  CoeffDev cm, cc;
+  int cross;  // (the mixed forms are matrix-free: no q-data is ever asked for them)
+  nd_terms(so, use_u, use_c, cm, cc, cross);
   auto *qd = new QData;
   qd->ncomp = 6 * ((int)use_u + (int)use_c);
   // (padded to a multiple of four elements for the streaming kernel; the pad is never used in a result)
   const size_t nq = (size_t)((so.ne + 3) & ~3) * qd->ncomp * nd_qd_cstride(so.q1d);
   qd->d = dev_alloc<double>(nq);
   PA_HIP(hipMemsetAsync(qd->d, 0, nq * sizeof(double), s));
-  CoeffDev cm{}, cc{};
-  if (so.qf == PA_QF_HDIV_33) cc = so.c0.dev();
-  if (so.qf == PA_QF_HCURL_33) cm = so.c0.dev();
-  if (so.qf == PA_QF_HDIVMASS_33) cm = so.c0.dev(), cc = so.c1.dev();
   const long long n = (long long)so.ne * so.Q;
   hipLaunchKernelGGL(nd_hex_qdata_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, so.ne, so.Q, so.q1d,
                      so.geom->d_geom, cm, cc, (int)use_u, (int)use_c, qd->d);
@@ -756,16 +733,7 @@ void launch_nd_hex_diag(const SubOp &so, double *diag, hipStream_t s) {
   a.y = diag;
   const int nc = so.p + 1;
   a.Bo = so.d_tab, a.Bc = so.d_tab + so.q1d * so.p, a.Gc = a.Bc + so.q1d * nc;
-  a.use_u = a.use_c = false;
-  a.cross = 0;
-  switch (so.qf) {
-    case PA_QF_HCURLHDIV_33: a.c_mass = so.c0.dev(), a.cross = 1; break;
-    case PA_QF_HDIVHCURL_33: a.c_mass = so.c0.dev(), a.cross = 2; break;
-    case PA_QF_HDIV_33: a.c_curl = so.c0.dev(), a.use_c = true; break;
-    case PA_QF_HCURL_33: a.c_mass = so.c0.dev(), a.use_u = true; break;
-    case PA_QF_HDIVMASS_33: a.c_mass = so.c0.dev(), a.c_curl = so.c1.dev(), a.use_u = a.use_c = true; break;
-    default: throw Error("QFunction not available for H(curl) hexahedra");
-  }
+  nd_terms(so, a.use_u, a.use_c, a.c_mass, a.c_curl, a.cross);
   const size_t lds = sizeof(double) * 18 * (size_t)so.Q;
   hipLaunchKernelGGL(nd_hex_diag_kernel, dim3(so.ne), dim3(128), lds, s, a);
   PA_HIP(hipGetLastError());

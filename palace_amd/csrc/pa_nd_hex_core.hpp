@@ -1,12 +1,12 @@
-// Shared device code of the H(curl) hexahedron kernels (pa_nd_hex.hip, pa_nd_hex_stream.hip): the mirror-symmetric
-// half tables, the LDS layouts of the contraction buffers and the sum-factorised forward / transposed passes of one
-// vector component.  See pa_nd_hex.hip for the mapping of elements and lines to lanes.
+// Shared device code of the H(curl) hexahedron kernels (pa_nd_hex.hip, pa_nd_hex_stream.hip, pa_nd_hex_stream5.hip): the
+// truncated mirror-symmetric half tables, the LDS layouts of the contraction buffers and the sum-factorised forward /
+// transposed passes of one vector component.  What all hexahedron families share is in pa_hex_core.hpp; see pa_nd_hex.hip for
+// the mapping of elements and lines to lanes.
 #pragma once
 
 #include <type_traits>
 
-#include "pa_internal.hpp"
-#include "pa_device.hpp"
+#include "pa_hex_core.hpp"
 
 namespace pa {
 

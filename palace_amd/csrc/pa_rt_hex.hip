@@ -9,29 +9,26 @@
 // Same mapping as pa_h1_hex.hip / pa_nd_hex.hip: Q1^2 lanes per element, 64 / Q1^2 elements per wave, passes X -> Y -> Z
 // through LDS inside the wave (wave-level syncs only), lane (qx, qy) ends with its qz column of the three values and the
 // divergence; E is the sorted gather through d_sidx / d_perm, E^T the E-vector + gather form.
-#include "pa_internal.hpp"
+#include "pa_hex_core.hpp"
 
 namespace pa {
 
 template <int P1, int Q1>
 struct RTTab {
-  static constexpr int QH = (Q1 + 1) / 2;  // mirror symmetry of the tables, see pa_nd_hex.hip
+  static constexpr int QH = (Q1 + 1) / 2;  // mirror symmetry: whole half rows, pa_hex_core.hpp
   double Bo[QH * P1];
   double Bc[QH * (P1 + 1)];
   double Gc[QH * (P1 + 1)];
 };
 
-// Mirror symmetry T[q][i] = +-T[Q1-1-q][N-1-i]: rows q >= QH come from the stored half, and the middle row of an odd rule from
-// its own first half, so that fewer table entries have to stay resident in scalar registers.
+// the tables are read with the second half of an odd rule's middle row mirrored (pa_hex_core.hpp)
 template <int N, int Q1>
 __device__ __forceinline__ double rt_even(const double *H, const int q, const int i) {
-  const bool flip = q >= (Q1 + 1) / 2 || ((Q1 & 1) && q == Q1 / 2 && 2 * i > N - 1);
-  return flip ? H[(Q1 - 1 - q) * N + (N - 1 - i)] : H[q * N + i];
+  return half_even<N, Q1, true>(H, q, i);
 }
 template <int N, int Q1>
 __device__ __forceinline__ double rt_odd(const double *H, const int q, const int i) {
-  const bool flip = q >= (Q1 + 1) / 2 || ((Q1 & 1) && q == Q1 / 2 && 2 * i > N - 1);
-  return flip ? -H[(Q1 - 1 - q) * N + (N - 1 - i)] : H[q * N + i];
+  return half_odd<N, Q1, true>(H, q, i);
 }
 
 template <int P1, int Q1>
@@ -48,66 +45,10 @@ struct RTArgs {
   RTTab<P1, Q1> tab;
 };
 
-__device__ __forceinline__ void rt_wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// utils_33_qf.h:20-37 on the stored adj(J)^T / detJ: J / detJ
-__device__ __forceinline__ void rt_adjJt33(const double J[9], double A[9]) {
-  A[0] = J[4] * J[8] - J[7] * J[5];
-  A[3] = J[7] * J[2] - J[1] * J[8];
-  A[6] = J[1] * J[5] - J[4] * J[2];
-  A[1] = J[6] * J[5] - J[3] * J[8];
-  A[4] = J[0] * J[8] - J[6] * J[2];
-  A[7] = J[3] * J[2] - J[0] * J[5];
-  A[2] = J[3] * J[7] - J[6] * J[4];
-  A[5] = J[6] * J[1] - J[0] * J[7];
-  A[8] = J[0] * J[4] - J[3] * J[1];
-}
-
-// utils_33_qf.h:64-84: y = s A^T B C x
-__device__ __forceinline__ void rt_AtBCx33(const double A[9], const double B[9], const double C[9], const double x0,
-                                           const double x1, const double x2, const double s, double &y0, double &y1,
-                                           double &y2) {
-  const double t0 = C[0] * x0 + C[3] * x1 + C[6] * x2;
-  const double t1 = C[1] * x0 + C[4] * x1 + C[7] * x2;
-  const double t2 = C[2] * x0 + C[5] * x1 + C[8] * x2;
-  const double z0 = B[0] * t0 + B[3] * t1 + B[6] * t2;
-  const double z1 = B[1] * t0 + B[4] * t1 + B[7] * t2;
-  const double z2 = B[2] * t0 + B[5] * t1 + B[8] * t2;
-  y0 = s * (A[0] * z0 + A[1] * z1 + A[2] * z2);
-  y1 = s * (A[3] * z0 + A[4] * z1 + A[5] * z2);
-  y2 = s * (A[6] * z0 + A[7] * z1 + A[8] * z2);
-}
-
-__device__ __forceinline__ void rt_coeff3(const CoeffDev &c, const int attr, double Cm[9]) {
-  const int k = (c.nattr > 0) ? c.attr_mat[attr - 1] : 0;
-#pragma unroll
-  for (int i = 0; i < 9; i++) Cm[i] = c.mat[9 * k + i];
-}
-__device__ __forceinline__ double rt_coeff1(const CoeffDev &c, const int attr) {
-  return c.mat[(c.nattr > 0) ? c.attr_mat[attr - 1] : 0];
-}
-
 // LDS of one element: the P dofs in tensor order, then two fields after pass X [Q1][NC][NC] and two after pass Y
 // [Q1][Q1][NC] (field 0: the chain of values, field 1: the chain of the divergence once the pass along c has split them)
 template <int P1, int Q1>
-struct RTLayout {
-  static constexpr int NC = P1 + 1;
-  static constexpr int T = Q1 * Q1;
-  static constexpr int EPW = 64 / T;
-  static constexpr int P = 3 * P1 * P1 * NC;
-  static constexpr int A_FIELD = Q1 * NC * NC;
-  static constexpr int B_FIELD = Q1 * Q1 * NC;
-  static constexpr int ELEM = P + 2 * A_FIELD + 2 * B_FIELD;
-  static constexpr int ELEM_PAD = ((ELEM + 15) / 16 * 16) | 16;
-  __device__ static __forceinline__ int ia(int f, int qx, int j, int k) { return P + f * A_FIELD + (qx * NC + j) * NC + k; }
-  __device__ static __forceinline__ int ib(int f, int qx, int qy, int k) {
-    return P + 2 * A_FIELD + f * B_FIELD + (qx * Q1 + qy) * NC + k;
-  }
-};
+using RTLayout = HexLayout<P1, Q1, 3 * P1 * P1 * (P1 + 1), 2, 2>;
 
 constexpr int kRTWaves = 4;
 
@@ -146,7 +87,7 @@ __device__ __forceinline__ void rt_fwd_comp(const RTTab<P1, Q1> &tab, double *sm
       }
     }
   }
-  rt_wave_sync();
+  wave_sync();
   // pass Y, lane (qx, k)
   {
     const bool act = tb < NZ;
@@ -178,7 +119,7 @@ __device__ __forceinline__ void rt_fwd_comp(const RTTab<P1, Q1> &tab, double *sm
       }
     }
   }
-  rt_wave_sync();
+  wave_sync();
   // pass Z, lane (qx, qy)
   {
     double s0[NZ], s1[NZ];
@@ -237,7 +178,7 @@ __device__ __forceinline__ void rt_bwd_comp(const RTTab<P1, Q1> &tab, double *sm
       }
     }
   }
-  rt_wave_sync();
+  wave_sync();
   // Y^T, lane (qx, k)
   {
     const bool act = tb < NZ;
@@ -269,7 +210,7 @@ __device__ __forceinline__ void rt_bwd_comp(const RTTab<P1, Q1> &tab, double *sm
       }
     }
   }
-  rt_wave_sync();
+  wave_sync();
   // X^T, lane (j, k) -> dofs [i][j][k] of the component
   {
     const bool act = ta < NY && tb < NZ;
@@ -301,7 +242,7 @@ __device__ __forceinline__ void rt_bwd_comp(const RTTab<P1, Q1> &tab, double *sm
 template <int P1, int Q1, bool USE_V, bool USE_DIV, bool QD>
 __global__ __launch_bounds__(64 * kRTWaves, 2) void rt_hex_apply_kernel(const RTArgs<P1, Q1> a) {
   using L = RTLayout<P1, Q1>;
-  constexpr int Q = Q1 * Q1 * Q1, P = L::P;
+  constexpr int Q = Q1 * Q1 * Q1, P = L::BASE;
   extern __shared__ __attribute__((aligned(16))) double smem[];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int sub = lane / L::T, t = lane - sub * L::T;
@@ -340,7 +281,7 @@ __global__ __launch_bounds__(64 * kRTWaves, 2) void rt_hex_apply_kernel(const RT
       sm[lp[r]] = neg[r] ? -v : v;
     }
   }
-  rt_wave_sync();
+  wave_sync();
 
   double V[3][Q1], DV[Q1];
 #pragma unroll
@@ -348,19 +289,13 @@ __global__ __launch_bounds__(64 * kRTWaves, 2) void rt_hex_apply_kernel(const RT
   rt_fwd_comp<P1, Q1, 0, USE_V, USE_DIV>(a.tab, sm, ta, tb, lane_ok, V[0], DV);
   rt_fwd_comp<P1, Q1, 1, USE_V, USE_DIV>(a.tab, sm, ta, tb, lane_ok, V[1], DV);
   rt_fwd_comp<P1, Q1, 2, USE_V, USE_DIV>(a.tab, sm, ta, tb, lane_ok, V[2], DV);
-  rt_wave_sync();
+  wave_sync();
 
   // ---- D (hdiv_33 / l2_1 / l2mass_33)
 #pragma unroll
   for (int qz = 0; qz < Q1; qz++) {
     if (QD) {
-      if (USE_V) {
-        const double *m = &gd[qz][0];
-        const double x0 = V[0][qz], x1 = V[1][qz], x2 = V[2][qz];
-        V[0][qz] = m[0] * x0 + m[1] * x1 + m[2] * x2;
-        V[1][qz] = m[1] * x0 + m[3] * x1 + m[4] * x2;
-        V[2][qz] = m[2] * x0 + m[4] * x1 + m[5] * x2;
-      }
+      if (USE_V) sym_mv(&gd[qz][0], V[0][qz], V[1][qz], V[2][qz], V[0][qz], V[1][qz], V[2][qz]);
       if (USE_DIV) DV[qz] *= gd[qz][NG - 1];
     } else {
       const double *g = a.geom + eg * 11 * Q + ta + Q1 * tb + Q1 * Q1 * qz;
@@ -370,13 +305,13 @@ __global__ __launch_bounds__(64 * kRTWaves, 2) void rt_hex_apply_kernel(const RT
         double adj[9], Jl[9], Cm[9];
 #pragma unroll
         for (int c = 0; c < 9; c++) adj[c] = g[(2 + c) * Q];
-        rt_adjJt33(adj, Jl);
-        rt_coeff3(a.c_mass, attr, Cm);
-        rt_AtBCx33(Jl, Cm, Jl, V[0][qz], V[1][qz], V[2][qz], wdetJ, V[0][qz], V[1][qz], V[2][qz]);
+        adjJt33(adj, Jl);
+        coeff_unpack3(a.c_mass, attr, Cm);
+        mult_AtBCx33(Jl, Cm, Jl, V[0][qz], V[1][qz], V[2][qz], wdetJ, V[0][qz], V[1][qz], V[2][qz]);
       }
       if (USE_DIV) {
         const double qw = a.w1[ta] * a.w1[tb] * a.w1[qz];
-        DV[qz] *= rt_coeff1(a.c_div, attr) * qw * qw / wdetJ;
+        DV[qz] *= coeff_unpack1(a.c_div, attr) * qw * qw / wdetJ;
       }
     }
   }
@@ -384,7 +319,7 @@ __global__ __launch_bounds__(64 * kRTWaves, 2) void rt_hex_apply_kernel(const RT
   rt_bwd_comp<P1, Q1, 0, USE_V, USE_DIV>(a.tab, sm, ta, tb, lane_ok, V[0], DV);
   rt_bwd_comp<P1, Q1, 1, USE_V, USE_DIV>(a.tab, sm, ta, tb, lane_ok, V[1], DV);
   rt_bwd_comp<P1, Q1, 2, USE_V, USE_DIV>(a.tab, sm, ta, tb, lane_ok, V[2], DV);
-  rt_wave_sync();
+  wave_sync();
   // E^T, first half: out of LDS in sorted order (coalesced).  The E-vector holds the unsigned element results: the gather
   // applies the orientation sign of the entry (d_tent).
 #pragma unroll
@@ -440,37 +375,11 @@ static void rt_launch_pq(const SubOp &so, const double *x, bool masked, hipStrea
   PA_HIP(hipGetLastError());
 }
 
-// the pairs of PA_ND_DISPATCH (pa_nd_hex.hip): an RT space sits on any geometry data an ND space of its order can
-#define PA_RT_DISPATCH(FN, ...)                                                           \
-  switch (so.p * 16 + so.q1d) {                                                            \
-    case 1 * 16 + 2: FN<1, 2>(__VA_ARGS__); break;                                         \
-    case 1 * 16 + 3: FN<1, 3>(__VA_ARGS__); break;                                         \
-    case 2 * 16 + 3: FN<2, 3>(__VA_ARGS__); break;                                         \
-    case 1 * 16 + 4: FN<1, 4>(__VA_ARGS__); break;                                         \
-    case 2 * 16 + 4: FN<2, 4>(__VA_ARGS__); break;                                         \
-    case 3 * 16 + 4: FN<3, 4>(__VA_ARGS__); break;                                         \
-    case 1 * 16 + 5: FN<1, 5>(__VA_ARGS__); break;                                         \
-    case 2 * 16 + 5: FN<2, 5>(__VA_ARGS__); break;                                         \
-    case 3 * 16 + 5: FN<3, 5>(__VA_ARGS__); break;                                         \
-    case 4 * 16 + 5: FN<4, 5>(__VA_ARGS__); break;                                         \
-    default:                                                                               \
-      throw Error("no H(div) hex kernel for order " + std::to_string(so.p) + " with " +    \
-                  std::to_string(so.q1d) + " points per direction");                       \
-  }
-
-bool rt_hex_supported(int p, int q1d) {
-  switch (p * 16 + q1d) {
-    case 1 * 16 + 2: case 1 * 16 + 3: case 2 * 16 + 3: case 1 * 16 + 4: case 2 * 16 + 4:
-    case 3 * 16 + 4: case 1 * 16 + 5: case 2 * 16 + 5: case 3 * 16 + 5: case 4 * 16 + 5: return true;
-  }
-  return false;
-}
-
 // writes the E-vector so.d_ye; the caller follows with launch_et_gather
 void launch_rt_hex_apply(const SubOp &so, const double *x, bool masked, hipStream_t s) {
   PA_REQUIRE(so.d_ye, "H(div) blocks use the gather form of E^T");
   PA_REQUIRE(!masked || so.d_sidx_bc, "pa_op_set_essential has not been called");
-  PA_RT_DISPATCH(rt_launch_pq, so, x, masked, s)
+  PA_HEX_DISPATCH(rt_launch_pq, "H(div)", so, x, masked, s)
 }
 
 // ---- packed q-data and diagonal (set-up) ----------------------------------------------------------
@@ -496,22 +405,16 @@ __global__ void rt_hex_qdata_kernel(const int ne, const int q1d, const double *_
   if (use_v) {
     double adj[9], Jl[9], Cm[9], M[9];
     for (int c = 0; c < 9; c++) adj[c] = g[(2 + c) * Q + q];
-    rt_adjJt33(adj, Jl);
-    rt_coeff3(c_mass, attr, Cm);
+    adjJt33(adj, Jl);
+    coeff_unpack3(c_mass, attr, Cm);
     for (int col = 0; col < 3; col++)
-      rt_AtBCx33(Jl, Cm, Jl, col == 0, col == 1, col == 2, w, M[0 + 3 * col], M[1 + 3 * col], M[2 + 3 * col]);
-    // symmetric by construction when C is; average the off-diagonal pairs against rounding drift
-    out[0 * Q] = M[0];
-    out[1 * Q] = 0.5 * (M[3] + M[1]);
-    out[2 * Q] = 0.5 * (M[6] + M[2]);
-    out[3 * Q] = M[4];
-    out[4 * Q] = 0.5 * (M[7] + M[5]);
-    out[5 * Q] = M[8];
+      mult_AtBCx33(Jl, Cm, Jl, col == 0, col == 1, col == 2, w, M[0 + 3 * col], M[1 + 3 * col], M[2 + 3 * col]);
+    sym_pack(M, [&](const int i, const double v) { out[i * Q] = v; });
     o = 6;
   }
   if (use_d) {
     const double qw = w1.w[q % q1d] * w1.w[(q / q1d) % q1d] * w1.w[q / (q1d * q1d)];
-    out[o * Q] = rt_coeff1(c_div, attr) * qw * qw / w;
+    out[o * Q] = coeff_unpack1(c_div, attr) * qw * qw / w;
   }
 }
 
@@ -578,15 +481,15 @@ __global__ void rt_hex_diag_kernel(const RTDiagArgs a) {
       if (a.use_v) {
         double adj[9], Jl[9], Cm[9], y0, y1, y2;
         for (int c = 0; c < 9; c++) adj[c] = g[(2 + c) * Q];
-        rt_adjJt33(adj, Jl);
-        rt_coeff3(a.c_mass, attr, Cm);
-        rt_AtBCx33(Jl, Cm, Jl, 1.0, 0.0, 0.0, w, d0, y1, y2);
-        rt_AtBCx33(Jl, Cm, Jl, 0.0, 1.0, 0.0, w, y0, d1, y2);
-        rt_AtBCx33(Jl, Cm, Jl, 0.0, 0.0, 1.0, w, y0, y1, d2);
+        adjJt33(adj, Jl);
+        coeff_unpack3(a.c_mass, attr, Cm);
+        mult_AtBCx33(Jl, Cm, Jl, 1.0, 0.0, 0.0, w, d0, y1, y2);
+        mult_AtBCx33(Jl, Cm, Jl, 0.0, 1.0, 0.0, w, y0, d1, y2);
+        mult_AtBCx33(Jl, Cm, Jl, 0.0, 0.0, 1.0, w, y0, y1, d2);
       }
       if (a.use_d) {
         const double qw = a.w1[q % Q1] * a.w1[(q / Q1) % Q1] * a.w1[q / (Q1 * Q1)];
-        dd = rt_coeff1(a.c_div, attr) * qw * qw / w;
+        dd = coeff_unpack1(a.c_div, attr) * qw * qw / w;
       }
     }
     Dm[q] = d0, Dm[Q + q] = d1, Dm[2 * Q + q] = d2, Dm[3 * Q + q] = dd;
@@ -646,7 +549,7 @@ __global__ void rt_hex_diag_kernel(const RTDiagArgs a) {
 
 void launch_rt_hex_diag(const SubOp &so, double *diag, hipStream_t s) {
   PA_REQUIRE(so.d_ye && so.d_tptr && so.d_perm, "H(div) blocks use the gather form of E^T");
-  PA_REQUIRE(rt_hex_supported(so.p, so.q1d), "no H(div) hex kernel for this order and quadrature rule");
+  PA_REQUIRE(hex_pq_supported(so.p, so.q1d), "no H(div) hex kernel for this order and quadrature rule");
   RTDiagArgs a{};
   a.ne = so.ne, a.p = so.p, a.q1 = so.q1d;
   a.sidx = so.d_sidx, a.perm = so.d_perm, a.ye = so.d_ye;
