@@ -313,6 +313,17 @@ int pa_op_add_sub_dense(pa_op *op, pa_geom *geom, const pa_restriction_desc *res
 int pa_op_add_sub_dense_mixed(pa_op *op, pa_geom *geom, const pa_restriction_desc *trial_restr,
                               const pa_dense_basis_desc *trial_basis, const pa_restriction_desc *test_restr,
                               const pa_dense_basis_desc *test_basis, int32_t qfunction, const void *ctx, size_t ctx_size);
+/* The same `Flux` operator on tensor-product hexahedra, sum-factorised (pa_mixed_hex.hip): one H(curl) and one H(div) space of
+ * the SAME order on the hexahedra and rule of `geom` (from pa_geom_create), tensor descriptors as for pa_op_add_sub.
+ * PA_QF_HCURLHDIV_33 (f_apply_hcurlhdiv_33, fem/qfunctions/33/hcurlhdiv_33_qf.h:10-31: H(curl) trial, H(div) test) or
+ * PA_QF_HDIVHCURL_33 (f_apply_hdivhcurl_33, :33-54), picked by the map types as fem/integ/vecfemass.cpp:88-101 does; both
+ * evaluation modes Interp; D matrix-free from the geometry data, any 3 x 3 coefficient.  The (order, points per direction) pairs
+ * are those of the other hex kernels.  op: height = test lsize, width = trial lsize.  pa_op_mult_transpose /
+ * pa_op_apply_add_transpose apply the transposed form (fem/libceed/operator.cpp:199-240).  As with pa_op_add_sub_dense_mixed: no
+ * essential-dof, diagonal, complex, fused-step, streaming or split form; pa_op_full_assemble gives the rectangular matrix. */
+int pa_op_add_sub_mixed(pa_op *op, pa_geom *geom, const pa_restriction_desc *trial_restr, const pa_basis_desc *trial_basis,
+                        const pa_restriction_desc *test_restr, const pa_basis_desc *test_basis, int32_t qfunction, const void *ctx,
+                        size_t ctx_size);
 /* GradientIntegrator (fem/integ/grad.cpp:16-72; f_apply_hcurlh1d_22 | _33 | _21 | _31 | _32 by the geometry data): (C grad u, v)
  * with u in a scalar H1 space (trial, Grad: `trial_basis->deriv`) and v in a vector H1 space with space_dim components (test,
  * Interp).  `test_restr` / `test_basis` describe ONE component of the test space -- the scalar value table, offsets = L-vector
@@ -339,6 +350,15 @@ typedef struct pa_error_op pa_error_op;
 int pa_error_op_create(pa_geom *geom, const pa_restriction_desc *restr1, const pa_dense_basis_desc *basis1,
                        const pa_restriction_desc *restr2, const pa_dense_basis_desc *basis2, int32_t qfunction,
                        const void *ctx, size_t ctx_size, pa_error_op **out);
+/* The same on tensor-product hexahedra, sum-factorised (pa_mixed_hex.hip): PA_QF_HCURLHDIV_ERROR_33 (f_apply_hcurlhdiv_error_33,
+ * fem/qfunctions/33/hcurlhdiv_error_33_qf.h:10-43: first input in H(curl), second in H(div)) or PA_QF_HDIVHCURL_ERROR_33
+ * (f_apply_hdivhcurl_error_33, :45-78) for two spaces of the same order on the hexahedra of `geom` (from pa_geom_create), as
+ * GradFluxErrorEstimator / CurlFluxErrorEstimator use them (linalg/errorestimator.cpp:318-349, :448-489).  One value per
+ * element, in the CALLER's element order (the order of the mesh descriptor `geom` was built from); one writer per element, the
+ * points summed in a fixed order.  The functions below serve both kinds of error operator. */
+int pa_error_op_create_tensor(pa_geom *geom, const pa_restriction_desc *restr1, const pa_basis_desc *basis1,
+                              const pa_restriction_desc *restr2, const pa_basis_desc *basis2, int32_t qfunction, const void *ctx,
+                              size_t ctx_size, pa_error_op **out);
 int pa_error_op_apply_add(pa_error_op *e, const double *u1, const double *u2, double *estimates, void *stream);
 int pa_error_op_num_elem(const pa_error_op *e);
 void pa_error_op_destroy(pa_error_op *e);

@@ -202,6 +202,24 @@ class ElementErrorIntegrator:
             pass
 
 
+class HexElementErrorIntegrator(ElementErrorIntegrator):
+    """The same on tensor-product hexahedra, sum-factorised (pa_error_op_create_tensor, pa_mixed_hex.hip): `first` / `second` an
+    NDHexSpace and an RTHexSpace of the same order on the mesh of `geom` (a GeomFactorData), in the order the QFunction names
+    them.  The estimates are in the mesh's element order."""
+
+    def __init__(self, geom, first, second, qf, ctx_pair):
+        r1, k1 = _restriction_desc(first)
+        b1, k2 = _basis_desc(first, geom.q1d)
+        r2, k3 = _restriction_desc(second)
+        b2, k4 = _basis_desc(second, geom.q1d)
+        ctx = np.ascontiguousarray(ctx_pair)
+        self.handle = C.c_void_p()
+        self._keep = (geom, first, second)
+        _lib.check(_lib.load().pa_error_op_create_tensor(geom.handle, C.byref(r1), C.byref(b1), C.byref(r2), C.byref(b2),
+                                                         C.c_int32(qf), _ptr(ctx), C.c_size_t(ctx.nbytes), C.byref(self.handle)))
+        self.ne = int(_lib.load().pa_error_op_num_elem(self.handle))
+
+
 class DenseBlock:
     """What Palace hands to libCEED for one (geometry, space) pair on the non-tensor path: the native
     restriction (fem/libceed/restriction.cpp:207-385: offsets + bool orients, or + int8 tridiagonal
@@ -314,6 +332,18 @@ class Operator:
         _lib.check(_lib.load().pa_op_add_sub(self.handle, geom.handle, C.byref(r), C.byref(b),
                                              C.c_int32(qf), _ptr(ctx), C.c_size_t(ctx.nbytes),
                                              C.c_uint32(ops), C.c_uint32(ops if test_ops is None else test_ops)))
+        return self
+
+    def add_mixed_integrator(self, geom: GeomFactorData, trial_space, test_space, qf, ctx_blob):
+        """BilinearForm(trial_fespace, test_fespace) + VectorFEMassIntegrator between an NDHexSpace and an RTHexSpace of the same
+        order (pa_op_add_sub_mixed, sum-factorised): qf = QF_HCURLHDIV_33 (H(curl) trial) or QF_HDIVHCURL_33 (H(div) trial)."""
+        r1, k1 = _restriction_desc(trial_space)
+        b1, k2 = _basis_desc(trial_space, geom.q1d)
+        r2, k3 = _restriction_desc(test_space)
+        b2, k4 = _basis_desc(test_space, geom.q1d)
+        ctx = np.ascontiguousarray(ctx_blob)
+        _lib.check(_lib.load().pa_op_add_sub_mixed(self.handle, geom.handle, C.byref(r1), C.byref(b1), C.byref(r2), C.byref(b2),
+                                                   C.c_int32(qf), _ptr(ctx), C.c_size_t(ctx.nbytes)))
         return self
 
     def add_dense_integrator(self, geom: DenseGeomFactorData, block: DenseBlock, qf, ctx_blob, ops):
@@ -575,6 +605,13 @@ def rtmass_operator(geom, rt: RTHexSpace, ctx, dense=None):
     """VectorFEMassIntegrator on an H(div) space (fem/integ/vecfemass.cpp): f_apply_hdiv_33, Interp/Interp; sum-factorised
     (pa_rt_hex.hip).  dense = (values [3, Q, P], divergence [Q, P]): checked against the 1-D tables."""
     return Operator(rt.ndofs, rt.ndofs).add_integrator(geom, rt, QF_HDIV_33, ctx, EVAL_INTERP, dense).finalize()
+
+
+def mixedmass_operator(geom, trial, test, ctx):
+    """FluxProjector's `Flux` operator (linalg/errorestimator.cpp:164-176) on tensor-product hexahedra: (v, C u) between an
+    NDHexSpace and an RTHexSpace, either way round; the QFunction follows from the trial space (fem/integ/vecfemass.cpp:88-101)."""
+    qf = QF_HCURLHDIV_33 if isinstance(trial, NDHexSpace) else QF_HDIVHCURL_33
+    return Operator(test.ndofs, trial.ndofs).add_mixed_integrator(geom, trial, test, qf, ctx).finalize()
 
 
 def divdiv_operator(geom, rt: RTHexSpace, ctx1, dense=None):

@@ -162,12 +162,18 @@ FluxErrorEstimatorBase::FluxErrorEstimatorBase(const FiniteElementSpace &fespace
                                                int max_it, int print)
     : ctx_(&fespace.GetContext()), fespace_(fespace), smooth_fespace_(smooth_fespace),
       projector_(flux_coeff, smooth_fespace, fespace, tol, max_it, print), G_(smooth_fespace.GetTrueVSize()) {
-  PA_REQUIRE(fespace.IsDense() && smooth_fespace.IsDense() && &fespace.GetMesh() == &smooth_fespace.GetMesh(),
-             "the estimators take two dense-table spaces on one mesh");
+  PA_REQUIRE(fespace.IsDense() == smooth_fespace.IsDense() && &fespace.GetMesh() == &smooth_fespace.GetMesh(),
+             "the estimators take two dense-table spaces or two tensor spaces on one mesh");
   const auto c1 = first.Coefficient(), c2 = second.Coefficient();
   PA_REQUIRE(first.dim == second.dim, "the two coefficients of an error integrator have one dimension");
   const auto ctx = ceed::PopulateCoefficientContext(first.dim, &c1, second.dim, &c2);  // errorestimator.cpp:326-329, :459-460
   const auto r1 = fespace.GetCeedElemRestriction(), r2 = smooth_fespace.GetCeedElemRestriction();
+  if (!fespace.IsDense()) {  // tensor-product hexahedra: the sum-factorised error integrator (pa_mixed_hex.hip)
+    const auto b1 = fespace.GetCeedBasis(), b2 = smooth_fespace.GetCeedBasis();
+    check(pa_error_op_create_tensor(fespace.GetMesh().GetCeedGeomFactorData(), &r1, &b1, &r2, &b2, error_qf, ctx.data(),
+                                    ctx.size() * sizeof(double), &integ_op_));
+    return;
+  }
   const auto b1 = fespace.GetCeedDenseBasis(), b2 = smooth_fespace.GetCeedDenseBasis();
   check(pa_error_op_create(fespace.GetMesh().GetCeedGeomFactorData(), &r1, &b1, &r2, &b2, error_qf, ctx.data(),
                            ctx.size() * sizeof(double), &integ_op_));

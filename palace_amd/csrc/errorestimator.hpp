@@ -2,8 +2,10 @@
 // (FluxProjector, :111-187), element-wise error between the discontinuous and the smooth flux (ComputeErrorEstimates,
 // :189-268), and the two estimators built on them (GradFluxErrorEstimator :271-360, CurlFluxErrorEstimator :390-510,
 // TimeDependentFluxErrorEstimator :512-541), plus the running indicator they feed (fem/errorindicator.{hpp,cpp}).
-// Spaces are dense-table spaces on one dense Mesh (fem.hpp); the operators are pa_op_add_sub_dense[_mixed] and
-// pa_error_op_* (pa_mixed.hip).  Real vectors; a complex field is estimated part by part into the same estimates, as
+// Spaces are two dense-table spaces on one dense Mesh (fem.hpp; the operators are pa_op_add_sub_dense[_mixed] and
+// pa_error_op_create, pa_mixed.hip) or, for the 3-D vector estimators on hexahedra, two tensor spaces of one order on one tensor
+// Mesh (pa_op_add_sub, pa_op_add_sub_mixed and pa_error_op_create_tensor: sum-factorised, pa_rt_hex.hip / pa_nd_hex.hip /
+// pa_mixed_hex.hip).  Real vectors; a complex field is estimated part by part into the same estimates, as
 // ComputeErrorEstimates does for a ComplexVector (:255-261).
 #pragma once
 

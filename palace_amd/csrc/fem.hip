@@ -628,9 +628,17 @@ void BilinearFormIntegrator::AssembleCeedOperator(pa_op *op, const FiniteElement
     }
     return;
   }
-  PA_REQUIRE(&trial == &test, "square forms only: test and trial space must be the same object");
   const auto r = trial.GetCeedElemRestriction();
   const auto b = trial.GetCeedBasis();
+  if (&trial != &test) {  // two tensor spaces on one mesh: the sum-factorised mixed mass between H(curl) and H(div) (pa_op_add_sub_mixed)
+    PA_REQUIRE(&trial.GetMesh() == &test.GetMesh() && (qf == PA_QF_HCURLHDIV_33 || qf == PA_QF_HDIVHCURL_33) &&
+                   trial_ops == PA_EVAL_INTERP && test_ops == PA_EVAL_INTERP,
+               "square forms only: test and trial space must be the same object");
+    const auto r2 = test.GetCeedElemRestriction();
+    const auto b2 = test.GetCeedBasis();
+    check(pa_op_add_sub_mixed(op, trial.GetMesh().GetCeedGeomFactorData(), &r, &b, &r2, &b2, qf, ctx.data(), ctx.size() * sizeof(double)));
+    return;
+  }
   check(pa_op_add_sub(op, trial.GetMesh().GetCeedGeomFactorData(), &r, &b, qf, ctx.data(), ctx.size() * sizeof(double),
                       trial_ops, test_ops));
 }

@@ -168,6 +168,118 @@ static void check_dense_tables(const pa_basis_desc &b, int P, int Q) {
                 std::to_string(worst) + ")");
 }
 
+// The part of a tensor-product block that depends on the space alone: the 1-D tables (checked against the dense ones and for
+// mirror symmetry), the signed tensor-order index in the geometry data's element order, its sorted form and the transpose
+// map of the gather form of E^T.  always_gather: build that map whatever PALACE_AMD_SCATTER says (the two-space forms).
+static SubOp *new_hex_block(pa_geom *geom, const pa_restriction_desc &r, const pa_basis_desc &b, const int P, const bool always_gather) {
+  auto *so = new SubOp;
+  so->geom = geom;
+  geom->refcount++;
+  try {
+    so->fe_type = b.fe_type, so->p = b.order, so->q1d = b.q1d, so->P = P, so->Q = geom->Q;
+    so->ne = r.num_elem, so->lsize = r.lsize;
+    const int nc = b.order + 1;
+    so->Bc.assign(b.Bc, b.Bc + b.q1d * nc);
+    so->Gc.assign(b.Gc, b.Gc + b.q1d * nc);
+    if (b.Bo) so->Bo.assign(b.Bo, b.Bo + b.q1d * b.order);
+    check_dense_tables(b, P, geom->Q);
+    // the kernels rely on the mirror symmetry of Gauss-Legendre / Gauss-Lobatto tables
+    {
+      double worst = 0.0;
+      const int q1 = b.q1d;
+      for (int q = 0; q < q1; q++) {
+        for (int i = 0; i < nc; i++) {
+          worst = std::fmax(worst, std::fabs(so->Bc[q * nc + i] - so->Bc[(q1 - 1 - q) * nc + (nc - 1 - i)]));
+          worst = std::fmax(worst, std::fabs(so->Gc[q * nc + i] + so->Gc[(q1 - 1 - q) * nc + (nc - 1 - i)]));
+        }
+        if (b.Bo)
+          for (int i = 0; i < b.order; i++)
+            worst = std::fmax(worst, std::fabs(so->Bo[q * b.order + i] -
+                                               so->Bo[(q1 - 1 - q) * b.order + (b.order - 1 - i)]));
+      }
+      if (!(worst < 1e-12)) throw Error("1-D basis tables are not mirror-symmetric (non Gauss-Legendre/Lobatto nodes?)");
+      std::vector<double> tab;
+      tab.insert(tab.end(), so->Bo.begin(), so->Bo.end());
+      if (so->Bo.empty()) tab.assign((size_t)b.q1d * b.order, 0.0);
+      tab.insert(tab.end(), so->Bc.begin(), so->Bc.end());
+      tab.insert(tab.end(), so->Gc.begin(), so->Gc.end());
+      so->d_tab = dev_upload(tab.data(), tab.size());
+    }
+
+    // signed tensor-order index array (restriction.cpp:290-296 semantics folded with dof_map)
+    std::vector<int32_t> lidx((size_t)r.num_elem * P);
+    std::vector<char> seen(P);
+    for (int l = 0; l < P; l++) {
+      int n = b.dof_map ? b.dof_map[l] : l;
+      if (n < 0) n = -1 - n;
+      PA_REQUIRE(n >= 0 && n < P && !seen[n], "dof_map is not a signed permutation");
+      seen[n] = 1;
+    }
+    for (int e = 0; e < r.num_elem; e++)  // internal element order (the geometry data's, pa_geom.hip)
+      for (int l = 0; l < P; l++) {
+        int n = b.dof_map ? b.dof_map[l] : l;
+        bool neg = false;
+        if (n < 0) n = -1 - n, neg = true;
+        const size_t k = (size_t)(geom->eorder.empty() ? e : geom->eorder[e]) * P + n;
+        const int32_t off = r.offsets[k];
+        PA_REQUIRE(off >= 0 && off < r.lsize, "restriction offset out of range");
+        if (r.orients && r.orients[k]) neg = !neg;
+        lidx[(size_t)e * P + l] = neg ? -1 - off : off;
+      }
+    so->d_lidx = dev_upload(lidx.data(), lidx.size());
+    PA_REQUIRE(r.lsize < kEssBit, "too many local dofs for the index encoding");
+    PA_REQUIRE(P < 65536, "element too large for the 16-bit slot permutation");
+    // Sorted order of the element's entries (by global dof, stable): what E gathers and E^T stores
+    // in, so that one load/store instruction touches neighbouring dofs.
+    const size_t nnz = lidx.size();
+    std::vector<int32_t> sidx(nnz);
+    std::vector<uint16_t> perm(nnz);
+    {
+      std::vector<int> ord(P);
+      for (int e = 0; e < r.num_elem; e++) {
+        const int32_t *le = &lidx[(size_t)e * P];
+        for (int l = 0; l < P; l++) ord[l] = l;
+        std::stable_sort(ord.begin(), ord.end(), [&](int a, int c2) {
+          const int da = le[a] >= 0 ? le[a] : -1 - le[a], dc = le[c2] >= 0 ? le[c2] : -1 - le[c2];
+          return da < dc;
+        });
+        for (int m = 0; m < P; m++) {
+          sidx[(size_t)e * P + m] = le[ord[m]];
+          perm[(size_t)e * P + m] = (uint16_t)ord[m];
+        }
+      }
+    }
+    so->d_sidx = dev_upload(sidx.data(), nnz);
+    so->d_perm = dev_upload(perm.data(), nnz);
+    so->h_perm = perm;
+    // transpose map for the gather form of E^T (counting sort by dof; element order preserved, so the
+    // summation order of every dof is fixed) unless PALACE_AMD_SCATTER=atomic asks for the atomic form
+    const char *mode = getenv("PALACE_AMD_SCATTER");
+    if (always_gather || !(mode && std::string(mode) == "atomic") || b.fe_type != PA_FE_HCURL) {
+      std::vector<int32_t> tptr((size_t)r.lsize + 1, 0), tent(nnz);
+      for (size_t k = 0; k < nnz; k++) {
+        const int32_t s = sidx[k];
+        tptr[(size_t)(s >= 0 ? s : -1 - s) + 1]++;
+      }
+      for (int d = 0; d < r.lsize; d++) tptr[d + 1] += tptr[d];
+      std::vector<int32_t> fill(tptr.begin(), tptr.end() - 1);
+      for (size_t k = 0; k < nnz; k++) {  // E-vector position of a sorted entry is its own index
+        const int32_t s = sidx[k];
+        const int d = s >= 0 ? s : -1 - s;
+        tent[fill[d]++] = s >= 0 ? (int32_t)k : -1 - (int32_t)k;
+      }
+      so->d_tptr = dev_upload(tptr.data(), tptr.size());
+      so->d_tent = dev_upload(tent.data(), tent.size());
+      so->d_ye = dev_alloc<double>((size_t)((r.num_elem + 3) & ~3) * P);  // padded to whole batches of the streaming kernel
+    }
+    so->h_sidx = std::move(sidx);
+  } catch (...) {
+    free_sub(so);
+    throw;
+  }
+  return so;
+}
+
 static SubOp *make_sub(pa_geom *geom, const pa_restriction_desc &r, const pa_basis_desc &b, int qf,
                        const void *ctx, size_t ctx_size, uint32_t trial_ops, uint32_t test_ops,
                        QData *shared_qd = nullptr) {
@@ -221,111 +333,9 @@ static SubOp *make_sub(pa_geom *geom, const pa_restriction_desc &r, const pa_bas
                      (qf == PA_QF_HCURL_33 && b.fe_type == PA_FE_HCURL);
   PA_REQUIRE(rt || nd_qf == (b.fe_type == PA_FE_HCURL), "QFunction does not match the element type");
 
-  auto *so = new SubOp;
-  so->geom = geom;
-  geom->refcount++;
-  so->fe_type = b.fe_type, so->p = b.order, so->q1d = b.q1d, so->P = P, so->Q = geom->Q;
-  so->ne = r.num_elem, so->lsize = r.lsize, so->qf = qf;
+  SubOp *so = new_hex_block(geom, r, b, P, false);
+  so->qf = qf;
   so->trial_ops = trial_ops, so->test_ops = test_ops;
-  const int nc = b.order + 1;
-  so->Bc.assign(b.Bc, b.Bc + b.q1d * nc);
-  so->Gc.assign(b.Gc, b.Gc + b.q1d * nc);
-  if (b.Bo) so->Bo.assign(b.Bo, b.Bo + b.q1d * b.order);
-  check_dense_tables(b, P, geom->Q);
-  // the kernels rely on the mirror symmetry of Gauss-Legendre / Gauss-Lobatto tables
-  {
-    double worst = 0.0;
-    const int q1 = b.q1d;
-    for (int q = 0; q < q1; q++) {
-      for (int i = 0; i < nc; i++) {
-        worst = std::fmax(worst, std::fabs(so->Bc[q * nc + i] - so->Bc[(q1 - 1 - q) * nc + (nc - 1 - i)]));
-        worst = std::fmax(worst, std::fabs(so->Gc[q * nc + i] + so->Gc[(q1 - 1 - q) * nc + (nc - 1 - i)]));
-      }
-      if (b.Bo)
-        for (int i = 0; i < b.order; i++)
-          worst = std::fmax(worst, std::fabs(so->Bo[q * b.order + i] -
-                                             so->Bo[(q1 - 1 - q) * b.order + (b.order - 1 - i)]));
-    }
-    if (!(worst < 1e-12)) {
-      delete so;
-      geom->refcount--;
-      throw Error("1-D basis tables are not mirror-symmetric (non Gauss-Legendre/Lobatto nodes?)");
-    }
-    std::vector<double> tab;
-    tab.insert(tab.end(), so->Bo.begin(), so->Bo.end());
-    if (so->Bo.empty()) tab.assign((size_t)b.q1d * b.order, 0.0);
-    tab.insert(tab.end(), so->Bc.begin(), so->Bc.end());
-    tab.insert(tab.end(), so->Gc.begin(), so->Gc.end());
-    so->d_tab = dev_upload(tab.data(), tab.size());
-  }
-
-  // signed tensor-order index array (restriction.cpp:290-296 semantics folded with dof_map)
-  std::vector<int32_t> lidx((size_t)r.num_elem * P);
-  std::vector<char> seen(P);
-  for (int l = 0; l < P; l++) {
-    int n = b.dof_map ? b.dof_map[l] : l;
-    if (n < 0) n = -1 - n;
-    PA_REQUIRE(n >= 0 && n < P && !seen[n], "dof_map is not a signed permutation");
-    seen[n] = 1;
-  }
-  for (int e = 0; e < r.num_elem; e++)  // internal element order (the geometry data's, pa_geom.hip)
-    for (int l = 0; l < P; l++) {
-      int n = b.dof_map ? b.dof_map[l] : l;
-      bool neg = false;
-      if (n < 0) n = -1 - n, neg = true;
-      const size_t k = (size_t)(geom->eorder.empty() ? e : geom->eorder[e]) * P + n;
-      const int32_t off = r.offsets[k];
-      PA_REQUIRE(off >= 0 && off < r.lsize, "restriction offset out of range");
-      if (r.orients && r.orients[k]) neg = !neg;
-      lidx[(size_t)e * P + l] = neg ? -1 - off : off;
-    }
-  so->d_lidx = dev_upload(lidx.data(), lidx.size());
-  PA_REQUIRE(r.lsize < kEssBit, "too many local dofs for the index encoding");
-  PA_REQUIRE(P < 65536, "element too large for the 16-bit slot permutation");
-  // Sorted order of the element's entries (by global dof, stable): what E gathers and E^T stores
-  // in, so that one load/store instruction touches neighbouring dofs.
-  const size_t nnz = lidx.size();
-  std::vector<int32_t> sidx(nnz);
-  std::vector<uint16_t> perm(nnz);
-  {
-    std::vector<int> ord(P);
-    for (int e = 0; e < r.num_elem; e++) {
-      const int32_t *le = &lidx[(size_t)e * P];
-      for (int l = 0; l < P; l++) ord[l] = l;
-      std::stable_sort(ord.begin(), ord.end(), [&](int a, int c2) {
-        const int da = le[a] >= 0 ? le[a] : -1 - le[a], dc = le[c2] >= 0 ? le[c2] : -1 - le[c2];
-        return da < dc;
-      });
-      for (int m = 0; m < P; m++) {
-        sidx[(size_t)e * P + m] = le[ord[m]];
-        perm[(size_t)e * P + m] = (uint16_t)ord[m];
-      }
-    }
-  }
-  so->d_sidx = dev_upload(sidx.data(), nnz);
-  so->d_perm = dev_upload(perm.data(), nnz);
-  so->h_perm = perm;
-  // transpose map for the gather form of E^T (counting sort by dof; element order preserved, so the
-  // summation order of every dof is fixed) unless PALACE_AMD_SCATTER=atomic asks for the atomic form
-  const char *mode = getenv("PALACE_AMD_SCATTER");
-  if (!(mode && std::string(mode) == "atomic") || b.fe_type != PA_FE_HCURL) {
-    std::vector<int32_t> tptr((size_t)r.lsize + 1, 0), tent(nnz);
-    for (size_t k = 0; k < nnz; k++) {
-      const int32_t s = sidx[k];
-      tptr[(size_t)(s >= 0 ? s : -1 - s) + 1]++;
-    }
-    for (int d = 0; d < r.lsize; d++) tptr[d + 1] += tptr[d];
-    std::vector<int32_t> fill(tptr.begin(), tptr.end() - 1);
-    for (size_t k = 0; k < nnz; k++) {  // E-vector position of a sorted entry is its own index
-      const int32_t s = sidx[k];
-      const int d = s >= 0 ? s : -1 - s;
-      tent[fill[d]++] = s >= 0 ? (int32_t)k : -1 - (int32_t)k;
-    }
-    so->d_tptr = dev_upload(tptr.data(), tptr.size());
-    so->d_tent = dev_upload(tent.data(), tent.size());
-    so->d_ye = dev_alloc<double>((size_t)((r.num_elem + 3) & ~3) * P);  // padded to whole batches of the streaming kernel
-  }
-  so->h_sidx = std::move(sidx);
 
   so->ctx_blob.assign((const uint8_t *)ctx, (const uint8_t *)ctx + ctx_size);
   PA_REQUIRE(ctx && ctx_size >= 24 && ctx_size % 8 == 0, "coefficient context missing or malformed");
@@ -406,7 +416,7 @@ static SubOp *make_sub(pa_geom *geom, const pa_restriction_desc &r, const pa_bas
   return so;
 }
 
-static void free_sub(SubOp *so) {
+void free_sub(SubOp *so) {
   if (!so) return;
   hipFree(so->d_lidx);
   hipFree(so->d_sidx), hipFree(so->d_sidx_bc), hipFree(so->d_perm), hipFree(so->d_perm_x), hipFree(so->d_shared), hipFree(so->d_shared_bc);
@@ -421,6 +431,64 @@ static void free_sub(SubOp *so) {
   hipFree(so->c1.d_attr_mat), hipFree(so->c1.d_mat), hipFree(so->c1.d_mat_t);
   pa_geom_destroy(static_cast<pa_geom *>(so->geom));
   delete so;
+}
+
+// One Nedelec and one Raviart-Thomas tensor-product space of the same order on the same hexahedra: the mixed mass (kind 0 | 1) or
+// the element error integrator (2 | 3) of pa_mixed_hex.hip.  The argument checks are those of make_mixed_sub (pa_mixed.hip).
+MixedSub *make_mixed_hex_sub(pa_geom *geom, const pa_restriction_desc &r1, const pa_basis_desc &b1, const pa_restriction_desc &r2,
+                             const pa_basis_desc &b2, int qf, const void *ctx, size_t ctx_size) {
+  require_device();
+  PA_REQUIRE(geom && geom->d_geom && geom->eb == 0 && geom->dim == 3 && geom->sdim == 3,
+             "tensor-product mixed-space operators need geometry data from pa_geom_create");
+  PA_REQUIRE(r1.num_elem == geom->ne && r2.num_elem == geom->ne, "restrictions do not match the mesh");
+  int kind = -1;
+  switch (qf) {
+    case PA_QF_HCURLHDIV_33: kind = 0; break;
+    case PA_QF_HDIVHCURL_33: kind = 1; break;
+    case PA_QF_HCURLHDIV_ERROR_33: kind = 2; break;
+    case PA_QF_HDIVHCURL_ERROR_33: kind = 3; break;
+    default: throw Error("not a mixed-space QFunction of tensor-product hexahedra");
+  }
+  const bool err = kind >= 2, nd_first = kind == 0 || kind == 2;
+  PA_REQUIRE(b1.fe_type == (nd_first ? PA_FE_HCURL : PA_FE_HDIV) && b2.fe_type == (nd_first ? PA_FE_HDIV : PA_FE_HCURL),
+             "element types do not match the QFunction (vecfemass.cpp:88-101)");
+  PA_REQUIRE(!r1.curl_orients && !r2.curl_orients, "the curl-oriented restriction needs the dense-table path (pa_op_add_sub_dense_mixed)");
+  PA_REQUIRE(b1.order == b2.order, "the two spaces of a tensor-product mixed-space operator have the same order");
+  PA_REQUIRE(b1.q1d == geom->q1d && b2.q1d == geom->q1d, "basis and geometry data use different quadrature rules");
+  if (!hex_pq_supported(b1.order, b1.q1d)) throw hex_pq_error("H(curl) - H(div)", b1.order, b1.q1d);
+  PA_REQUIRE(b1.Bc && b1.Gc && b1.Bo && b2.Bc && b2.Gc && b2.Bo, "1-D basis tables missing");
+  PA_REQUIRE(r1.elem_size == expected_P(b1.fe_type, b1.order) && r2.elem_size == expected_P(b2.fe_type, b2.order) && r1.offsets &&
+                 r2.offsets && r1.lsize > 0 && r2.lsize > 0,
+             "restriction does not match the basis");
+  PA_REQUIRE(ctx && ctx_size >= 16 && ctx_size % 8 == 0, "bad coefficient context");
+  auto *ms = new MixedSub;
+  try {
+    ms->geom = geom;
+    geom->refcount++;
+    ms->ne = geom->ne, ms->Q = geom->Q, ms->qf = qf, ms->kind = kind, ms->error = err;
+    ms->hex1 = new_hex_block(geom, r1, b1, r1.elem_size, true);
+    ms->hex2 = new_hex_block(geom, r2, b2, r2.elem_size, true);
+    for (size_t i = 0; i < ms->hex1->Bo.size(); i++)
+      PA_REQUIRE(ms->hex1->Bo[i] == ms->hex2->Bo[i], "the two spaces use different 1-D tables");
+    for (size_t i = 0; i < ms->hex1->Bc.size(); i++)
+      PA_REQUIRE(ms->hex1->Bc[i] == ms->hex2->Bc[i], "the two spaces use different 1-D tables");
+    // what full assembly reads of a two-space operator: the plain dof lists of the two sides (internal element order)
+    auto plain = [](const SubOp &so, MixedSide &sd) {
+      sd.fe_type = so.fe_type, sd.P = so.P, sd.lsize = so.lsize;
+      sd.h_off.resize(so.h_sidx.size());
+      for (size_t k = 0; k < sd.h_off.size(); k++) sd.h_off[k] = so.h_sidx[k] >= 0 ? so.h_sidx[k] : -1 - so.h_sidx[k];
+    };
+    plain(*ms->hex1, ms->s1), plain(*ms->hex2, ms->s2);
+    parse_coeff(ctx, ctx_size, 3, ms->c0, 0);
+    if (err) {
+      parse_coeff(ctx, ctx_size, 3, ms->c1, ms->c0.slots);  // PopulateCoefficientContext(dim, first, dim, second)
+      if (!geom->eorder.empty()) ms->d_eorder = dev_upload(geom->eorder.data(), geom->eorder.size());
+    }
+  } catch (...) {
+    free_mixed_sub(ms);
+    throw;
+  }
+  return ms;
 }
 
 // y (+)= A x.  overwrite: the first sub-operator writes y instead of accumulating (Mult without a
@@ -715,6 +783,20 @@ int pa_op_add_sub_dense_mixed(pa_op *op, pa_geom *geom, const pa_restriction_des
   });
 }
 
+int pa_op_add_sub_mixed(pa_op *op, pa_geom *geom, const pa_restriction_desc *trial_restr, const pa_basis_desc *trial_basis,
+                        const pa_restriction_desc *test_restr, const pa_basis_desc *test_basis, int32_t qfunction, const void *ctx,
+                        size_t ctx_size) {
+  return guarded([&] {
+    require_device();
+    PA_REQUIRE(op && geom && trial_restr && trial_basis && test_restr && test_basis, "null argument");
+    PA_REQUIRE(!op->finalized, "operator already finalized");
+    PA_REQUIRE(qfunction == PA_QF_HCURLHDIV_33 || qfunction == PA_QF_HDIVHCURL_33, "not a mixed-space QFunction");
+    PA_REQUIRE(test_restr->lsize == op->height && trial_restr->lsize == op->width,
+               "dimensions mismatch for sub-operator");  // operator.cpp:69-71
+    op->msubs.push_back(make_mixed_hex_sub(geom, *trial_restr, *trial_basis, *test_restr, *test_basis, qfunction, ctx, ctx_size));
+  });
+}
+
 int pa_op_add_sub_dense_gradient(pa_op *op, pa_geom *geom, const pa_restriction_desc *trial_restr,
                                  const pa_dense_basis_desc *trial_basis, const pa_restriction_desc *test_restr,
                                  const pa_dense_basis_desc *test_basis, int32_t comp_stride, int32_t qfunction, const void *ctx,
@@ -795,6 +877,24 @@ int pa_error_op_create(pa_geom *geom, const pa_restriction_desc *restr1, const p
     auto *e = new pa_error_op;
     try {
       e->ms = make_mixed_sub(geom, *restr1, *basis1, *restr2, *basis2, qfunction, ctx, ctx_size);
+    } catch (...) {
+      delete e;
+      throw;
+    }
+    *out = e;
+  });
+}
+
+int pa_error_op_create_tensor(pa_geom *geom, const pa_restriction_desc *restr1, const pa_basis_desc *basis1,
+                              const pa_restriction_desc *restr2, const pa_basis_desc *basis2, int32_t qfunction, const void *ctx,
+                              size_t ctx_size, pa_error_op **out) {
+  return guarded([&] {
+    require_device();
+    PA_REQUIRE(geom && restr1 && basis1 && restr2 && basis2 && out, "null argument");
+    PA_REQUIRE(qfunction == PA_QF_HCURLHDIV_ERROR_33 || qfunction == PA_QF_HDIVHCURL_ERROR_33, "not an error QFunction");
+    auto *e = new pa_error_op;
+    try {
+      e->ms = make_mixed_hex_sub(geom, *restr1, *basis1, *restr2, *basis2, qfunction, ctx, ctx_size);
     } catch (...) {
       delete e;
       throw;
@@ -1452,7 +1552,9 @@ double pa_op_algorithmic_bytes(const pa_op *op) {
   }
   for (const DenseSub *ds : op->dsubs)  // o = 3 for the curl-oriented restriction; G = 11 (3-D) or 6 (2-D)
     bytes += (double)ds->ne * ((double)ds->Q * ds->geom->nrows * 8 + (double)ds->P * (ds->d_co ? 7 : 5));
-  return bytes + 16.0 * op->height;
+  for (const MixedSub *ms : op->msubs)  // tensor-product two-space blocks (pa_mixed_hex.hip): the 11 geometry rows, 6 B per entry of both sides
+    if (ms->hex1) bytes += (double)ms->ne * ((double)ms->Q * 11 * 8 + (double)(ms->hex1->P + ms->hex2->P) * 6);
+  return bytes + 8.0 * op->height + 8.0 * op->width;  // y and x
 }
 
 void pa_op_destroy(pa_op *op) {

@@ -44,6 +44,16 @@ __device__ __forceinline__ void mult_AtBCx33(const double A[9], const double B[9
   y2 = s * (A[6] * z0 + A[7] * z1 + A[8] * z2);
 }
 
+// y = B (A x), column-major 3x3 (utils_33_qf.h:86-101)
+__device__ __forceinline__ void mult_BAx33(const double A[9], const double B[9], const double (&x)[3], double (&y)[3]) {
+  const double z0 = A[0] * x[0] + A[3] * x[1] + A[6] * x[2];
+  const double z1 = A[1] * x[0] + A[4] * x[1] + A[7] * x[2];
+  const double z2 = A[2] * x[0] + A[5] * x[1] + A[8] * x[2];
+  y[0] = B[0] * z0 + B[3] * z1 + B[6] * z2;
+  y[1] = B[1] * z0 + B[4] * z1 + B[7] * z2;
+  y[2] = B[2] * z0 + B[5] * z1 + B[8] * z2;
+}
+
 // The same product when the coefficient is c * I (every material isotropic): y = (s c) A^T A x
 __device__ __forceinline__ void mult_AtAx33(const double A[9], const double x0, const double x1,
                                             const double x2, const double sc, double &y0, double &y1,

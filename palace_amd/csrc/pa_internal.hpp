@@ -291,6 +291,10 @@ struct MixedSub {
   CoeffHost c0, c1;
   double *d_ye = nullptr;
   mutable double *d_ye_t = nullptr;  // E-vector of the transposed apply (trial side), allocated at its first use
+  // sum-factorised form on tensor-product hexahedra (pa_mixed_hex.hip): the two spaces as index-only blocks (sorted signed
+  // gather, slot permutation, transpose map and E-vector of each), the 1-D tables shared by both
+  SubOp *hex1 = nullptr, *hex2 = nullptr;
+  int32_t *d_eorder = nullptr;  // the caller's number of internal element e (error integrator), nullptr: the same order
 };
 
 void parse_coeff(const void *blob, size_t bytes, int dim, CoeffHost &out, size_t slot_offset);
@@ -421,6 +425,12 @@ MixedSub *make_mixed_gradient_sub(pa_geom *geom, const pa_restriction_desc &r1, 
 void free_mixed_sub(MixedSub *ms);
 void launch_mixed_apply(const MixedSub &ms, const double *x, double *y, bool accumulate, hipStream_t s, bool transpose = false);
 void launch_mixed_error(const MixedSub &ms, const double *u1, const double *u2, double *out, hipStream_t s);
+// pa_capi.hip: the tensor-product form of a two-space operator / error integrator; the blocks of its two spaces
+MixedSub *make_mixed_hex_sub(pa_geom *geom, const pa_restriction_desc &r1, const pa_basis_desc &b1, const pa_restriction_desc &r2,
+                             const pa_basis_desc &b2, int qf, const void *ctx, size_t ctx_size);
+void free_sub(SubOp *so);
+// pa_mixed_hex.hip: x1 -> the E-vector of the output block (apply; transpose: hex2 -> hex1) or x1, x2 -> out (error)
+void launch_mixed_hex(const MixedSub &ms, const double *x1, const double *x2, double *out, hipStream_t s, bool transpose);
 
 }  // namespace pa
 

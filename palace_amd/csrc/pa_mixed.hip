@@ -99,16 +99,6 @@ __device__ __forceinline__ void mix_eval(const MixSideDev &sd, const int Q, cons
   }
 }
 
-// y = B (A x), column-major 3x3 (utils_33_qf.h:86-101)
-__device__ __forceinline__ void mult_BAx33(const double A[9], const double B[9], const double (&x)[3], double (&y)[3]) {
-  const double z0 = A[0] * x[0] + A[3] * x[1] + A[6] * x[2];
-  const double z1 = A[1] * x[0] + A[4] * x[1] + A[7] * x[2];
-  const double z2 = A[2] * x[0] + A[5] * x[1] + A[8] * x[2];
-  y[0] = B[0] * z0 + B[3] * z1 + B[6] * z2;
-  y[1] = B[1] * z0 + B[4] * z1 + B[7] * z2;
-  y[2] = B[2] * z0 + B[5] * z1 + B[8] * z2;
-}
-
 // A 2 x 2 column-major matrix as the leading block of a 3 x 3 one
 __device__ __forceinline__ void embed22(double m0, double m1, double m2, double m3, double corner, double M[9]) {
   M[0] = m0, M[1] = m1, M[2] = 0.0, M[3] = m2, M[4] = m3, M[5] = 0.0, M[6] = 0.0, M[7] = 0.0, M[8] = corner;
@@ -567,6 +557,8 @@ MixedSub *make_mixed_gradient_sub(pa_geom *geom, const pa_restriction_desc &r1, 
 
 void free_mixed_sub(MixedSub *ms) {
   if (!ms) return;
+  free_sub(ms->hex1), free_sub(ms->hex2);
+  hipFree(ms->d_eorder);
   free_side(ms->s1), free_side(ms->s2);
   hipFree(ms->d_ye), hipFree(ms->d_ye_t);
   hipFree(ms->c0.d_attr_mat), hipFree(ms->c0.d_mat), hipFree(ms->c0.d_mat_t);
@@ -577,6 +569,12 @@ void free_mixed_sub(MixedSub *ms) {
 
 void launch_mixed_apply(const MixedSub &ms, const double *x, double *y, bool accumulate, hipStream_t s, bool transpose) {
   PA_REQUIRE(!ms.error, "error integrators have no apply");
+  if (ms.hex1) {  // tensor-product hexahedra: pa_mixed_hex.hip writes the E-vector of the output space's block
+    launch_mixed_hex(ms, x, nullptr, nullptr, s, transpose);
+    const SubOp &ob = transpose ? *ms.hex1 : *ms.hex2;
+    launch_et_gather_raw(ob.lsize, ob.d_tptr, ob.d_tent, ob.d_ye, y, accumulate, s);
+    return;
+  }
   launch(ms, x, nullptr, nullptr, s, transpose);
   const MixedSide &out = transpose ? ms.s1 : ms.s2;
   launch_et_gather_raw(out.lsize, out.d_tptr, out.d_tent, transpose ? ms.d_ye_t : ms.d_ye, y, accumulate, s);
@@ -584,6 +582,7 @@ void launch_mixed_apply(const MixedSub &ms, const double *x, double *y, bool acc
 
 void launch_mixed_error(const MixedSub &ms, const double *u1, const double *u2, double *out, hipStream_t s) {
   PA_REQUIRE(ms.error, "not an error integrator");
+  if (ms.hex1) return launch_mixed_hex(ms, u1, u2, out, s, false);
   launch(ms, u1, u2, out, s);
 }
 
