@@ -13,6 +13,8 @@ from palace_amd.fem.fespace import H1HexSpace  # noqa: E402
 from tests import util  # noqa: E402
 
 RTOL = 1e-12
+# every (p, q1d) pair of PA_HEX_PQ_LIST (tests/test_hex_instantiations.py compares)
+PQ = [(1, 2), (2, 3), (3, 4), (1, 4), (2, 4), (4, 5), (1, 3), (1, 5), (2, 5), (3, 5)]
 
 
 def _dev(a):
@@ -45,7 +47,7 @@ def _ctxs():
     return c_mass, c_diff
 
 
-@pytest.mark.parametrize("p,q1d", [(1, 2), (2, 3), (3, 4), (1, 4), (2, 4), (4, 5)])
+@pytest.mark.parametrize("p,q1d", PQ)
 @pytest.mark.parametrize("qf", ["diffusion", "mass", "diffusionmass"])
 @pytest.mark.parametrize("dstage", ["qdata", "matrix_free"])
 def test_h1_apply_and_diagonal(cylinder_mesh, monkeypatch, p, q1d, qf, dstage):
@@ -99,9 +101,7 @@ def test_h1_prolongation(cylinder_mesh):
         xc = np.random.default_rng(3).uniform(-1, 1, hc.ndofs)
         yf = P.mult(_dev(xc), _new(hf.ndofs)).cpu().numpy()
         # oracle: dense element interpolation in tensor order
-        cpc, cpf = po.gll_points(pc + 1), po.gll_points(pf + 1)
-        I1 = np.array([[po.lagrange(cpc, xf, a)[0] for a in range(pc + 1)] for xf in cpf])
-        M = np.einsum("kc,jb,ia->kjicba", I1, I1, I1).reshape((pf + 1) ** 3, (pc + 1) ** 3)
+        M = util.h1_hex_interp_lex(pc, pf)
         ones_c = np.ones(hc.elem_dof_lex.shape, dtype=np.int8)
         ones_f = np.ones(hf.elem_dof_lex.shape, dtype=np.int8)
         o = po.InterpOracle(hc.elem_dof_lex, ones_c, hf.elem_dof_lex, ones_f, hc.ndofs, hf.ndofs, M)

@@ -13,7 +13,7 @@ from tests import util
 pytestmark = pytest.mark.gpu
 REL = 1e-12
 
-PQ = [(1, 2), (2, 3), (3, 4), (4, 5), (1, 4), (2, 4), (3, 5)]
+PQ = [(1, 2), (2, 3), (3, 4), (4, 5), (1, 4), (2, 4), (3, 5), (1, 3), (1, 5), (2, 5)]  # PA_HEX_PQ_LIST
 FORMS = ("mass", "divdiv", "divdivmass")
 _geoms = {}
 

@@ -92,6 +92,14 @@ class FastParOperatorOracle(po.ParOperatorOracle):
         return self._diag
 
 
+def h1_hex_interp_lex(pc, pf):
+    """Dense [(pf+1)^3, (pc+1)^3] element matrix of the H1 p-prolongation in tensor dof order: the Kronecker product of the
+    1-D Lagrange matrices (coarse basis functions at the fine closed nodes), i fastest."""
+    cpc, cpf = po.gll_points(pc + 1), po.gll_points(pf + 1)
+    I1 = np.array([[po.lagrange(cpc, xf, a)[0] for a in range(pc + 1)] for xf in cpf])
+    return np.einsum("kc,jb,ia->kjicba", I1, I1, I1).reshape((pf + 1) ** 3, (pc + 1) ** 3)
+
+
 def hex_rotations():
     """The 24 proper rotations of the reference cube as permutations of the 27 lattice nodes i + 3 j + 9 k (rotation about
     the centre node): returns (R [24, 3, 3] signed permutation matrices with determinant +1, perm [24, 27]) where the rotated
