@@ -379,6 +379,16 @@ int pa_interp_create(pa_context *ctx, const pa_restriction_desc *coarse_restr,
 int pa_gradient_create(pa_context *ctx, const pa_restriction_desc *h1_restr, const pa_basis_desc *h1_basis,
                        const pa_restriction_desc *nd_restr, const pa_basis_desc *nd_basis, const double *Dg,
                        pa_halo *h1_halo, int n_true_h1, int n_true_nd, pa_interp **G);
+/* Discrete curl C : ND(p) -> RT(p) on the same tensor hexahedra (the flux B = curl A; fem/fespace.cpp:199-206 builds it with
+ * the curl interpolator on the Raviart-Thomas space, fem/libceed/basis.cpp:139-150 asks for its element matrix).  With the
+ * nodal tensor bases that matrix is RT_c = D_d ND_e - D_e ND_d over the cyclic triples (c, d, e), D_d being Dg along d and the
+ * identity along the other two directions; it is applied line by line, never formed.
+ *   Dg [p][p+1]  derivative of the closed (Gauss-Lobatto) basis at the open (Gauss-Legendre) nodes, as for pa_gradient_create
+ * Both restrictions are sign-oriented (`orients`), p <= 5.  Mult = C, MultTranspose = C^T through pa_interp_mult /
+ * pa_interp_mult_transpose; nd_halo is the halo of the domain space as coarse_halo is for pa_interp_create. */
+int pa_curl_create(pa_context *ctx, const pa_restriction_desc *nd_restr, const pa_basis_desc *nd_basis,
+                   const pa_restriction_desc *rt_restr, const pa_basis_desc *rt_basis, const double *Dg, pa_halo *nd_halo,
+                   int n_true_nd, int n_true_rt, pa_interp **C);
 /* The same two operators for non-tensor elements (tetrahedra, ...): the element projection matrix
  * M [P_range][P_domain] (row-major) MFEM's GetTransferMatrix / discrete-gradient interpolator gives
  * (basis.cpp:132-150), with the native restrictions of both spaces.  When the range space has a dof

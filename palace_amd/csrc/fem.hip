@@ -466,12 +466,22 @@ void FiniteElementSpace::SetLocalInterpolation(const double *M, int nmat) {
 const Operator &FiniteElementSpace::GetDiscreteInterpolator(const FiniteElementSpace &aux) const {
   auto it = G_.find(&aux);
   if (it != G_.end()) return *it->second;
-  PA_REQUIRE(fe_type_ == PA_FE_HCURL && aux.fe_type_ == PA_FE_H1 && aux.order_ == order_,
-             "the discrete gradient maps the H1 space of the same order into the Nedelec space");
+  const bool grad = fe_type_ == PA_FE_HCURL && aux.fe_type_ == PA_FE_H1, curl = fe_type_ == PA_FE_HDIV && aux.fe_type_ == PA_FE_HCURL;
+  PA_REQUIRE((grad || (curl && !IsDense() && !aux.IsDense() && mesh_ == aux.mesh_)) && aux.order_ == order_,
+             "discrete interpolators: the gradient from the H1 space of the same order into the Nedelec space, or the curl from "
+             "the tensor Nedelec space of the same order on the same mesh into the tensor Raviart-Thomas space");
   // derivative of the closed basis at the open nodes, [p][p + 1]; the identity in the other directions
   std::vector<double> ox, ow, Bg, Dg;
   fem::GaussLegendre(order_, ox, ow);
   fem::LagrangeEval(fem::GaussLobatto(order_ + 1), ox, Bg, Dg);
+  if (curl) {
+    // curl interpolator (fespace.cpp:199-206): RT_c = D_d ND_e - D_e ND_d, the same Dg; the domain halo is the Nedelec space's
+    const auto rn = aux.GetCeedElemRestriction(), rr = GetCeedElemRestriction();
+    const auto bn = aux.GetCeedBasis(), br = GetCeedBasis();
+    auto &slot = G_[&aux];
+    slot.reset(make_interp_operator(*ctx_, rn, bn, rr, br, nullptr, Dg.data(), aux.halo_, aux.true_vsize_, true_vsize_, 2));
+    return *slot;
+  }
   const int n = order_ + 1;
   std::vector<double> I((size_t)n * n, 0.0);
   for (int i = 0; i < n; i++) I[(size_t)i * n + i] = 1.0;

@@ -192,7 +192,9 @@ public:
   // extracts from boundary attribute markers with MFEM)
   void SetEssentialTrueDofs(const int32_t *tdofs, int n) { ess_tdofs_.assign(tdofs, tdofs + n); }
   const std::vector<int32_t> &GetEssentialTrueDofs() const { return ess_tdofs_; }
-  // discrete gradient from the H1 space `aux` of the same order into this Nedelec space (fespace.cpp:171-186)
+  // discrete gradient from the H1 space `aux` of the same order into this Nedelec space (fespace.cpp:171-186), or discrete curl
+  // from the Nedelec space `aux` of the same order on the same mesh into this Raviart-Thomas space (fespace.cpp:199-206); tensor
+  // spaces only, cached per `aux`
   const Operator &GetDiscreteInterpolator(const FiniteElementSpace &aux) const;
   // dof and sign (true: flipped) of tensor (lexicographic) index t of element e -- native index t for dense spaces
   std::pair<int32_t, bool> GetElementDofSigned(int e, int t) const;

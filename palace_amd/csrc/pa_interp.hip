@@ -1036,7 +1036,13 @@ Operator *make_dense_interp_operator(const Context &ctx, const pa_restriction_de
   return new DenseInterpOperator(ctx, rd, rr, M, halo_d, nt_d, nt_r, nmat, mat_id);
 }
 
+// pa_curl_hex.hip: the discrete curl ND(p) -> RT(p) on the index arrays of an InterpOperator of kind 2
+void launch_curl_hex(bool transpose, int p, int ne, const int32_t *lidx_nd, const int32_t *lidx_rt, const double *Dg, const double *Dg_dev,
+                     const double *x, double *out, hipStream_t stream);
+
 // The prolongation as an Operator on T-vectors: Mult coarse -> fine, MultTranspose fine -> coarse.
+// kind 0: p-prolongation within one element family; 1: discrete gradient H1(p) -> ND(p); 2: discrete curl ND(p) -> RT(p) (the
+// "coarse" side is the domain, the "fine" side the range)
 class InterpOperator : public Operator {
   const Context *ctx_;
   const Halo *halo_c_;
@@ -1050,6 +1056,10 @@ class InterpOperator : public Operator {
 
   template <bool TR>
   void launch(const double *x, double *y) const {
+    if (kind_ == 2) {
+      launch_curl_hex(TR, pf_, ne_, d_lidx_c_, d_lidx_f_, h_Io_.data(), d_Io_, x, TR ? d_ye_c_ : y, ctx_->stream);
+      return;
+    }
     InterpArgs a{kind_, ne_, fe_type_, pc_, pf_, d_lidx_c_, d_lidx_f_, d_Ic_, d_Io_, x, y, d_ye_c_, {}, {}};
     const int n1 = pf_ + 1, epw = 64 / (n1 * n1), epb = 4 * epw;
     const size_t lds = sizeof(double) * (size_t)epb * 2 * n1 * n1 * n1;
@@ -1087,16 +1097,25 @@ public:
     if (kind == 1) {
       PA_REQUIRE(bc.fe_type == PA_FE_H1 && bf.fe_type == PA_FE_HCURL && bc.order == bf.order,
                  "discrete gradient maps H1(p) to ND(p)");
+    } else if (kind == 2) {
+      PA_REQUIRE(bc.fe_type == PA_FE_HCURL && bf.fe_type == PA_FE_HDIV, "discrete curl maps a Nedelec space to a Raviart-Thomas space");
+      PA_REQUIRE(bc.order == bf.order, "discrete curl needs the same order on both sides");
+      PA_REQUIRE(bf.order >= 1 && bf.order + 1 <= kMaxN, "discrete curl: order above 5");
+      PA_REQUIRE(rc.num_elem == rf.num_elem, "discrete curl needs the same elements on both sides");
+      PA_REQUIRE(!rc.curl_orients && !rf.curl_orients, "discrete curl on tensor hexahedra takes sign orientations, not curl_orients");
+      PA_REQUIRE(Io, "discrete curl: the 1-D derivative matrix is missing");
     } else {
       PA_REQUIRE(bc.fe_type == bf.fe_type, "prolongation needs the same element family on both levels");
     }
     PA_REQUIRE(rc.num_elem == rf.num_elem, "prolongation needs the same mesh on both levels");
     PA_REQUIRE(pf_ + 1 <= kMaxN && pc_ <= pf_, "unsupported orders for prolongation");
-    PA_REQUIRE(Ic && (kind == 0 && fe_type_ == PA_FE_H1 ? true : Io != nullptr), "1-D interpolation matrices missing");
+    PA_REQUIRE((Ic || kind == 2) && (kind == 0 && fe_type_ == PA_FE_H1 ? true : Io != nullptr), "1-D interpolation matrices missing");
     PA_REQUIRE(nt_c <= nl_c_ && nt_f <= nl_f_, "true dof counts exceed local sizes");
-    PA_REQUIRE(halo_c || nt_c == nl_c_, "ghost dofs on the coarse level need a halo plan");
+    PA_REQUIRE(halo_c || nt_c == nl_c_, kind == 2 ? "ghost dofs on the Nedelec side need a halo plan" : "ghost dofs on the coarse level need a halo plan");
     const int Pc = bc.fe_type == PA_FE_HCURL ? 3 * pc_ * (pc_ + 1) * (pc_ + 1) : (pc_ + 1) * (pc_ + 1) * (pc_ + 1);
-    const int Pf = bf.fe_type == PA_FE_HCURL ? 3 * pf_ * (pf_ + 1) * (pf_ + 1) : (pf_ + 1) * (pf_ + 1) * (pf_ + 1);
+    const int Pf = bf.fe_type == PA_FE_HCURL  ? 3 * pf_ * (pf_ + 1) * (pf_ + 1)
+                   : bf.fe_type == PA_FE_HDIV ? 3 * pf_ * pf_ * (pf_ + 1)
+                                              : (pf_ + 1) * (pf_ + 1) * (pf_ + 1);
     PA_REQUIRE(rc.elem_size == Pc && rf.elem_size == Pf, "restriction sizes do not match the bases");
     auto lc = signed_lex_index(rc, bc, Pc), lf = signed_lex_index(rf, bf, Pf);
     PA_REQUIRE(nl_f_ < kOwnBit, "too many fine dofs for the owner-flag encoding");
@@ -1126,10 +1145,12 @@ public:
     }
     d_lidx_c_ = pa::dev_upload(lc.data(), lc.size(), ctx.stream);
     d_lidx_f_ = pa::dev_upload(lf.data(), lf.size(), ctx.stream);
-    d_Ic_ = pa::dev_upload(Ic, (size_t)(pf_ + 1) * (pc_ + 1), ctx.stream);
-    h_Ic_.assign(Ic, Ic + (size_t)(pf_ + 1) * (pc_ + 1));
+    if (Ic) {
+      d_Ic_ = pa::dev_upload(Ic, (size_t)(pf_ + 1) * (pc_ + 1), ctx.stream);
+      h_Ic_.assign(Ic, Ic + (size_t)(pf_ + 1) * (pc_ + 1));
+    }
     if (Io) {
-      const size_t nio = kind == 1 ? (size_t)pf_ * (pf_ + 1) : (size_t)pf_ * pc_;
+      const size_t nio = kind != 0 ? (size_t)pf_ * (pf_ + 1) : (size_t)pf_ * pc_;
       d_Io_ = pa::dev_upload(Io, nio, ctx.stream);
       h_Io_.assign(Io, Io + nio);
     }

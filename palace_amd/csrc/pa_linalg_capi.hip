@@ -1153,6 +1153,17 @@ int pa_gradient_create(pa_context *ctx, const pa_restriction_desc *rh, const pa_
     *G = p;
   });
 }
+int pa_curl_create(pa_context *ctx, const pa_restriction_desc *rn, const pa_basis_desc *bn, const pa_restriction_desc *rr,
+                   const pa_basis_desc *br, const double *Dg, pa_halo *nd_halo, int nt_nd, int nt_rt, pa_interp **Cu) {
+  return guarded([&] {
+    PA_REQUIRE(ctx && rn && bn && rr && br && Dg && Cu, "null argument");
+    auto *p = new pa_interp;
+    p->ctx = ctx;
+    p->op.reset(make_interp_operator(ctx->ctx, *rn, *bn, *rr, *br, nullptr, Dg, nd_halo ? nd_halo->halo.get() : nullptr, nt_nd,
+                                     nt_rt, 2));
+    *Cu = p;
+  });
+}
 int pa_interp_create_dense(pa_context *ctx, const pa_restriction_desc *dom, const pa_restriction_desc *range,
                            const double *M, pa_halo *dom_halo, int nt_dom, int nt_range, pa_interp **P) {
   return guarded([&] {

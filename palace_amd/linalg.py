@@ -822,6 +822,26 @@ class Gradient(Interp):
                                            nd_space.ndofs if n_true_nd is None else n_true_nd, C.byref(self.handle)))
 
 
+class Curl(Interp):
+    """Discrete curl C : ND(p) -> RT(p) on tensor hexahedra (the flux B = curl A, fem/fespace.cpp:199-206), sum-factorised:
+    pa_curl_create.  mult = C, mult_transpose = C^T."""
+
+    def __init__(self, ctx, nd_space, rt_space, nd_halo=None, n_true_nd=None, n_true_rt=None):
+        self.ctx = ctx
+        p = rt_space.p
+        _, Dg = lagrange_eval(gauss_lobatto(p + 1), gauss_legendre(p)[0])  # [p][p+1]
+        Dg = np.ascontiguousarray(Dg)
+        rn, k1 = _restriction_desc(nd_space)
+        rr, k2 = _restriction_desc(rt_space)
+        bn, k3 = _basis_desc(nd_space, p + 1)
+        br, k4 = _basis_desc(rt_space, p + 1)
+        self.handle = C.c_void_p()
+        _lib.check(_L().pa_curl_create(ctx.handle, C.byref(rn), C.byref(bn), C.byref(rr), C.byref(br), _ptr(Dg),
+                                       nd_halo.handle if nd_halo else None,
+                                       nd_space.ndofs if n_true_nd is None else n_true_nd,
+                                       rt_space.ndofs if n_true_rt is None else n_true_rt, C.byref(self.handle)))
+
+
 def gmg(ctx, A_levels, P_levels, coarse: Solver, cycle_it=1, smooth_it=1, cheby_order=4, sf_max=1.0, sf_min=0.0,
         fourth_kind=True, A_aux=None, G=None):
     """GeometricMultigridSolver (gmg.cpp); takes ownership of `coarse`.  With A_aux (H1 ParOperators)
