@@ -360,6 +360,14 @@ int pa_error_op_create_tensor(pa_geom *geom, const pa_restriction_desc *restr1, 
                               const pa_restriction_desc *restr2, const pa_basis_desc *basis2, int32_t qfunction, const void *ctx,
                               size_t ctx_size, pa_error_op **out);
 int pa_error_op_apply_add(pa_error_op *e, const double *u1, const double *u2, double *estimates, void *stream);
+/* Both parts of a complex field: estimates[e] += eta_e^2(u1_re, u2_re) + eta_e^2(u1_im, u2_im), what ComputeErrorEstimates
+ * does with two ApplyAdd calls (linalg/errorestimator.cpp:249-261).  Tensor operators whose (order, points) pair has a two-part
+ * kernel (pa_error_op_two_parts: 1) run one launch that reads the geometry rows and index words of an element for both
+ * parts; every other operator, the dense-table ones of pa_error_op_create included, runs the two passes in that order.
+ * PALACE_AMD_TWO_PART=0 forces the two passes. */
+int pa_error_op_apply_add2(pa_error_op *e, const double *u1_re, const double *u2_re, const double *u1_im, const double *u2_im,
+                           double *estimates, void *stream);
+int pa_error_op_two_parts(const pa_error_op *e);
 int pa_error_op_num_elem(const pa_error_op *e);
 void pa_error_op_destroy(pa_error_op *e);
 /* SURVEY.md 8(f)-1, behind BuildParSumOperator (linalg/rap.cpp:843-919) and SpaceOperator::GetSystemMatrix
@@ -506,7 +514,11 @@ int pa_op_mult_split(pa_op *op, const double *x, const double *xg0, const double
 /* Two right-hand sides in one pass: y0 = A x0, y1 = A x1.  This is what ComplexWrapperOperator::Mult needs
  * (linalg/operator.cpp:98-134: Ar and Ai are each applied to the real and to the imaginary part); the element's index
  * arrays and D-stage data are read once for both vectors.  The *_essential_diag form is the two-vector version of
- * pa_op_mult_essential_diag. */
+ * pa_op_mult_essential_diag.  One pass where such a kernel exists -- a single H(curl) hexahedron block on packed D with at
+ * most four points per direction, a single H(div) hexahedron block on packed D, a single tensor two-space block (pa_op_add_sub_mixed)
+ * whose (order, points) pair is compiled in -- else two applies; pa_op_two_rhs tells which (1: one pass).  PALACE_AMD_TWO_PART=0
+ * keeps the H(div) and two-space blocks on two applies. */
+int pa_op_two_rhs(const pa_op *op);
 int pa_op_mult2(pa_op *op, const double *x0, const double *x1, double *y0, double *y1, void *stream);
 int pa_op_mult2_essential_diag(pa_op *op, const double *x0, const double *x1, double *y0, double *y1, int diag_policy,
                                void *stream, int *handled);

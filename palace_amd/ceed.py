@@ -193,6 +193,17 @@ class ElementErrorIntegrator:
                                                      C.c_void_p(estimates.data_ptr()), _stream()))
         return estimates
 
+    def apply_add2(self, u1_re, u2_re, u1_im, u2_im, estimates):
+        """Both parts of a complex field: estimates += eta^2(u1_re, u2_re) + eta^2(u1_im, u2_im) (pa_error_op_apply_add2; one
+        launch where two_parts(), else the two passes of ComputeErrorEstimates, errorestimator.cpp:249-261)."""
+        _lib.check(_lib.load().pa_error_op_apply_add2(self.handle, *(C.c_void_p(v.data_ptr()) for v in (u1_re, u2_re, u1_im, u2_im)),
+                                                      C.c_void_p(estimates.data_ptr()), _stream()))
+        return estimates
+
+    def two_parts(self):
+        """True when apply_add2 runs one launch over the element data (pa_error_op_two_parts)."""
+        return bool(_lib.load().pa_error_op_two_parts(self.handle))
+
     def __del__(self):
         try:  # (module globals may already be gone at interpreter shutdown)
             if getattr(self, "handle", None):
@@ -464,6 +475,10 @@ class Operator:
         _lib.check(_lib.load().pa_op_mult2(self.handle, C.c_void_p(x0.data_ptr()), C.c_void_p(x1.data_ptr()),
                                            C.c_void_p(y0.data_ptr()), C.c_void_p(y1.data_ptr()), _stream()))
         return y0, y1
+
+    def two_rhs(self):
+        """True when mult2 runs one pass over the element data, False when it runs two applies (pa_op_two_rhs)."""
+        return bool(_lib.load().pa_op_two_rhs(self.handle))
 
     def mult_transpose(self, x, y):
         """y = A^T x (Operator::MultTranspose, fem/libceed/operator.cpp:214-224)."""

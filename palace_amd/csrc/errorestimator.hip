@@ -230,6 +230,176 @@ CurlFluxErrorEstimator::CurlFluxErrorEstimator(const MaterialTensors &muinv, con
                              muinv.Map([](const double *m) { return linalg::MatrixSqrt(m); }),
                              muinv.Map([](const double *m) { return linalg::MatrixPow(m, -0.5); }), tol, max_it, print) {}
 
+// ---- the same for a ComplexVector -------------------------------------------------------------------------------------
+namespace {
+
+// the error integrator of two dense-table spaces or two tensor spaces on one mesh (both estimator bases)
+pa_error_op *make_error_op(const FiniteElementSpace &fespace, const FiniteElementSpace &smooth_fespace, int error_qf,
+                           const MaterialTensors &first, const MaterialTensors &second) {
+  PA_REQUIRE(fespace.IsDense() == smooth_fespace.IsDense() && &fespace.GetMesh() == &smooth_fespace.GetMesh(),
+             "the estimators take two dense-table spaces or two tensor spaces on one mesh");
+  PA_REQUIRE(first.dim == second.dim, "the two coefficients of an error integrator have one dimension");
+  const auto c1 = first.Coefficient(), c2 = second.Coefficient();
+  const auto ctx = ceed::PopulateCoefficientContext(first.dim, &c1, second.dim, &c2);
+  const auto r1 = fespace.GetCeedElemRestriction(), r2 = smooth_fespace.GetCeedElemRestriction();
+  pa_error_op *op = nullptr;
+  if (!fespace.IsDense()) {
+    const auto b1 = fespace.GetCeedBasis(), b2 = smooth_fespace.GetCeedBasis();
+    check(pa_error_op_create_tensor(fespace.GetMesh().GetCeedGeomFactorData(), &r1, &b1, &r2, &b2, error_qf, ctx.data(),
+                                    ctx.size() * sizeof(double), &op));
+  } else {
+    const auto b1 = fespace.GetCeedDenseBasis(), b2 = smooth_fespace.GetCeedDenseBasis();
+    check(pa_error_op_create(fespace.GetMesh().GetCeedGeomFactorData(), &r1, &b1, &r2, &b2, error_qf, ctx.data(),
+                             ctx.size() * sizeof(double), &op));
+  }
+  return op;
+}
+
+// true-dof vector -> L-vector through the halo: lv[0, n) = x, ghosts filled
+void to_lvector(const Context &ctx, const Halo &h, const Vector &x, Vector &lv) {
+  Vector t(lv.Data(), x.Size());
+  linalg::Copy(ctx, x, t);
+  h.Prolongate(lv.Data(), ctx.stream);
+}
+
+}  // namespace
+
+ComplexFluxProjector::ComplexFluxProjector(const MaterialPropertyCoefficient &coeff, const FiniteElementSpace &smooth_fespace,
+                                           const FiniteElementSpace &rhs_fespace, double tol, int max_it, int print)
+    : ctx_(&smooth_fespace.GetContext()), smooth_(&smooth_fespace), rhs_space_(&rhs_fespace) {
+  PhaseRange range("Estimation / Construction");
+  const bool scalar_flux = smooth_fespace.GetFEType() == PA_FE_H1;
+  {
+    BilinearForm m(smooth_fespace);
+    if (scalar_flux)
+      m.AddDomainIntegrator<MassIntegrator>((const MaterialPropertyCoefficient *)nullptr);
+    else
+      m.AddDomainIntegrator<VectorFEMassIntegrator>((const MaterialPropertyCoefficient *)nullptr);
+    mass_ = m.PartialAssemble();
+    // BuildLevelParOperator<ComplexOperator> (:50-65): the real mass matrix as the real part, no imaginary part
+    M_ = std::make_unique<ComplexParOperator>(*ctx_, mass_.get(), nullptr, smooth_fespace.GetTrueVSize(), smooth_fespace.GetHalo());
+  }
+  {
+    BilinearForm flux(rhs_fespace, smooth_fespace);
+    if (scalar_flux)
+      flux.AddDomainIntegrator<MassIntegrator>(coeff);
+    else
+      flux.AddDomainIntegrator<VectorFEMassIntegrator>(coeff);
+    flux_ = flux.PartialAssemble();
+  }
+  pc_ = std::make_unique<ComplexJacobiSmoother>(*ctx_);
+  pcg_ = std::make_unique<ComplexCgSolver>(*ctx_, print);
+  pcg_->SetTol(tol);
+  pcg_->SetAbsTol(std::numeric_limits<double>::epsilon());
+  pcg_->SetMaxIter(max_it);
+  Mboth_ = std::make_unique<ComplexMassOperator>(*mass_, *M_, smooth_fespace.GetHalo() != nullptr);
+  pcg_->SetOperator(*Mboth_);
+  pc_->SetOperator(*M_);
+  pcg_->SetPreconditioner(*pc_);
+  rhs_.SetSize(smooth_fespace.GetTrueVSize());
+  if (rhs_fespace.GetHalo()) lx_.SetSize(rhs_fespace.GetVSize());
+  if (smooth_fespace.GetHalo()) ly_.SetSize(smooth_fespace.GetVSize());
+}
+
+bool ComplexFluxProjector::FluxTwoRhs() const { return pa_op_two_rhs(flux_->Handle()) != 0; }
+
+ComplexMassOperator::ComplexMassOperator(const ceed::Operator &mass, const ComplexParOperator &par, bool has_halo)
+    : ComplexOperator(par.Height(), par.Width()), mass_(&mass), par_(&par), has_halo_(has_halo) {}
+
+// (with a streaming form two separate applies are the faster choice, as in ParOperator::Mult2)
+bool ComplexMassOperator::OnePass() const { return !has_halo_ && pa_op_two_rhs(mass_->Handle()) != 0 && !mass_->Streams(); }
+
+void ComplexMassOperator::Mult(const ComplexVector &x, ComplexVector &y) const {
+  if (!OnePass()) return par_->Mult(x, y);
+  mass_->Mult2(x.Real(), x.Imag(), y.Real(), y.Imag());  // no essential dofs, no imaginary part: yr = M xr, yi = M xi
+  one_pass_applies_++;
+}
+
+void ComplexFluxProjector::Mult(const ComplexVector &x, ComplexVector &y) const {
+  PhaseRange range("Estimation / Solve");
+  PA_REQUIRE(x.Size() == rhs_space_->GetTrueVSize() && y.Size() == rhs_.Size(),
+             "Invalid vector dimensions for ComplexFluxProjector::Mult!");
+  const Halo *hx = rhs_space_->GetHalo(), *hy = smooth_->GetHalo();
+  const Vector *in_r = &x.Real(), *in_i = &x.Imag();
+  if (hx) {
+    to_lvector(*ctx_, *hx, x.Real(), lx_.Real());
+    to_lvector(*ctx_, *hx, x.Imag(), lx_.Imag());
+    in_r = &lx_.Real(), in_i = &lx_.Imag();
+  }
+  if (hy) {
+    flux_->Mult2(*in_r, *in_i, ly_.Real(), ly_.Imag());
+    for (Vector *part : {&ly_.Real(), &ly_.Imag()}) hy->RestrictAdd(part->Data(), ctx_->stream);
+    Vector tr(ly_.Real().Data(), rhs_.Size()), ti(ly_.Imag().Data(), rhs_.Size());
+    linalg::Copy(*ctx_, tr, rhs_.Real());
+    linalg::Copy(*ctx_, ti, rhs_.Imag());
+  } else {
+    flux_->Mult2(*in_r, *in_i, rhs_.Real(), rhs_.Imag());
+  }
+  pcg_->Mult(rhs_, y, false);
+}
+
+ComplexFluxErrorEstimatorBase::ComplexFluxErrorEstimatorBase(const FiniteElementSpace &fespace,
+                                                             const FiniteElementSpace &smooth_fespace,
+                                                             const MaterialPropertyCoefficient &flux_coeff, int error_qf,
+                                                             const MaterialTensors &first, const MaterialTensors &second,
+                                                             double tol, int max_it, int print)
+    : ctx_(&fespace.GetContext()), fespace_(fespace), smooth_fespace_(smooth_fespace),
+      projector_(flux_coeff, smooth_fespace, fespace, tol, max_it, print) {
+  G_.SetSize(smooth_fespace.GetTrueVSize());
+  integ_op_ = make_error_op(fespace, smooth_fespace, error_qf, first, second);
+}
+
+ComplexFluxErrorEstimatorBase::~ComplexFluxErrorEstimatorBase() { pa_error_op_destroy(integ_op_); }
+
+void ComplexFluxErrorEstimatorBase::AddErrorEstimates(const ComplexVector &F, Vector &estimates) const {
+  PA_REQUIRE(F.Size() == fespace_.GetTrueVSize() && estimates.Size() == fespace_.GetMesh().GetNE(),
+             "Invalid vector dimensions for the error estimate!");
+  projector_.Mult(F, G_);
+  // both parts of F and G as L-vectors (:202-214), then one error integrator call for the two parts (:249-261)
+  const Halo *hf = fespace_.GetHalo(), *hg = smooth_fespace_.GetHalo();
+  ComplexVector F_gf, G_gf;
+  const double *pf[2] = {F.Real().Data(), F.Imag().Data()}, *pg[2] = {G_.Real().Data(), G_.Imag().Data()};
+  if (hf) {
+    F_gf.SetSize(fespace_.GetVSize());
+    to_lvector(*ctx_, *hf, F.Real(), F_gf.Real());
+    to_lvector(*ctx_, *hf, F.Imag(), F_gf.Imag());
+    pf[0] = F_gf.Real().Data(), pf[1] = F_gf.Imag().Data();
+  }
+  if (hg) {
+    G_gf.SetSize(smooth_fespace_.GetVSize());
+    to_lvector(*ctx_, *hg, G_.Real(), G_gf.Real());
+    to_lvector(*ctx_, *hg, G_.Imag(), G_gf.Imag());
+    pg[0] = G_gf.Real().Data(), pg[1] = G_gf.Imag().Data();
+  }
+  check(pa_error_op_apply_add2(integ_op_, pf[0], pg[0], pf[1], pg[1], estimates.Data(), ctx_->stream));
+  if (hf || hg) PA_HIP(hipStreamSynchronize(ctx_->stream));  // the temporaries go out of scope
+}
+
+void ComplexFluxErrorEstimatorBase::AddErrorIndicator(const ComplexVector &F, double Et, ErrorIndicator &indicator) const {
+  PhaseRange range("Estimation");
+  Vector estimates(fespace_.GetMesh().GetNE());
+  linalg::Fill(*ctx_, estimates, 0.0);
+  AddErrorEstimates(F, estimates);
+  linalg::Sqrt(*ctx_, estimates, (Et > 0.0) ? 0.5 / Et : 1.0);  // Correct factor of 1/2 in energy
+  indicator.AddIndicator(estimates);
+}
+
+ComplexGradFluxErrorEstimator::ComplexGradFluxErrorEstimator(const MaterialTensors &epsilon, const FiniteElementSpace &nd_fespace,
+                                                             const FiniteElementSpace &rt_fespace, double tol, int max_it,
+                                                             int print)
+    : ComplexFluxErrorEstimatorBase(nd_fespace, rt_fespace, epsilon.Coefficient(),
+                                    nd_fespace.GetMesh().Dimension() == 2 ? PA_QF_HCURLHDIV_ERROR_22 : PA_QF_HCURLHDIV_ERROR_33,
+                                    epsilon.Map([](const double *m) { return linalg::MatrixSqrt(m); }),
+                                    epsilon.Map([](const double *m) { return linalg::MatrixPow(m, -0.5); }), tol, max_it, print) {}
+
+ComplexCurlFluxErrorEstimator::ComplexCurlFluxErrorEstimator(const MaterialTensors &muinv, const FiniteElementSpace &rt_fespace,
+                                                             const FiniteElementSpace &nd_fespace, double tol, int max_it,
+                                                             int print)
+    : ComplexFluxErrorEstimatorBase(rt_fespace, nd_fespace, muinv.Coefficient(),
+                                    rt_fespace.GetMesh().Dimension() == 2 ? PA_QF_L2H1_ERROR : PA_QF_HDIVHCURL_ERROR_33,
+                                    muinv.Map([](const double *m) { return linalg::MatrixSqrt(m); }),
+                                    muinv.Map([](const double *m) { return linalg::MatrixPow(m, -0.5); }), tol, max_it, print) {}
+
 TimeDependentFluxErrorEstimator::TimeDependentFluxErrorEstimator(const MaterialTensors &epsilon, const MaterialTensors &muinv,
                                                                  const FiniteElementSpace &nd_fespace,
                                                                  const FiniteElementSpace &rt_fespace, double tol,

@@ -5,14 +5,20 @@
 // Spaces are two dense-table spaces on one dense Mesh (fem.hpp; the operators are pa_op_add_sub_dense[_mixed] and
 // pa_error_op_create, pa_mixed.hip) or, for the 3-D vector estimators on hexahedra, two tensor spaces of one order on one tensor
 // Mesh (pa_op_add_sub, pa_op_add_sub_mixed and pa_error_op_create_tensor: sum-factorised, pa_rt_hex.hip / pa_nd_hex.hip /
-// pa_mixed_hex.hip).  Real vectors; a complex field is estimated part by part into the same estimates, as
-// ComputeErrorEstimates does for a ComplexVector (:255-261).
+// pa_mixed_hex.hip).  FluxProjector and the two estimators come for real vectors and, as Complex*, for a ComplexVector (the
+// reference's second instantiation, errorestimator.cpp:183-268, :272-480).  There the flux operator (ceed::Operator::Mult2) and the
+// error integrator (pa_error_op_apply_add2) take both parts together, and so does the mass apply inside the PCG where it can:
+// on one rank, where the mass operator has a two-vector kernel and no streaming form (ComplexMassOperator below); with a halo, or
+// without such a kernel, the mass solve runs two applies per iteration.  On tensor hexahedra "together" is one pass over the
+// element data where a two-part kernel is compiled in (pa_op_two_rhs, pa_error_op_two_parts), two passes in the reference's
+// order everywhere else.
 #pragma once
 
 #include <array>
 #include <memory>
 #include <vector>
 
+#include "complex.hpp"
 #include "fem.hpp"
 #include "ksp.hpp"
 
@@ -123,7 +129,86 @@ public:
                          const FiniteElementSpace &nd_fespace, double tol, int max_it, int print);
 };
 
-// :512-541: both of the above added before the square root
+// FluxProjector<ComplexVector> (errorestimator.cpp:111-187): the same two forms; M is a ComplexParOperator with a real part only
+// (BuildLevelParOperator<ComplexOperator>, :50-65), the solver ComplexCgSolver + ComplexJacobiSmoother (ConfigureLinearSolver
+// with use_mg = false), the flux operator is applied to both parts at once (ceed::Operator::Mult2)
+// The projector's system matrix as the PCG applies it: y = M x on both parts of x.  ComplexParOperator::Mult applies a real
+// part without essential dofs as two one-part applies; here, on one rank and where the mass operator has a two-vector kernel and
+// no streaming form (pa_op_two_rhs, pa_op_streams), both parts go through one ceed::Operator::Mult2.  Everything else, and the
+// diagonal, is the ComplexParOperator's.
+class ComplexMassOperator : public ComplexOperator {
+  const ceed::Operator *mass_;
+  const ComplexParOperator *par_;
+  bool has_halo_;
+  mutable long one_pass_applies_ = 0;
+
+public:
+  ComplexMassOperator(const ceed::Operator &mass, const ComplexParOperator &par, bool has_halo);
+  const Operator *Real() const override { return par_->Real(); }
+  void AssembleDiagonal(ComplexVector &diag) const override { par_->AssembleDiagonal(diag); }
+  void Mult(const ComplexVector &x, ComplexVector &y) const override;
+  bool OnePass() const;                                       // the route Mult takes (PALACE_AMD_TWO_PART is read at every call)
+  long OnePassApplies() const { return one_pass_applies_; }   // how often it took the one-pass route
+};
+
+class ComplexFluxProjector {
+  const Context *ctx_;
+  std::unique_ptr<ceed::Operator> flux_, mass_;
+  std::unique_ptr<ComplexParOperator> M_;
+  std::unique_ptr<ComplexMassOperator> Mboth_;
+  std::unique_ptr<ComplexJacobiSmoother> pc_;
+  std::unique_ptr<ComplexCgSolver> pcg_;
+  const FiniteElementSpace *smooth_, *rhs_space_;
+  mutable ComplexVector rhs_, lx_, ly_;
+
+public:
+  ComplexFluxProjector(const MaterialPropertyCoefficient &coeff, const FiniteElementSpace &smooth_fespace,
+                       const FiniteElementSpace &rhs_fespace, double tol, int max_it, int print);
+  void Mult(const ComplexVector &x, ComplexVector &y) const;
+  int NumIterations() const { return pcg_->GetNumIterations(); }
+  bool FluxTwoRhs() const;  // the flux operator takes both parts in one pass over the element data (pa_op_two_rhs)
+  bool MassTwoRhs() const { return Mboth_->OnePass(); }  // ... and so does the mass apply inside the PCG (the route taken)
+  long MassOnePassApplies() const { return Mboth_->OnePassApplies(); }  // mass applies that went through Mult2 so far
+};
+
+// The estimators for a complex field: F and its smooth recovery G as ComplexVectors, estimates += error^2 of the real parts +
+// error^2 of the imaginary parts (ComputeErrorEstimates, :249-261) through one pa_error_op_apply_add2
+class ComplexFluxErrorEstimatorBase {
+protected:
+  const Context *ctx_;
+  const FiniteElementSpace &fespace_, &smooth_fespace_;
+  ComplexFluxProjector projector_;
+  pa_error_op *integ_op_ = nullptr;
+  mutable ComplexVector G_;
+
+  ComplexFluxErrorEstimatorBase(const FiniteElementSpace &fespace, const FiniteElementSpace &smooth_fespace,
+                                const MaterialPropertyCoefficient &flux_coeff, int error_qf, const MaterialTensors &first,
+                                const MaterialTensors &second, double tol, int max_it, int print);
+
+public:
+  virtual ~ComplexFluxErrorEstimatorBase();
+  ComplexFluxErrorEstimatorBase(const ComplexFluxErrorEstimatorBase &) = delete;
+  void AddErrorEstimates(const ComplexVector &F, Vector &estimates) const;
+  void AddErrorIndicator(const ComplexVector &F, double Et, ErrorIndicator &indicator) const;
+  int NumElements() const { return fespace_.GetMesh().GetNE(); }
+  const ComplexFluxProjector &GetProjector() const { return projector_; }
+  const ComplexVector &GetSmoothFlux() const { return G_; }
+  bool TwoParts() const { return pa_error_op_two_parts(integ_op_) != 0; }  // the error integrator runs one launch for both parts
+};
+
+class ComplexGradFluxErrorEstimator : public ComplexFluxErrorEstimatorBase {
+public:
+  ComplexGradFluxErrorEstimator(const MaterialTensors &epsilon, const FiniteElementSpace &nd_fespace,
+                                const FiniteElementSpace &rt_fespace, double tol, int max_it, int print);
+};
+
+class ComplexCurlFluxErrorEstimator : public ComplexFluxErrorEstimatorBase {
+public:
+  ComplexCurlFluxErrorEstimator(const MaterialTensors &muinv, const FiniteElementSpace &rt_fespace,
+                                const FiniteElementSpace &nd_fespace, double tol, int max_it, int print);
+};
+
+// :512-541: both of the above added before the square root (real in the reference)
 class TimeDependentFluxErrorEstimator {
   const Context *ctx_;
   GradFluxErrorEstimator grad_;

@@ -592,7 +592,8 @@ void finalize_exclusive(pa_op *op) {
 }
 
 // y0 = A x0, y1 = A x1 (overwrite).  One pass over the index / q-data streams when the operator is a single
-// H(curl) hex block on the q-data path, else two applies.
+// H(curl) hex block on the q-data path, a single H(div) hex block on packed D or a single tensor two-space block with a
+// compiled two-part kernel (two_rhs_one_pass below), else two applies.
 static bool apply2(pa_op *op, const double *x0, const double *x1, double *y0, double *y1, hipStream_t s, bool masked,
                    int ess_policy) {
   PA_REQUIRE(op && x0 && x1 && y0 && y1, "null argument");
@@ -605,9 +606,39 @@ static bool apply2(pa_op *op, const double *x0, const double *x1, double *y0, do
     launch_et_gather2(*so, y0, y1, false, s, x0, x1, pol);
     return pol >= 0;
   }
+  // a single Raviart-Thomas block on packed D: one element pass, one gather over the (flagged) dof list for both vectors
+  if (op->subs.size() == 1 && op->dsubs.empty() && op->msubs.empty() && !TransposeScope::active() &&
+      rt_hex_supports_two_rhs(*op->subs[0])) {
+    SubOp *so = op->subs[0];
+    launch_rt_hex_apply2(*so, x0, x1, masked, s);
+    const bool fuse = masked && ess_policy >= 0 && so->d_shared_bc;
+    launch_et_gather2_raw(so->lsize, so->d_tptr, so->d_tent, so->d_ye, so->d_ye2, y0, y1, false, s, fuse ? so->d_shared_bc : nullptr,
+                          x0, x1, fuse ? ess_policy : -1);
+    return fuse;
+  }
+  // a single tensor two-space block whose pair has a two-part kernel
+  if (op->subs.empty() && op->dsubs.empty() && op->msubs.size() == 1 && !masked && !TransposeScope::active() &&
+      mixed_hex_two_part(*op->msubs[0])) {
+    launch_mixed_apply2(*op->msubs[0], x0, x1, y0, y1, false, s);
+    return false;
+  }
   apply(op, x0, y0, true, s, masked, -1);
   apply(op, x1, y1, true, s, masked, -1);
   return false;
+}
+
+// pa_op_two_rhs: apply2 above runs one pass over the element data
+static bool two_rhs_one_pass(const pa_op *op) {
+  if (op->subs.size() == 1 && op->dsubs.empty() && nd_hex_supports_two_rhs(*op->subs[0])) return true;
+  if (op->subs.size() == 1 && op->dsubs.empty() && op->msubs.empty() && rt_hex_supports_two_rhs(*op->subs[0])) return true;
+  return op->subs.empty() && op->dsubs.empty() && op->msubs.size() == 1 && mixed_hex_two_part(*op->msubs[0]);
+}
+
+// PALACE_AMD_TWO_PART=0: the Raviart-Thomas and two-space operators and the error integrators keep two one-part passes (the
+// A/B handle of the two-part kernels and their fall-back; the H(curl) two-vector form is not affected).  Read at every call.
+bool two_part_enabled() {
+  const char *mode = getenv("PALACE_AMD_TWO_PART");
+  return !(mode && std::string(mode) == "0");
 }
 
 void apply_for_assembly(pa_op *op, const double *x, double *y, hipStream_t s) { apply(op, x, y, true, s); }
@@ -909,6 +940,16 @@ int pa_error_op_apply_add(pa_error_op *e, const double *u1, const double *u2, do
     launch_mixed_error(*e->ms, u1, u2, estimates, (hipStream_t)stream);
   });
 }
+
+int pa_error_op_apply_add2(pa_error_op *e, const double *u1_re, const double *u2_re, const double *u1_im, const double *u2_im,
+                           double *estimates, void *stream) {
+  return guarded([&] {
+    PA_REQUIRE(e && e->ms && u1_re && u2_re && u1_im && u2_im && estimates, "null argument");
+    launch_mixed_error2(*e->ms, u1_re, u2_re, u1_im, u2_im, estimates, (hipStream_t)stream);
+  });
+}
+
+int pa_error_op_two_parts(const pa_error_op *e) { return (e && e->ms && mixed_hex_two_part(*e->ms)) ? 1 : 0; }
 
 int pa_error_op_num_elem(const pa_error_op *e) { return (e && e->ms) ? e->ms->ne : -1; }
 
@@ -1484,6 +1525,8 @@ int pa_op_mult_split_step(pa_op *op, const double *x, const double *xg0, const d
 int pa_op_mult2(pa_op *op, const double *x0, const double *x1, double *y0, double *y1, void *stream) {
   return guarded([&] { apply2(op, x0, x1, y0, y1, (hipStream_t)stream, false, -1); });
 }
+
+int pa_op_two_rhs(const pa_op *op) { return (op && two_rhs_one_pass(op)) ? 1 : 0; }
 
 int pa_op_mult2_essential_diag(pa_op *op, const double *x0, const double *x1, double *y0, double *y1, int diag_policy,
                                void *stream, int *handled) {

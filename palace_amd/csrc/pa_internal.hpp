@@ -380,6 +380,11 @@ void launch_h1_hex_diag(const SubOp &so, double *diag, hipStream_t s);
 void launch_rt_hex_apply(const SubOp &so, const double *x, bool masked, hipStream_t s);
 void launch_rt_hex_qdata(SubOp &so, hipStream_t s);
 void launch_rt_hex_diag(const SubOp &so, double *diag, hipStream_t s);
+// two right-hand sides per pass (packed D, a compiled pair, PALACE_AMD_TWO_PART != 0): the E-vectors d_ye and d_ye2
+bool rt_hex_supports_two_rhs(const SubOp &so);
+void launch_rt_hex_apply2(SubOp &so, const double *x0, const double *x1, bool masked, hipStream_t s);
+// pa_capi.hip: false when PALACE_AMD_TWO_PART=0 keeps the two-part RT and two-space kernels out (two one-part passes instead)
+bool two_part_enabled();
 
 // pa_dense.hip
 void launch_geom_dense(const pa_mesh_dense_desc &mesh, Geom &g, hipStream_t s);
@@ -414,6 +419,10 @@ void launch_dense_diag(const DenseSub &ds, double *diag, hipStream_t s);
 void launch_et_gather_raw(int n, const int32_t *tptr, const int32_t *tent, const double *ye, double *y,
                           bool accumulate, hipStream_t s, const int32_t *list = nullptr, const double *x = nullptr,
                           int ess_policy = -1);
+// the same for two E-vector / y pairs with one read of the transpose map (the summation order of the one-vector gather)
+void launch_et_gather2_raw(int n, const int32_t *tptr, const int32_t *tent, const double *ye0, const double *ye1, double *y0,
+                           double *y1, bool accumulate, hipStream_t s, const int32_t *list = nullptr, const double *x0 = nullptr,
+                           const double *x1 = nullptr, int ess_policy = -1);
 
 // pa_mixed.hip
 MixedSub *make_mixed_sub(pa_geom *geom, const pa_restriction_desc &r1, const pa_dense_basis_desc &b1,
@@ -431,6 +440,15 @@ MixedSub *make_mixed_hex_sub(pa_geom *geom, const pa_restriction_desc &r1, const
 void free_sub(SubOp *so);
 // pa_mixed_hex.hip: x1 -> the E-vector of the output block (apply; transpose: hex2 -> hex1) or x1, x2 -> out (error)
 void launch_mixed_hex(const MixedSub &ms, const double *x1, const double *x2, double *out, hipStream_t s, bool transpose);
+// both parts of a complex field in one launch (a compiled pair, PALACE_AMD_TWO_PART != 0)
+bool mixed_hex_two_part(const MixedSub &ms);
+void launch_mixed_hex2(const MixedSub &ms, const double *x1, const double *x2, const double *x1i, const double *x2i, double *out,
+                       hipStream_t s);
+// pa_mixed.hip: y0 = A x0, y1 = A x1 / estimates += eta^2(u1, u2) + eta^2(u1i, u2i); one launch where mixed_hex_two_part
+void launch_mixed_apply2(const MixedSub &ms, const double *x0, const double *x1, double *y0, double *y1, bool accumulate,
+                         hipStream_t s);
+void launch_mixed_error2(const MixedSub &ms, const double *u1, const double *u2, const double *u1i, const double *u2i, double *out,
+                         hipStream_t s);
 
 }  // namespace pa
 

@@ -580,6 +580,28 @@ void launch_mixed_apply(const MixedSub &ms, const double *x, double *y, bool acc
   launch_et_gather_raw(out.lsize, out.d_tptr, out.d_tent, transpose ? ms.d_ye_t : ms.d_ye, y, accumulate, s);
 }
 
+void launch_mixed_apply2(const MixedSub &ms, const double *x0, const double *x1, double *y0, double *y1, bool accumulate,
+                         hipStream_t s) {
+  PA_REQUIRE(!ms.error, "error integrators have no apply");
+  if (mixed_hex_two_part(ms)) {
+    launch_mixed_hex2(ms, x0, nullptr, x1, nullptr, nullptr, s);
+    const SubOp &ob = *ms.hex2;
+    launch_et_gather2_raw(ob.lsize, ob.d_tptr, ob.d_tent, ob.d_ye, ob.d_ye2, y0, y1, accumulate, s);
+    return;
+  }
+  launch_mixed_apply(ms, x0, y0, accumulate, s);
+  launch_mixed_apply(ms, x1, y1, accumulate, s);
+}
+
+// the two passes in the order of ComputeErrorEstimates (errorestimator.cpp:249-261): real parts, then imaginary parts
+void launch_mixed_error2(const MixedSub &ms, const double *u1, const double *u2, const double *u1i, const double *u2i, double *out,
+                         hipStream_t s) {
+  PA_REQUIRE(ms.error, "not an error integrator");
+  if (mixed_hex_two_part(ms)) return launch_mixed_hex2(ms, u1, u2, u1i, u2i, out, s);
+  launch_mixed_error(ms, u1, u2, out, s);
+  launch_mixed_error(ms, u1i, u2i, out, s);
+}
+
 void launch_mixed_error(const MixedSub &ms, const double *u1, const double *u2, double *out, hipStream_t s) {
   PA_REQUIRE(ms.error, "not an error integrator");
   if (ms.hex1) return launch_mixed_hex(ms, u1, u2, out, s, false);

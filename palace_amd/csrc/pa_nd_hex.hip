@@ -507,6 +507,15 @@ void launch_et_gather2(const SubOp &so, double *y0, double *y1, bool accumulate,
   PA_HIP(hipGetLastError());
 }
 
+void launch_et_gather2_raw(int n, const int32_t *tptr, const int32_t *tent, const double *ye0, const double *ye1, double *y0,
+                           double *y1, bool accumulate, hipStream_t s, const int32_t *list, const double *x0, const double *x1,
+                           int ess_policy) {
+  if (n == 0) return;
+  hipLaunchKernelGGL(et_gather2_kernel, dim3((n + 255) / 256), dim3(256), 0, s, n, tptr, tent, ye0, ye1, y0, y1,
+                     accumulate ? 1 : 0, list, x0, x1, ess_policy);
+  PA_HIP(hipGetLastError());
+}
+
 void launch_et_gather_raw(int n, const int32_t *tptr, const int32_t *tent, const double *ye, double *y,
                           bool accumulate, hipStream_t s, const int32_t *list, const double *x, int ess_policy) {
   const int bs = 256;
