@@ -365,7 +365,10 @@ int pa_par_op_mult_transpose(pa_par_op *A, const double *x, double *y);
  *     for these nodal tensor elements is the Kronecker product of two 1-D nodal interpolation
  *     matrices, which is what is passed:
  *       Ic [p_f+1][p_c+1]  coarse closed basis evaluated at the fine closed nodes
- *       Io [p_f][p_c]      coarse open basis evaluated at the fine open nodes (HCURL only)
+ *       Io [p_f][p_c]      coarse open basis evaluated at the fine open nodes (HCURL and HDIV; required there)
+ *     Two PA_FE_HDIV tensor descriptors on the same hexahedra, 1 <= p_c < p_f <= 5, give the Raviart-Thomas p-prolongation
+ *     (pa_prolong_rt_hex.hip): element sizes 3 p^2 (p+1), both restrictions sign-oriented (`orients`); component c takes Ic along
+ *     direction c and Io along the other two, the mirror image of the Nedelec block.  Two different element families are refused.
  *     In parallel the wrapper is ParOperator(P, coarse, fine, use_R = true) (fem/fespace.cpp): the
  *     coarse input is halo-prolongated, the fine output restricted to owned dofs. */
 int pa_interp_create(pa_context *ctx, const pa_restriction_desc *coarse_restr,

@@ -93,21 +93,81 @@ void ErrorIndicator::AddIndicator(const Vector &indicator) {
 double ErrorIndicator::Norml2() const { return n_ ? std::sqrt(linalg::Dot(*ctx_, local_, local_)) : 0.0; }
 
 // ---- FluxProjector ---------------------------------------------------------------------------------------------------
+namespace {
+
+// the mass form of the smooth space (:117-131): MassIntegrator for a scalar space, VectorFEMassIntegrator else, no coefficient
+void add_mass_integrator(BilinearForm &m, bool scalar_flux) {
+  if (scalar_flux)
+    m.AddDomainIntegrator<MassIntegrator>((const MaterialPropertyCoefficient *)nullptr);
+  else
+    m.AddDomainIntegrator<VectorFEMassIntegrator>((const MaterialPropertyCoefficient *)nullptr);
+}
+
+void require_one_rank(const FiniteElementSpaceHierarchy &fespaces) {
+  for (std::size_t l = 0; l < fespaces.GetNumLevels(); l++)
+    PA_REQUIRE(!fespaces.GetFESpaceAtLevel(l).GetHalo(),
+               "the multigrid (use_mg) flux projector runs on one rank: a level of the smooth space has a halo (use_mg = false "
+               "takes spaces with halos)");
+}
+
+}  // namespace
+
+void FluxAmgSolver::SetOperator(const Operator &op) {
+  StreamGraph::Invalidate();
+  height = op.Height(), width = op.Width();
+  const auto *fop = dynamic_cast<const FespaceParOperator *>(&op);
+  const ParOperator *par = fop ? &fop->Par() : dynamic_cast<const ParOperator *>(&op);
+  PA_REQUIRE(par && !par->GetHalo(), "the flux projector's AMG needs the ParOperator of a level without a halo");
+  AmgOptions opt;
+  opt.theta = 0.8;  // errorestimator.cpp:82 ("more coarsening to save memory")
+  if (const auto *csr = dynamic_cast<const CsrOperator *>(&par->LocalOperator())) {
+    amg_ = std::make_unique<AmgSolver>(*ctx_, DownloadCsr(csr->Matrix()), opt);
+    return;
+  }
+  const auto *pa = dynamic_cast<const ceed::Operator *>(&par->LocalOperator());
+  PA_REQUIRE(pa, "the coarse operator is neither assembled nor a partially assembled operator");
+  const auto m = BilinearForm::FullAssemble(*pa, /*skip_zeros=*/false);
+  amg_ = std::make_unique<AmgSolver>(*ctx_, DownloadCsr(m->Matrix()), opt);
+}
+
+void FluxAmgSolver::Mult(const Vector &b, Vector &x) const {
+  PA_REQUIRE(amg_, "FluxAmgSolver: SetOperator first");
+  amg_->Mult(b, x);  // one cycle from a zero guess
+}
+
 FluxProjector::FluxProjector(const MaterialPropertyCoefficient &coeff, const FiniteElementSpace &smooth_fespace,
                              const FiniteElementSpace &rhs_fespace, double tol, int max_it, int print)
     : ctx_(&smooth_fespace.GetContext()), smooth_(&smooth_fespace), rhs_space_(&rhs_fespace) {
+  Init(coeff, nullptr, tol, max_it, print);
+}
+
+FluxProjector::FluxProjector(const MaterialPropertyCoefficient &coeff, const FiniteElementSpaceHierarchy &smooth_fespaces,
+                             const FiniteElementSpace &rhs_fespace, double tol, int max_it, int print, bool use_mg)
+    : ctx_(&smooth_fespaces.GetFinestFESpace().GetContext()), smooth_(&smooth_fespaces.GetFinestFESpace()), rhs_space_(&rhs_fespace) {
+  Init(coeff, use_mg ? &smooth_fespaces : nullptr, tol, max_it, print);
+}
+
+// smooth_fespaces: the hierarchy of the multigrid form, nullptr for use_mg = false
+void FluxProjector::Init(const MaterialPropertyCoefficient &coeff, const FiniteElementSpaceHierarchy *smooth_fespaces, double tol,
+                         int max_it, int print) {
+  const FiniteElementSpace &smooth_fespace = *smooth_, &rhs_fespace = *rhs_space_;
   PhaseRange range("Estimation / Construction");  // errorestimator.cpp:114
   // :117-120: a scalar smooth space (the H1 recovery of the scalar curl of a plane field) takes MassIntegrator
   const bool scalar_flux = smooth_fespace.GetFEType() == PA_FE_H1;
-  {  // errorestimator.cpp:125-153 (use_mg = false): the mass matrix of the smooth space, no coefficient
+  if (!smooth_fespaces) {  // errorestimator.cpp:125-153 (use_mg = false): the mass matrix of the smooth space, no coefficient
     BilinearForm m(smooth_fespace);
-    if (scalar_flux)
-      m.AddDomainIntegrator<MassIntegrator>((const MaterialPropertyCoefficient *)nullptr);
-    else
-      m.AddDomainIntegrator<VectorFEMassIntegrator>((const MaterialPropertyCoefficient *)nullptr);
+    add_mass_integrator(m, scalar_flux);
     mass_ = m.PartialAssemble();
     M_ = std::make_unique<ParOperator>(*ctx_, *mass_, smooth_fespace.GetTrueVSize(), nullptr, 0,
                                        ParOperator::DiagonalPolicy::DIAG_ONE, smooth_fespace.GetHalo());
+  } else {  // :136-147: one mass per level
+    require_one_rank(*smooth_fespaces);
+    BilinearForm m(smooth_fespace);
+    add_mass_integrator(m, scalar_flux);
+    auto m_vec = m.Assemble(*smooth_fespaces, /*skip_zeros=*/false);
+    M_mg_ = std::make_unique<MultigridOperator>(smooth_fespaces->GetNumLevels());
+    for (std::size_t l = 0; l < smooth_fespaces->GetNumLevels(); l++)
+      M_mg_->AddOperator(std::make_unique<FespaceParOperator>(std::move(m_vec[l]), smooth_fespaces->GetFESpaceAtLevel(l)));
   }
   {  // :154-176: the flux operator is always partially assembled
     BilinearForm flux(rhs_fespace, smooth_fespace);
@@ -118,14 +178,32 @@ FluxProjector::FluxProjector(const MaterialPropertyCoefficient &coeff, const Fin
     flux_ = flux.PartialAssemble();
   }
   // ConfigureLinearSolver (:66-107): the system matrix is real, SPD and diagonally dominant
-  pc_ = std::make_unique<JacobiSmoother>(*ctx_);
   pcg_ = std::make_unique<CgSolver>(*ctx_, print);
   pcg_->SetInitialGuess(false);
   pcg_->SetTol(tol);
   pcg_->SetAbsTol(std::numeric_limits<double>::epsilon());
   pcg_->SetMaxIter(max_it);
-  pcg_->SetOperator(*M_);
-  pc_->SetOperator(*M_);
+  if (!smooth_fespaces) {
+    pc_ = std::make_unique<JacobiSmoother>(*ctx_);
+    pcg_->SetOperator(*M_);
+    pc_->SetOperator(*M_);
+  } else {
+    const ParOperator &finest = M_mg_->GetFinestOperator().Par();  // (what MultigridOperator::Mult applies)
+    pcg_->SetOperator(finest);
+    auto amg = std::make_unique<FluxAmgSolver>(*ctx_);
+    if (smooth_fespaces->GetNumLevels() > 1) {  // :83-91
+      const int mg_smooth_order = 2;  // smooth order independent of the order of the space
+      auto mg = std::make_unique<GeometricMultigridSolver>(*ctx_, std::move(amg), smooth_fespaces->GetProlongationOperators(), 1, 1,
+                                                           mg_smooth_order, 1.0, 0.0, true, nullptr);
+      std::vector<const ParOperator *> ops;
+      for (std::size_t l = 0; l < M_mg_->GetNumLevels(); l++) ops.push_back(&M_mg_->GetOperatorAtLevel(l).Par());
+      mg->SetOperators(ops);
+      pc_ = std::move(mg);
+    } else {
+      amg->SetOperator(finest);
+      pc_ = std::move(amg);
+    }
+  }
   pcg_->SetPreconditioner(*pc_);
   rhs_.SetSize(smooth_fespace.GetTrueVSize());
   if (rhs_fespace.GetHalo()) lx_.SetSize(rhs_fespace.GetVSize());
@@ -156,6 +234,32 @@ void FluxProjector::Mult(const Vector &x, Vector &y) const {
 }
 
 // ---- estimators ------------------------------------------------------------------------------------------------------
+namespace {
+
+// the error integrator of two dense-table spaces or two tensor spaces on one mesh (both estimator bases)
+pa_error_op *make_error_op(const FiniteElementSpace &fespace, const FiniteElementSpace &smooth_fespace, int error_qf,
+                           const MaterialTensors &first, const MaterialTensors &second) {
+  PA_REQUIRE(fespace.IsDense() == smooth_fespace.IsDense() && &fespace.GetMesh() == &smooth_fespace.GetMesh(),
+             "the estimators take two dense-table spaces or two tensor spaces on one mesh");
+  PA_REQUIRE(first.dim == second.dim, "the two coefficients of an error integrator have one dimension");
+  const auto c1 = first.Coefficient(), c2 = second.Coefficient();
+  const auto ctx = ceed::PopulateCoefficientContext(first.dim, &c1, second.dim, &c2);
+  const auto r1 = fespace.GetCeedElemRestriction(), r2 = smooth_fespace.GetCeedElemRestriction();
+  pa_error_op *op = nullptr;
+  if (!fespace.IsDense()) {
+    const auto b1 = fespace.GetCeedBasis(), b2 = smooth_fespace.GetCeedBasis();
+    check(pa_error_op_create_tensor(fespace.GetMesh().GetCeedGeomFactorData(), &r1, &b1, &r2, &b2, error_qf, ctx.data(),
+                                    ctx.size() * sizeof(double), &op));
+  } else {
+    const auto b1 = fespace.GetCeedDenseBasis(), b2 = smooth_fespace.GetCeedDenseBasis();
+    check(pa_error_op_create(fespace.GetMesh().GetCeedGeomFactorData(), &r1, &b1, &r2, &b2, error_qf, ctx.data(),
+                             ctx.size() * sizeof(double), &op));
+  }
+  return op;
+}
+
+}  // namespace
+
 FluxErrorEstimatorBase::FluxErrorEstimatorBase(const FiniteElementSpace &fespace, const FiniteElementSpace &smooth_fespace,
                                                const MaterialPropertyCoefficient &flux_coeff, int error_qf,
                                                const MaterialTensors &first, const MaterialTensors &second, double tol,
@@ -177,6 +281,15 @@ FluxErrorEstimatorBase::FluxErrorEstimatorBase(const FiniteElementSpace &fespace
   const auto b1 = fespace.GetCeedDenseBasis(), b2 = smooth_fespace.GetCeedDenseBasis();
   check(pa_error_op_create(fespace.GetMesh().GetCeedGeomFactorData(), &r1, &b1, &r2, &b2, error_qf, ctx.data(),
                            ctx.size() * sizeof(double), &integ_op_));
+}
+
+FluxErrorEstimatorBase::FluxErrorEstimatorBase(const FiniteElementSpace &fespace, const FiniteElementSpaceHierarchy &smooth_fespaces,
+                                               const MaterialPropertyCoefficient &flux_coeff, int error_qf,
+                                               const MaterialTensors &first, const MaterialTensors &second, double tol,
+                                               int max_it, int print, bool use_mg)
+    : ctx_(&fespace.GetContext()), fespace_(fespace), smooth_fespace_(smooth_fespaces.GetFinestFESpace()),
+      projector_(flux_coeff, smooth_fespaces, fespace, tol, max_it, print, use_mg), G_(smooth_fespace_.GetTrueVSize()) {
+  integ_op_ = make_error_op(fespace, smooth_fespace_, error_qf, first, second);
 }
 
 FluxErrorEstimatorBase::~FluxErrorEstimatorBase() { pa_error_op_destroy(integ_op_); }
@@ -230,30 +343,24 @@ CurlFluxErrorEstimator::CurlFluxErrorEstimator(const MaterialTensors &muinv, con
                              muinv.Map([](const double *m) { return linalg::MatrixSqrt(m); }),
                              muinv.Map([](const double *m) { return linalg::MatrixPow(m, -0.5); }), tol, max_it, print) {}
 
+GradFluxErrorEstimator::GradFluxErrorEstimator(const MaterialTensors &epsilon, const FiniteElementSpace &nd_fespace,
+                                               const FiniteElementSpaceHierarchy &rt_fespaces, double tol, int max_it, int print,
+                                               bool use_mg)
+    : FluxErrorEstimatorBase(nd_fespace, rt_fespaces, epsilon.Coefficient(),
+                             nd_fespace.GetMesh().Dimension() == 2 ? PA_QF_HCURLHDIV_ERROR_22 : PA_QF_HCURLHDIV_ERROR_33,
+                             epsilon.Map([](const double *m) { return linalg::MatrixSqrt(m); }),
+                             epsilon.Map([](const double *m) { return linalg::MatrixPow(m, -0.5); }), tol, max_it, print, use_mg) {}
+
+CurlFluxErrorEstimator::CurlFluxErrorEstimator(const MaterialTensors &muinv, const FiniteElementSpace &rt_fespace,
+                                               const FiniteElementSpaceHierarchy &nd_fespaces, double tol, int max_it, int print,
+                                               bool use_mg)
+    : FluxErrorEstimatorBase(rt_fespace, nd_fespaces, muinv.Coefficient(),
+                             rt_fespace.GetMesh().Dimension() == 2 ? PA_QF_L2H1_ERROR : PA_QF_HDIVHCURL_ERROR_33,
+                             muinv.Map([](const double *m) { return linalg::MatrixSqrt(m); }),
+                             muinv.Map([](const double *m) { return linalg::MatrixPow(m, -0.5); }), tol, max_it, print, use_mg) {}
+
 // ---- the same for a ComplexVector -------------------------------------------------------------------------------------
 namespace {
-
-// the error integrator of two dense-table spaces or two tensor spaces on one mesh (both estimator bases)
-pa_error_op *make_error_op(const FiniteElementSpace &fespace, const FiniteElementSpace &smooth_fespace, int error_qf,
-                           const MaterialTensors &first, const MaterialTensors &second) {
-  PA_REQUIRE(fespace.IsDense() == smooth_fespace.IsDense() && &fespace.GetMesh() == &smooth_fespace.GetMesh(),
-             "the estimators take two dense-table spaces or two tensor spaces on one mesh");
-  PA_REQUIRE(first.dim == second.dim, "the two coefficients of an error integrator have one dimension");
-  const auto c1 = first.Coefficient(), c2 = second.Coefficient();
-  const auto ctx = ceed::PopulateCoefficientContext(first.dim, &c1, second.dim, &c2);
-  const auto r1 = fespace.GetCeedElemRestriction(), r2 = smooth_fespace.GetCeedElemRestriction();
-  pa_error_op *op = nullptr;
-  if (!fespace.IsDense()) {
-    const auto b1 = fespace.GetCeedBasis(), b2 = smooth_fespace.GetCeedBasis();
-    check(pa_error_op_create_tensor(fespace.GetMesh().GetCeedGeomFactorData(), &r1, &b1, &r2, &b2, error_qf, ctx.data(),
-                                    ctx.size() * sizeof(double), &op));
-  } else {
-    const auto b1 = fespace.GetCeedDenseBasis(), b2 = smooth_fespace.GetCeedDenseBasis();
-    check(pa_error_op_create(fespace.GetMesh().GetCeedGeomFactorData(), &r1, &b1, &r2, &b2, error_qf, ctx.data(),
-                             ctx.size() * sizeof(double), &op));
-  }
-  return op;
-}
 
 // true-dof vector -> L-vector through the halo: lv[0, n) = x, ghosts filled
 void to_lvector(const Context &ctx, const Halo &h, const Vector &x, Vector &lv) {
@@ -267,17 +374,40 @@ void to_lvector(const Context &ctx, const Halo &h, const Vector &x, Vector &lv) 
 ComplexFluxProjector::ComplexFluxProjector(const MaterialPropertyCoefficient &coeff, const FiniteElementSpace &smooth_fespace,
                                            const FiniteElementSpace &rhs_fespace, double tol, int max_it, int print)
     : ctx_(&smooth_fespace.GetContext()), smooth_(&smooth_fespace), rhs_space_(&rhs_fespace) {
+  Init(coeff, nullptr, tol, max_it, print);
+}
+
+ComplexFluxProjector::ComplexFluxProjector(const MaterialPropertyCoefficient &coeff, const FiniteElementSpaceHierarchy &smooth_fespaces,
+                                           const FiniteElementSpace &rhs_fespace, double tol, int max_it, int print, bool use_mg)
+    : ctx_(&smooth_fespaces.GetFinestFESpace().GetContext()), smooth_(&smooth_fespaces.GetFinestFESpace()), rhs_space_(&rhs_fespace) {
+  Init(coeff, use_mg ? &smooth_fespaces : nullptr, tol, max_it, print);
+}
+
+void ComplexFluxProjector::Init(const MaterialPropertyCoefficient &coeff, const FiniteElementSpaceHierarchy *smooth_fespaces, double tol,
+                                int max_it, int print) {
+  const FiniteElementSpace &smooth_fespace = *smooth_, &rhs_fespace = *rhs_space_;
   PhaseRange range("Estimation / Construction");
   const bool scalar_flux = smooth_fespace.GetFEType() == PA_FE_H1;
-  {
+  const ceed::Operator *finest_mass = nullptr;
+  const ComplexParOperator *finest_M = nullptr;
+  if (!smooth_fespaces) {
     BilinearForm m(smooth_fespace);
-    if (scalar_flux)
-      m.AddDomainIntegrator<MassIntegrator>((const MaterialPropertyCoefficient *)nullptr);
-    else
-      m.AddDomainIntegrator<VectorFEMassIntegrator>((const MaterialPropertyCoefficient *)nullptr);
+    add_mass_integrator(m, scalar_flux);
     mass_ = m.PartialAssemble();
     // BuildLevelParOperator<ComplexOperator> (:50-65): the real mass matrix as the real part, no imaginary part
     M_ = std::make_unique<ComplexParOperator>(*ctx_, mass_.get(), nullptr, smooth_fespace.GetTrueVSize(), smooth_fespace.GetHalo());
+    finest_mass = mass_.get(), finest_M = M_.get();
+  } else {  // :136-147
+    require_one_rank(*smooth_fespaces);
+    BilinearForm m(smooth_fespace);
+    add_mass_integrator(m, scalar_flux);
+    level_mass_ = m.Assemble(*smooth_fespaces, /*skip_zeros=*/false);
+    for (std::size_t l = 0; l < smooth_fespaces->GetNumLevels(); l++)
+      level_M_.push_back(std::make_unique<ComplexParOperator>(*ctx_, level_mass_[l].get(), nullptr,
+                                                              smooth_fespaces->GetFESpaceAtLevel(l).GetTrueVSize(), nullptr));
+    finest_mass = dynamic_cast<const ceed::Operator *>(level_mass_.back().get());
+    PA_REQUIRE(finest_mass, "the finest level of the flux projector's hierarchy is partially assembled");
+    finest_M = level_M_.back().get();
   }
   {
     BilinearForm flux(rhs_fespace, smooth_fespace);
@@ -287,14 +417,30 @@ ComplexFluxProjector::ComplexFluxProjector(const MaterialPropertyCoefficient &co
       flux.AddDomainIntegrator<VectorFEMassIntegrator>(coeff);
     flux_ = flux.PartialAssemble();
   }
-  pc_ = std::make_unique<ComplexJacobiSmoother>(*ctx_);
   pcg_ = std::make_unique<ComplexCgSolver>(*ctx_, print);
   pcg_->SetTol(tol);
   pcg_->SetAbsTol(std::numeric_limits<double>::epsilon());
   pcg_->SetMaxIter(max_it);
-  Mboth_ = std::make_unique<ComplexMassOperator>(*mass_, *M_, smooth_fespace.GetHalo() != nullptr);
+  Mboth_ = std::make_unique<ComplexMassOperator>(*finest_mass, *finest_M, smooth_fespace.GetHalo() != nullptr);
   pcg_->SetOperator(*Mboth_);
-  pc_->SetOperator(*M_);
+  if (!smooth_fespaces) {
+    pc_ = std::make_unique<ComplexJacobiSmoother>(*ctx_);
+    pc_->SetOperator(*M_);
+  } else {
+    amg_ = std::make_unique<FluxAmgSolver>(*ctx_);
+    auto coarse = std::make_unique<ComplexWrapperSolver>(*amg_);
+    if (smooth_fespaces->GetNumLevels() > 1) {
+      auto mg = std::make_unique<ComplexGeometricMultigridSolver>(*ctx_, std::move(coarse), smooth_fespaces->GetProlongationOperators(),
+                                                                  1, 1, /*mg_smooth_order=*/2, 1.0, 0.0, true, nullptr);
+      std::vector<const ComplexParOperator *> ops;
+      for (const auto &M : level_M_) ops.push_back(M.get());
+      mg->SetOperators(ops);
+      pc_ = std::move(mg);
+    } else {
+      coarse->SetOperator(*finest_M);
+      pc_ = std::move(coarse);
+    }
+  }
   pcg_->SetPreconditioner(*pc_);
   rhs_.SetSize(smooth_fespace.GetTrueVSize());
   if (rhs_fespace.GetHalo()) lx_.SetSize(rhs_fespace.GetVSize());
@@ -349,6 +495,17 @@ ComplexFluxErrorEstimatorBase::ComplexFluxErrorEstimatorBase(const FiniteElement
   integ_op_ = make_error_op(fespace, smooth_fespace, error_qf, first, second);
 }
 
+ComplexFluxErrorEstimatorBase::ComplexFluxErrorEstimatorBase(const FiniteElementSpace &fespace,
+                                                             const FiniteElementSpaceHierarchy &smooth_fespaces,
+                                                             const MaterialPropertyCoefficient &flux_coeff, int error_qf,
+                                                             const MaterialTensors &first, const MaterialTensors &second,
+                                                             double tol, int max_it, int print, bool use_mg)
+    : ctx_(&fespace.GetContext()), fespace_(fespace), smooth_fespace_(smooth_fespaces.GetFinestFESpace()),
+      projector_(flux_coeff, smooth_fespaces, fespace, tol, max_it, print, use_mg) {
+  G_.SetSize(smooth_fespace_.GetTrueVSize());
+  integ_op_ = make_error_op(fespace, smooth_fespace_, error_qf, first, second);
+}
+
 ComplexFluxErrorEstimatorBase::~ComplexFluxErrorEstimatorBase() { pa_error_op_destroy(integ_op_); }
 
 void ComplexFluxErrorEstimatorBase::AddErrorEstimates(const ComplexVector &F, Vector &estimates) const {
@@ -399,6 +556,32 @@ ComplexCurlFluxErrorEstimator::ComplexCurlFluxErrorEstimator(const MaterialTenso
                                     rt_fespace.GetMesh().Dimension() == 2 ? PA_QF_L2H1_ERROR : PA_QF_HDIVHCURL_ERROR_33,
                                     muinv.Map([](const double *m) { return linalg::MatrixSqrt(m); }),
                                     muinv.Map([](const double *m) { return linalg::MatrixPow(m, -0.5); }), tol, max_it, print) {}
+
+ComplexGradFluxErrorEstimator::ComplexGradFluxErrorEstimator(const MaterialTensors &epsilon, const FiniteElementSpace &nd_fespace,
+                                                             const FiniteElementSpaceHierarchy &rt_fespaces, double tol, int max_it,
+                                                             int print, bool use_mg)
+    : ComplexFluxErrorEstimatorBase(nd_fespace, rt_fespaces, epsilon.Coefficient(),
+                                    nd_fespace.GetMesh().Dimension() == 2 ? PA_QF_HCURLHDIV_ERROR_22 : PA_QF_HCURLHDIV_ERROR_33,
+                                    epsilon.Map([](const double *m) { return linalg::MatrixSqrt(m); }),
+                                    epsilon.Map([](const double *m) { return linalg::MatrixPow(m, -0.5); }), tol, max_it, print,
+                                    use_mg) {}
+
+ComplexCurlFluxErrorEstimator::ComplexCurlFluxErrorEstimator(const MaterialTensors &muinv, const FiniteElementSpace &rt_fespace,
+                                                             const FiniteElementSpaceHierarchy &nd_fespaces, double tol, int max_it,
+                                                             int print, bool use_mg)
+    : ComplexFluxErrorEstimatorBase(rt_fespace, nd_fespaces, muinv.Coefficient(),
+                                    rt_fespace.GetMesh().Dimension() == 2 ? PA_QF_L2H1_ERROR : PA_QF_HDIVHCURL_ERROR_33,
+                                    muinv.Map([](const double *m) { return linalg::MatrixSqrt(m); }),
+                                    muinv.Map([](const double *m) { return linalg::MatrixPow(m, -0.5); }), tol, max_it, print,
+                                    use_mg) {}
+
+TimeDependentFluxErrorEstimator::TimeDependentFluxErrorEstimator(const MaterialTensors &epsilon, const MaterialTensors &muinv,
+                                                                 const FiniteElementSpaceHierarchy &nd_fespaces,
+                                                                 const FiniteElementSpaceHierarchy &rt_fespaces, double tol,
+                                                                 int max_it, int print, bool use_mg)
+    : ctx_(&nd_fespaces.GetFinestFESpace().GetContext()),
+      grad_(epsilon, nd_fespaces.GetFinestFESpace(), rt_fespaces, tol, max_it, print, use_mg),
+      curl_(muinv, rt_fespaces.GetFinestFESpace(), nd_fespaces, tol, max_it, print, use_mg) {}
 
 TimeDependentFluxErrorEstimator::TimeDependentFluxErrorEstimator(const MaterialTensors &epsilon, const MaterialTensors &muinv,
                                                                  const FiniteElementSpace &nd_fespace,

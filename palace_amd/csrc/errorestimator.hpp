@@ -18,6 +18,7 @@
 #include <memory>
 #include <vector>
 
+#include "amg_solver.hpp"
 #include "complex.hpp"
 #include "fem.hpp"
 #include "ksp.hpp"
@@ -72,19 +73,44 @@ struct MaterialTensors {
 };
 
 // errorestimator.hpp:34-58, .cpp:111-187: y = M^-1 Flux x with M the mass matrix of the smooth space and Flux the
-// coefficient-weighted mixed mass from the space of x into the smooth space; PCG + Jacobi (use_mg = false)
+// coefficient-weighted mixed mass from the space of x into the smooth space; PCG + Jacobi (use_mg = false), or PCG preconditioned
+// by a p-multigrid cycle over a hierarchy of the smooth space (use_mg = true, ConfigureLinearSolver :67-104): the system operator
+// is the MultigridOperator of the levels' masses, the cycle one pre and one post step of 4th-kind Chebyshev of order 2 and one
+// native AMG cycle (strength threshold 0.8) on the fully assembled coarsest level; a one-level hierarchy gets the AMG alone.
+// One rank.
+
+// BoomerAmgSolver(1, 1, true, 0) with SetStrengthThresh(0.8) as the projectors' coarse solve (:81-82): one cycle of the native
+// AMG on the assembled matrix of the level it is given (a ParOperator or FespaceParOperator without a halo)
+class FluxAmgSolver : public Solver {
+  const Context *ctx_;
+  std::unique_ptr<AmgSolver> amg_;
+
+public:
+  explicit FluxAmgSolver(const Context &ctx) : ctx_(&ctx) {}
+  void SetOperator(const Operator &op) override;
+  void Mult(const Vector &b, Vector &x) const override;
+  const AmgSolver *Amg() const { return amg_.get(); }
+};
+
 class FluxProjector {
   const Context *ctx_;
   std::unique_ptr<ceed::Operator> flux_, mass_;
   std::unique_ptr<ParOperator> M_;
-  std::unique_ptr<JacobiSmoother> pc_;
+  std::unique_ptr<MultigridOperator> M_mg_;  // use_mg: the masses of all levels
+  std::unique_ptr<Solver> pc_;
   std::unique_ptr<CgSolver> pcg_;
   const FiniteElementSpace *smooth_, *rhs_space_;
   mutable Vector rhs_, lx_, ly_;
+  void Init(const MaterialPropertyCoefficient &coeff, const FiniteElementSpaceHierarchy *smooth_fespaces, double tol, int max_it,
+            int print);
 
 public:
   FluxProjector(const MaterialPropertyCoefficient &coeff, const FiniteElementSpace &smooth_fespace,
                 const FiniteElementSpace &rhs_fespace, double tol, int max_it, int print);
+  FluxProjector(const MaterialPropertyCoefficient &coeff, const FiniteElementSpaceHierarchy &smooth_fespaces,
+                const FiniteElementSpace &rhs_fespace, double tol, int max_it, int print, bool use_mg);
+  bool UsesMultigrid() const { return M_mg_ != nullptr; }
+  bool Converged() const { return pcg_->GetConverged(); }
   void Mult(const Vector &x, Vector &y) const;
   int NumIterations() const { return pcg_->GetNumIterations(); }
 };
@@ -101,6 +127,9 @@ protected:
   FluxErrorEstimatorBase(const FiniteElementSpace &fespace, const FiniteElementSpace &smooth_fespace,
                          const MaterialPropertyCoefficient &flux_coeff, int error_qf, const MaterialTensors &first,
                          const MaterialTensors &second, double tol, int max_it, int print);
+  FluxErrorEstimatorBase(const FiniteElementSpace &fespace, const FiniteElementSpaceHierarchy &smooth_fespaces,
+                         const MaterialPropertyCoefficient &flux_coeff, int error_qf, const MaterialTensors &first,
+                         const MaterialTensors &second, double tol, int max_it, int print, bool use_mg);
 
 public:
   virtual ~FluxErrorEstimatorBase();
@@ -119,6 +148,9 @@ class GradFluxErrorEstimator : public FluxErrorEstimatorBase {
 public:
   GradFluxErrorEstimator(const MaterialTensors &epsilon, const FiniteElementSpace &nd_fespace,
                          const FiniteElementSpace &rt_fespace, double tol, int max_it, int print);
+  // errorestimator.cpp:272-280: the smooth space as a hierarchy (`rt_fespaces`), the projector's use_mg passed through
+  GradFluxErrorEstimator(const MaterialTensors &epsilon, const FiniteElementSpace &nd_fespace,
+                         const FiniteElementSpaceHierarchy &rt_fespaces, double tol, int max_it, int print, bool use_mg);
 };
 
 // eta_e^2 = || mu^1/2 H - mu^-1/2 B ||^2_e with H the ND recovery of mu^-1 B (B in RT).  Plane problems: B = curl E is a scalar
@@ -127,6 +159,9 @@ class CurlFluxErrorEstimator : public FluxErrorEstimatorBase {
 public:
   CurlFluxErrorEstimator(const MaterialTensors &muinv, const FiniteElementSpace &rt_fespace,
                          const FiniteElementSpace &nd_fespace, double tol, int max_it, int print);
+  // errorestimator.cpp:394-398 (`nd_fespaces`)
+  CurlFluxErrorEstimator(const MaterialTensors &muinv, const FiniteElementSpace &rt_fespace,
+                         const FiniteElementSpaceHierarchy &nd_fespaces, double tol, int max_it, int print, bool use_mg);
 };
 
 // FluxProjector<ComplexVector> (errorestimator.cpp:111-187): the same two forms; M is a ComplexParOperator with a real part only
@@ -151,21 +186,33 @@ public:
   long OnePassApplies() const { return one_pass_applies_; }   // how often it took the one-pass route
 };
 
+// use_mg: the levels' masses as ComplexParOperators with a real part only, a ComplexGeometricMultigridSolver with complex Chebyshev
+// smoothers and the real FluxAmgSolver wrapped for both parts (MfemWrapperSolver<ComplexOperator>) as coarse solve; the PCG still
+// applies the finest mass through ComplexMassOperator (one pass where there is one)
 class ComplexFluxProjector {
   const Context *ctx_;
   std::unique_ptr<ceed::Operator> flux_, mass_;
+  std::vector<std::unique_ptr<Operator>> level_mass_;          // use_mg: the local masses of all levels, finest last
+  std::vector<std::unique_ptr<ComplexParOperator>> level_M_;   // ... and their complex ParOperators
   std::unique_ptr<ComplexParOperator> M_;
   std::unique_ptr<ComplexMassOperator> Mboth_;
-  std::unique_ptr<ComplexJacobiSmoother> pc_;
+  std::unique_ptr<FluxAmgSolver> amg_;
+  std::unique_ptr<ComplexSolver> pc_;
   std::unique_ptr<ComplexCgSolver> pcg_;
   const FiniteElementSpace *smooth_, *rhs_space_;
   mutable ComplexVector rhs_, lx_, ly_;
+  void Init(const MaterialPropertyCoefficient &coeff, const FiniteElementSpaceHierarchy *smooth_fespaces, double tol, int max_it,
+            int print);
 
 public:
   ComplexFluxProjector(const MaterialPropertyCoefficient &coeff, const FiniteElementSpace &smooth_fespace,
                        const FiniteElementSpace &rhs_fespace, double tol, int max_it, int print);
+  ComplexFluxProjector(const MaterialPropertyCoefficient &coeff, const FiniteElementSpaceHierarchy &smooth_fespaces,
+                       const FiniteElementSpace &rhs_fespace, double tol, int max_it, int print, bool use_mg);
   void Mult(const ComplexVector &x, ComplexVector &y) const;
   int NumIterations() const { return pcg_->GetNumIterations(); }
+  bool UsesMultigrid() const { return !level_M_.empty(); }
+  bool Converged() const { return pcg_->GetConverged(); }
   bool FluxTwoRhs() const;  // the flux operator takes both parts in one pass over the element data (pa_op_two_rhs)
   bool MassTwoRhs() const { return Mboth_->OnePass(); }  // ... and so does the mass apply inside the PCG (the route taken)
   long MassOnePassApplies() const { return Mboth_->OnePassApplies(); }  // mass applies that went through Mult2 so far
@@ -184,6 +231,9 @@ protected:
   ComplexFluxErrorEstimatorBase(const FiniteElementSpace &fespace, const FiniteElementSpace &smooth_fespace,
                                 const MaterialPropertyCoefficient &flux_coeff, int error_qf, const MaterialTensors &first,
                                 const MaterialTensors &second, double tol, int max_it, int print);
+  ComplexFluxErrorEstimatorBase(const FiniteElementSpace &fespace, const FiniteElementSpaceHierarchy &smooth_fespaces,
+                                const MaterialPropertyCoefficient &flux_coeff, int error_qf, const MaterialTensors &first,
+                                const MaterialTensors &second, double tol, int max_it, int print, bool use_mg);
 
 public:
   virtual ~ComplexFluxErrorEstimatorBase();
@@ -200,12 +250,16 @@ class ComplexGradFluxErrorEstimator : public ComplexFluxErrorEstimatorBase {
 public:
   ComplexGradFluxErrorEstimator(const MaterialTensors &epsilon, const FiniteElementSpace &nd_fespace,
                                 const FiniteElementSpace &rt_fespace, double tol, int max_it, int print);
+  ComplexGradFluxErrorEstimator(const MaterialTensors &epsilon, const FiniteElementSpace &nd_fespace,
+                                const FiniteElementSpaceHierarchy &rt_fespaces, double tol, int max_it, int print, bool use_mg);
 };
 
 class ComplexCurlFluxErrorEstimator : public ComplexFluxErrorEstimatorBase {
 public:
   ComplexCurlFluxErrorEstimator(const MaterialTensors &muinv, const FiniteElementSpace &rt_fespace,
                                 const FiniteElementSpace &nd_fespace, double tol, int max_it, int print);
+  ComplexCurlFluxErrorEstimator(const MaterialTensors &muinv, const FiniteElementSpace &rt_fespace,
+                                const FiniteElementSpaceHierarchy &nd_fespaces, double tol, int max_it, int print, bool use_mg);
 };
 
 // :512-541: both of the above added before the square root (real in the reference)
@@ -218,6 +272,10 @@ public:
   TimeDependentFluxErrorEstimator(const MaterialTensors &epsilon, const MaterialTensors &muinv,
                                   const FiniteElementSpace &nd_fespace, const FiniteElementSpace &rt_fespace, double tol,
                                   int max_it, int print);
+  // :512-520: both hierarchies, the finest spaces carry the fields
+  TimeDependentFluxErrorEstimator(const MaterialTensors &epsilon, const MaterialTensors &muinv,
+                                  const FiniteElementSpaceHierarchy &nd_fespaces, const FiniteElementSpaceHierarchy &rt_fespaces,
+                                  double tol, int max_it, int print, bool use_mg);
   void AddErrorIndicator(const Vector &E, const Vector &B, double Et, ErrorIndicator &indicator) const;
 };
 

@@ -516,7 +516,7 @@ const Operator &FiniteElementSpaceHierarchy::BuildProlongationAtLevel(std::size_
       PA_REQUIRE(mf.GetNumCorners() == 8 && mf.Dimension() == 3, "tensor blocks of hexahedra expected");
       PA_REQUIRE(f.GetFEType() == PA_FE_HCURL || f.GetFEType() == PA_FE_H1,
                  "refinement transfer of tensor spaces: H(curl) and H1 hexahedra only (a Raviart-Thomas space has no multigrid "
-                 "hierarchy here: its operators are assembled on one level)");
+                 "hierarchy over refined meshes here: its levels are orders on one mesh)");
       const bool hcurl = f.GetFEType() == PA_FE_HCURL;
       const std::vector<double> cp = fem::GaussLobatto(p + 1);
       std::vector<double> op, ow;
@@ -582,9 +582,11 @@ const Operator &FiniteElementSpaceHierarchy::BuildProlongationAtLevel(std::size_
                                            mid.data()));
     return *P_[l];
   }
-  PA_REQUIRE(c.IsDense() || ((c.GetFEType() == PA_FE_HCURL || c.GetFEType() == PA_FE_H1) && c.GetFEType() == f.GetFEType()),
-             "p-prolongation of tensor spaces: two H(curl) or two H1 spaces (a Raviart-Thomas space has no multigrid hierarchy "
-             "here: its operators are assembled on one level)");
+  PA_REQUIRE(c.IsDense() || c.GetFEType() == f.GetFEType(), "p-prolongation of tensor spaces: two H(curl), two H1 or two Raviart-Thomas spaces");
+  // Raviart-Thomas levels (pa_prolong_rt_hex.hip): the orders of a p-hierarchy, 1 <= p_c < p_f <= 5
+  PA_REQUIRE(c.IsDense() || c.GetFEType() != PA_FE_HDIV || c.GetMaxElementOrder() < f.GetMaxElementOrder(),
+             "p-prolongation of tensor Raviart-Thomas spaces needs increasing orders (a Raviart-Thomas space has no multigrid hierarchy "
+             "of equal-order levels here)");
   std::vector<double> Ic, Io, tmp, xc, wc, xf, wf;
   fem::LagrangeEval(fem::GaussLobatto(c.GetMaxElementOrder() + 1), fem::GaussLobatto(f.GetMaxElementOrder() + 1), Ic, tmp);
   fem::GaussLegendre(c.GetMaxElementOrder(), xc, wc);
@@ -857,7 +859,11 @@ std::vector<std::unique_ptr<Operator>> BilinearForm::Assemble(const FiniteElemen
   PA_REQUIRE(boundary_integs.empty(), "forms with boundary integrators are assembled level by level (one boundary view per level)");
   std::vector<std::unique_ptr<ceed::Operator>> pa_ops;
   for (std::size_t l = l0; l < fespaces.GetNumLevels(); l++) {
-    if (l > l0 && &fespaces.GetFESpaceAtLevel(l).GetMesh() == &fespaces.GetFESpaceAtLevel(l - 1).GetMesh())
+    // tensor H(div) levels are assembled each on its own space and the mesh's rule: P^T M_f P is that operator (the p-prolongation
+    // is an exact embedding), and pa_op_coarsen takes H(curl) and H1 operators only
+    const FiniteElementSpace &fes = fespaces.GetFESpaceAtLevel(l);
+    const bool own_level = !fes.IsDense() && fes.GetFEType() == PA_FE_HDIV;
+    if (!own_level && l > l0 && &fes.GetMesh() == &fespaces.GetFESpaceAtLevel(l - 1).GetMesh())
       pa_ops.push_back(ceed::CeedOperatorCoarsen(*pa_ops.back(), fespaces.GetFESpaceAtLevel(l)));
     else
       pa_ops.push_back(PartialAssemble(fespaces.GetFESpaceAtLevel(l), fespaces.GetFESpaceAtLevel(l)));

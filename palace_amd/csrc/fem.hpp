@@ -354,7 +354,8 @@ public:
   static std::unique_ptr<CsrMatrix> FullAssemble(const ceed::Operator &op, bool skip_zeros);
   std::unique_ptr<Operator> Assemble(bool skip_zeros) const;
   // one operator per level l0..L-1: the coarsest requested level is assembled, the others reuse its quadrature data
-  // through CeedOperatorCoarsen (bilinearform.cpp:153-201)
+  // through CeedOperatorCoarsen (bilinearform.cpp:153-201); the levels of a tensor H(div) hierarchy are assembled each on its own
+  // space (the same Galerkin operators)
   std::vector<std::unique_ptr<Operator>> Assemble(const FiniteElementSpaceHierarchy &fespaces, bool skip_zeros,
                                                   std::size_t l0 = 0) const;
 };

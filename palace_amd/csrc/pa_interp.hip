@@ -1040,8 +1040,12 @@ Operator *make_dense_interp_operator(const Context &ctx, const pa_restriction_de
 void launch_curl_hex(bool transpose, int p, int ne, const int32_t *lidx_nd, const int32_t *lidx_rt, const double *Dg, const double *Dg_dev,
                      const double *x, double *out, hipStream_t stream);
 
+// pa_prolong_rt_hex.hip: the p-prolongation RT(pc) -> RT(pf) on the index arrays of an InterpOperator of kind 0 between two H(div) spaces
+void launch_rt_prolong_hex(bool transpose, int pc, int pf, int ne, const int32_t *lidx_c, const int32_t *lidx_f, const double *Ic,
+                           const double *Io, const double *Ic_dev, const double *Io_dev, const double *x, double *out, hipStream_t stream);
+
 // The prolongation as an Operator on T-vectors: Mult coarse -> fine, MultTranspose fine -> coarse.
-// kind 0: p-prolongation within one element family; 1: discrete gradient H1(p) -> ND(p); 2: discrete curl ND(p) -> RT(p) (the
+// kind 0: p-prolongation within one element family (H(curl), H1, or H(div) through pa_prolong_rt_hex.hip); 1: discrete gradient H1(p) -> ND(p); 2: discrete curl ND(p) -> RT(p) (the
 // "coarse" side is the domain, the "fine" side the range)
 class InterpOperator : public Operator {
   const Context *ctx_;
@@ -1058,6 +1062,10 @@ class InterpOperator : public Operator {
   void launch(const double *x, double *y) const {
     if (kind_ == 2) {
       launch_curl_hex(TR, pf_, ne_, d_lidx_c_, d_lidx_f_, h_Io_.data(), d_Io_, x, TR ? d_ye_c_ : y, ctx_->stream);
+      return;
+    }
+    if (fe_type_ == PA_FE_HDIV) {
+      launch_rt_prolong_hex(TR, pc_, pf_, ne_, d_lidx_c_, d_lidx_f_, h_Ic_.data(), h_Io_.data(), d_Ic_, d_Io_, x, TR ? d_ye_c_ : y, ctx_->stream);
       return;
     }
     InterpArgs a{kind_, ne_, fe_type_, pc_, pf_, d_lidx_c_, d_lidx_f_, d_Ic_, d_Io_, x, y, d_ye_c_, {}, {}};
@@ -1106,18 +1114,29 @@ public:
       PA_REQUIRE(Io, "discrete curl: the 1-D derivative matrix is missing");
     } else {
       PA_REQUIRE(bc.fe_type == bf.fe_type, "prolongation needs the same element family on both levels");
+      if (bc.fe_type == PA_FE_HDIV) {
+        PA_REQUIRE(bc.order >= 1 && bc.order < bf.order && bf.order + 1 <= kMaxN, "unsupported orders for prolongation: Raviart-Thomas levels need 1 <= p_c < p_f <= 5");
+        PA_REQUIRE(!rc.curl_orients && !rf.curl_orients, "Raviart-Thomas prolongation on tensor hexahedra takes sign orientations, not curl_orients");
+        PA_REQUIRE(Io, "Raviart-Thomas prolongation: the open 1-D interpolation matrix Io is missing");
+      }
     }
     PA_REQUIRE(rc.num_elem == rf.num_elem, "prolongation needs the same mesh on both levels");
     PA_REQUIRE(pf_ + 1 <= kMaxN && pc_ <= pf_, "unsupported orders for prolongation");
     PA_REQUIRE((Ic || kind == 2) && (kind == 0 && fe_type_ == PA_FE_H1 ? true : Io != nullptr), "1-D interpolation matrices missing");
     PA_REQUIRE(nt_c <= nl_c_ && nt_f <= nl_f_, "true dof counts exceed local sizes");
     PA_REQUIRE(halo_c || nt_c == nl_c_, kind == 2 ? "ghost dofs on the Nedelec side need a halo plan" : "ghost dofs on the coarse level need a halo plan");
-    const int Pc = bc.fe_type == PA_FE_HCURL ? 3 * pc_ * (pc_ + 1) * (pc_ + 1) : (pc_ + 1) * (pc_ + 1) * (pc_ + 1);
+    const int Pc = bc.fe_type == PA_FE_HCURL  ? 3 * pc_ * (pc_ + 1) * (pc_ + 1)
+                   : bc.fe_type == PA_FE_HDIV ? 3 * pc_ * pc_ * (pc_ + 1)
+                                              : (pc_ + 1) * (pc_ + 1) * (pc_ + 1);
     const int Pf = bf.fe_type == PA_FE_HCURL  ? 3 * pf_ * (pf_ + 1) * (pf_ + 1)
                    : bf.fe_type == PA_FE_HDIV ? 3 * pf_ * pf_ * (pf_ + 1)
                                               : (pf_ + 1) * (pf_ + 1) * (pf_ + 1);
     PA_REQUIRE(rc.elem_size == Pc && rf.elem_size == Pf, "restriction sizes do not match the bases");
     auto lc = signed_lex_index(rc, bc, Pc), lf = signed_lex_index(rf, bf, Pf);
+    if (kind == 0 && fe_type_ == PA_FE_HDIV) {
+      for (const int32_t sg : lc) PA_REQUIRE((sg >= 0 ? sg : -1 - sg) < nl_c_, "coarse offset out of range");
+      for (const int32_t sg : lf) PA_REQUIRE((sg >= 0 ? sg : -1 - sg) < nl_f_, "fine offset out of range");
+    }
     PA_REQUIRE(nl_f_ < kOwnBit, "too many fine dofs for the owner-flag encoding");
     {  // owner copy of every fine dof = its first occurrence in element order
       std::vector<char> seen((size_t)nl_f_, 0);
