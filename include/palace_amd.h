@@ -436,6 +436,12 @@ int pa_op_streams(const pa_op *op);
  * Jacobian, gate 1e-13).  out[0] elements, out[1] affine elements found, out[2] of them in all-affine batches (compressed);
  * first tensor H(curl) sub-operator; all zero when there is none or the form is off (PALACE_AMD_STREAM_AFFINE=0). */
 int pa_op_stream_affine(const pa_op *op, int32_t out[3]);
+/* Column form of the same kernel: an element extruded along its local zeta axis (x, y independent of zeta, z linear in it) has
+ * D_c(qx, qy, qz) = wz(qz) r_c(qx, qy), and a lane of the kernel owns one column (qx, qy): 8 bytes per component and lane instead of
+ * 32.  Batches of four such elements that are not all-affine read compact rows (detected from the q-data with the affine gate).
+ * out[0] elements, out[1] column-separable elements found (affine ones included), out[2] elements in column batches; first
+ * tensor H(curl) sub-operator; out[1] = out[2] = 0 when the form is off (PALACE_AMD_STREAM_COLUMN=0). */
+int pa_op_stream_column(const pa_op *op, int32_t out[3]);
 /* The E^T gather of the first dense-table sub-operator (round 6): out[0] = 1 if its E-vector keeps the dofs of an ELEMENT together
  * (chosen at creation by counting the 64-byte sectors the gather would read in either layout; PALACE_AMD_DENSE_ELAYOUT=rows | block
  * overrides), 0 for the rows by dof; out[1] = lanes that share the copies of one dof (1, 2, 4, 8: near the average number of copies;

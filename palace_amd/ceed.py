@@ -503,6 +503,13 @@ class Operator:
         _lib.check(_lib.load().pa_op_stream_affine(self.handle, out))
         return int(out[0]), int(out[1]), int(out[2])
 
+    def stream_column(self):
+        """(elements, column-separable elements, elements in column batches) of the streaming H(curl) hex kernel
+        (pa_op_stream_column)."""
+        out = (C.c_int32 * 3)()
+        _lib.check(_lib.load().pa_op_stream_column(self.handle, out))
+        return int(out[0]), int(out[1]), int(out[2])
+
     def dense_gather_form(self):
         """(E-vector rows by element?, lanes per dof) of the first dense-table block's E^T gather (pa_op_dense_gather_form)."""
         out = (C.c_int32 * 2)()

@@ -160,6 +160,18 @@ struct QData {
   bool aff_done = false;
   int n_aff_elems = 0, n_aff_batch_elems = 0;  // affine elements found / of them in all-affine batches (compressed)
   double wq2[2] = {0.0, 0.0};                  // the two distinct 1-D weights (symmetric four-point rule)
+  // Column-separable elements (extruded along the local zeta axis: x, y independent of zeta, z linear in it): every component
+  // factors as D_c(ta, tb, qz) = wz(qz) r_c(ta, tb) (metric component 6: r / wz(qz)), and lane (ta, tb) of the streaming kernel
+  // owns exactly the column qz = 0..3 -- one number per component and lane instead of four.  d_col [ne padded to 4][ncomp][16]
+  // doubles (+ 8 of padding: the kernel's second request of a component reads 64 bytes further, unused): r_c(t), the mean over
+  // the column of D_c / wz (component 6: of D_6 wz); the kernel multiplies it by wz(qz) (component 6: by 1 / wz(qz)) in registers
+  // ahead of its D stage.  batch_col[b] != 0: the four elements of batch b are all column-separable
+  // and the batch is not all-affine (those keep the smaller affine rows): 4 x ncomp x 128 B instead of 4 x ncomp x 512 B.
+  // Separability along the other two local axes is not looked for.  Built with the affine rows by stream_affine_setup;
+  // PALACE_AMD_STREAM_COLUMN=0 switches the form off.  The per-point data stays in place for every other consumer.
+  double *d_col = nullptr;
+  std::vector<unsigned char> batch_col;
+  int n_col_elems = 0, n_col_batch_elems = 0;  // column-separable elements found (affine ones included) / in column batches
 };
 
 // Offset of component c at point q inside one element's block of packed q-data (H(curl) hexahedra).  In general

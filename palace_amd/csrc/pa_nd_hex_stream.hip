@@ -82,7 +82,11 @@ struct NDStreamArgs {
   const double *qdata;    // [ne][NG][2][16][2]
   const double *qaff;     // [ne][2 NG] pairs: the compact D of affine elements (QData::d_aff); read by the batches whose flag words
                           // carry kAffBit (all four elements affine) instead of qdata
-  double wq2[2];          // 1-D quadrature weights {w(0) = w(3), w(1) = w(2)}: the in-plane factor of an affine batch's D
+  const double *qcol;     // [ne][ncomp][16]: the compact D of column-separable elements (QData::d_col), one number per component and lane;
+                          // read by the batches whose flag words carry kColBit instead of qdata
+  double wq2[2];          // 1-D quadrature weights {w(0) = w(3), w(1) = w(2)}: the in-plane factor of an affine batch's D, the factor
+                          // along the column of a column batch's
+  double wqi2[2];         // their reciprocals (column batches of the metric form: component 6 is r / wz)
   const double *coef;     // metric form: [ne][2] scalar mass / curl-curl coefficient of the element
   // GEOMN form (geometry from the nodes): [ne][27][3] node coordinates, {B [4][3], G [4][3], w [4]} of the 1-D geometry basis
   const double *xn, *gtab;
@@ -130,6 +134,8 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, MINW) void nd_hex_stream_kerne
   constexpr int Q1 = 4;
   // affine batches (round 6): D(q) = w_q D_e read from the compact rows of QData::d_aff (same number of loads, 16 bytes per row
   // for the whole element instead of per lane) and the D stage's result scaled by the in-plane weight; real forms on packed data
+  // column batches (extruded elements): D(ta, tb, qz) = wz(qz) r(ta, tb) read from the compact rows of QData::d_col (same number of
+  // loads; 8 bytes per component and lane, fetched as the aligned 16 bytes that hold them) and multiplied by wz(qz) ahead of the D stage
   constexpr bool AFF = (!CPLX || METRIC) && !GEOMN && !(PA_STREAM_QAHEAD && MINW == 2);
 #ifdef PA_STREAM_EARLY  // experiment builds
   constexpr bool EARLY_IDX = true;
@@ -236,15 +242,18 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, MINW) void nd_hex_stream_kerne
 #pragma unroll
     for (int r = 0; r < (GEOMN ? 6 : 1); r++) xl[r] = (t + 16 * r < 81) ? __builtin_nontemporal_load(&xp[t + 16 * r]) : 0.0;
   };
-  auto load_q = [&](const int ee, const int t, const int aff) {
+  auto load_q = [&](const int ee, const int t, const int kind) {  // kind: 2 affine batch, 1 column batch, 0 per-point data
     if (GEOMN) return load_xn(ee, t);  // (the nodes of the batch: consumed in its D stage)
     if (AFF && !(CPLX && !METRIC)) {
-      // one instruction stream for both kinds of batch (the counted waits below depend on the number of loads in flight): the
-      // wave-uniform flag selects the base, the lane offset and the row stride
+      // one instruction stream for the three kinds of batch (the counted waits below depend on the number of loads in flight): the
+      // wave-uniform kind selects the base, the lane offset and the row stride.  Column batches: a component's 16 numbers are 8 pairs,
+      // 128 bytes; row 2 c fetches the pair that holds r_c(t), row 2 c + 1 lands 64 bytes further (the second half of the same
+      // line or the first half of the next component's, 64 bytes of padding behind the last element) and is not used
       constexpr int NS = METRIC ? 7 : NG;
-      const int rs = aff ? 1 : 16;
-      const d2v *g = aff ? reinterpret_cast<const d2v *>(a.qaff) + (size_t)ee * (2 * NS)
-                         : reinterpret_cast<const d2v *>(a.qdata) + ((size_t)ee * (2 * NS * 16) + t);
+      const int rs = kind == 2 ? 1 : (kind == 1 ? 4 : 16);
+      const d2v *g = kind == 2   ? reinterpret_cast<const d2v *>(a.qaff) + (size_t)ee * (2 * NS)
+                     : kind == 1 ? reinterpret_cast<const d2v *>(a.qcol) + ((size_t)ee * (NS * 8) + (t >> 1))
+                                 : reinterpret_cast<const d2v *>(a.qdata) + ((size_t)ee * (2 * NS * 16) + t);
 #pragma unroll
       for (int k = 0; k < 2 * NG; k++) gq[k] = __builtin_nontemporal_load(&g[rs * k]);
       return;
@@ -279,8 +288,10 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, MINW) void nd_hex_stream_kerne
     PA_STAMP(0);
     // lane constants are re-derived from an opaque copy of the lane id in every iteration: hoisted out of the loop, the
     // few dozen LDS addresses and predicates of the passes stay live across it and end up in scratch memory
-    int lo = lane;
-    asm volatile("" : "+v"(lo));
+    // (the lane id itself is recomputed, not copied: one register less live across the batch -- the p = 3 curl-curl kernels sit at
+    // the 168 registers of three waves per SIMD, and a spilled lane id is reloaded behind a wait for every load in flight)
+    int lo;
+    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lo));
     const int sub = lo >> 4, t = lo & 15, ta = t & 3, tb = t >> 2;
     double *sm = smem + (size_t)(wave * 4 + sub) * LDS_ELEM;
     int *side = reinterpret_cast<int *>(sm + L::ELEM_PAD);  // index words of this batch, kept for the E^T stores
@@ -295,8 +306,9 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, MINW) void nd_hex_stream_kerne
     const int e = CPLX ? b * 2 + (sub >> 1) : b * 4 + sub;
 
     // q-data of this batch: consumed after the forward contraction
-    const int aff = AFF ? __builtin_amdgcn_readfirstlane((int)(pA[NPK] >> 31)) : 0;  // (the same for the 64 lanes: build_stream)
-    if (!QAHEAD) load_q(e, t, aff);
+    const int kind = AFF ? __builtin_amdgcn_readfirstlane((int)(pA[NPK] >> 30)) : 0;  // (the same for the 64 lanes: build_stream)
+    const int aff = kind >> 1, col = kind & 1;
+    if (!QAHEAD) load_q(e, t, kind);
     d2v ce = {0.0, 0.0}, ci = {0.0, 0.0};
     if (METRIC || GEOMN) ce = reinterpret_cast<const d2v *>(a.coef)[e];
     if (CPLX && METRIC) ci = reinterpret_cast<const d2v *>(a.coef1)[e];
@@ -414,6 +426,20 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, MINW) void nd_hex_stream_kerne
     double wab = 1.0;  // affine batch: the in-plane weight w(ta) w(tb) its compact D leaves out (1: exact no-op otherwise)
     double wxy = 1.0;
     if (AFF) {
+      if (col) {
+        // (wave-uniform) the per-point values of the column from this lane's number of every component: r wz(qz), the metric form's
+        // component 6 r / wz(qz), into the places the per-point data is read from (wz(2) = wz(1), wz(3) = wz(0)).  Done here, where the
+        // weights are at hand for the in-plane factor: the D stage below is the same for every kind of batch and no scalar stays live
+        // across it (the p = 3 kernels have neither vector nor scalar registers to spare).
+        const bool odd = t & 1;
+#pragma unroll
+        for (int c = 0; c < NG; c++) {
+          const double r = odd ? gq[2 * c][1] : gq[2 * c][0];
+          const bool inv = METRIC && c == 6;
+          const double v0 = r * (inv ? a.wqi2[0] : a.wq2[0]), v1 = r * (inv ? a.wqi2[1] : a.wq2[1]);
+          gq[2 * c][0] = v0, gq[2 * c][1] = v1, gq[2 * c + 1][0] = v1, gq[2 * c + 1][1] = v0;
+        }
+      }
       const double wa = (ta == 0 || ta == 3) ? a.wq2[0] : a.wq2[1], wb = (tb == 0 || tb == 3) ? a.wq2[0] : a.wq2[1];
       wxy = wa * wb;
       wab = aff ? wxy : 1.0;
@@ -784,9 +810,14 @@ void stream_element_coefficients(SubOp &so) {
 // Component c is w_q r_c(q) (the metric form's component 6: r / w_q); the element is affine when every r_c is the same at the 64
 // points to `tol` relative to the largest |mean r| of its group of six (mass / curl-curl / metric matrix; component 6 on its own).
 // Writes the compact rows (means) and the flag.
+// Column-separable elements (col != nullptr): thread q = t + 16 qz, so the four points of lane t's column are the threads q ^ 16,
+// q ^ 32.  Component c is wz(qz) r_c(t) (component 6: r / wz); the element is column-separable when every r_c is the same along each
+// of its 16 columns to `tol` relative to the largest |column mean| of the group over the element.  An affine element is one by
+// construction.  Writes the column means [ncomp][16] and bit 1 of the flag (bit 0: affine).
 __global__ __launch_bounds__(64) void stream_affine_kernel(const int ne, const int ncomp, const int metric, const double *__restrict__ qd,
                                                            const double w0, const double w1, const double tol,
-                                                           double *__restrict__ aff, unsigned char *__restrict__ flag) {
+                                                           double *__restrict__ aff, double *__restrict__ col,
+                                                           unsigned char *__restrict__ flag) {
   const int e = blockIdx.x, q = threadIdx.x;
   if (e >= ne) return;
   auto w1d = [&](const int i) { return (i == 0 || i == 3) ? w0 : w1; };
@@ -799,18 +830,28 @@ __global__ __launch_bounds__(64) void stream_affine_kernel(const int ne, const i
     for (int m = 32; m >= 1; m >>= 1) v = fmax(v, __shfl_xor(v, m, 64));
     return v;
   };
-  bool ok = true;
+  const double wz = w1d(q >> 4);
+  bool ok = true, cok = true;
   for (int g0 = 0; g0 < ncomp; g0 += 6) {
     const int gn = min(6, ncomp - g0);
-    double mean[6], dev = 0.0, scale = 0.0;
+    double mean[6], dev = 0.0, scale = 0.0, cdev = 0.0, cscale = 0.0;
     for (int c = 0; c < gn; c++) {
       const double v = qd[(size_t)e * ncomp * 64 + nd_qd_offset(4, g0 + c, q)];
       const double r = (metric && g0 + c == 6) ? v * wq : v / wq;
       mean[c] = wave_sum(r) * (1.0 / 64.0);
       dev = fmax(dev, wave_max(fabs(r - mean[c])));
       scale = fmax(scale, fabs(mean[c]));
+      if (col) {
+        const double rc = (metric && g0 + c == 6) ? v * wz : v / wz;
+        double cm = rc + __shfl_xor(rc, 16, 64);  // (the same bits in the four threads of a column: both sums commute)
+        cm = (cm + __shfl_xor(cm, 32, 64)) * 0.25;
+        cdev = fmax(cdev, wave_max(fabs(rc - cm)));
+        cscale = fmax(cscale, wave_max(fabs(cm)));
+        if (q < 16) col[((size_t)e * ncomp + g0 + c) * 16 + q] = cm;
+      }
     }
     ok = ok && dev <= tol * scale;
+    cok = cok && cdev <= tol * cscale;
     if (q < 2 * gn) {  // row 2 c + h: {r wz(2h), r wz(2h + 1)}, component 6 of the metric form: r / wz
       const int c = q >> 1, h = q & 1;
       const bool inv = metric && g0 + c == 6;
@@ -821,45 +862,68 @@ __global__ __launch_bounds__(64) void stream_affine_kernel(const int ne, const i
       row[1] = inv ? m / w1d(2 * h + 1) : m * w1d(2 * h + 1);
     }
   }
-  if (q == 0) flag[e] = ok ? 1 : 0;
+  if (q == 0) flag[e] = (ok ? 1 : 0) | ((col && (cok || ok)) ? 2 : 0);
 }
 
 // Once per QData (the p-coarsened operators share it): which elements are affine, which batches of four consist of such
 // elements only, the compact rows.  PALACE_AMD_STREAM_AFFINE=0 switches the form off (A / B runs; read when the data is built).
+// The same for the column-separable elements (QData::d_col): batches of four such elements that are not all-affine;
+// PALACE_AMD_STREAM_COLUMN=0 switches that form off.
 static void stream_affine_setup(SubOp &so) {
   QData &qd = *so.qd;
   if (qd.aff_done) return;
   qd.aff_done = true;
   const bool enabled = !(getenv("PALACE_AMD_STREAM_AFFINE") && atoi(getenv("PALACE_AMD_STREAM_AFFINE")) == 0);
-  if (!enabled || so.q1d != 4 || (int)so.geom->w1.size() != 4) return;
+  const bool col_enabled = !(getenv("PALACE_AMD_STREAM_COLUMN") && atoi(getenv("PALACE_AMD_STREAM_COLUMN")) == 0);
+  if ((!enabled && !col_enabled) || so.q1d != 4 || (int)so.geom->w1.size() != 4) return;
   const std::vector<double> &w = so.geom->w1;
   if (w[0] != w[3] || w[1] != w[2]) return;  // (not a symmetric rule: keep the per-point data)
   const int ne = so.ne, nep = (ne + 3) & ~3;
   const size_t nrow = (size_t)nep * 2 * qd.ncomp * 2;
-  double *d_aff = nullptr;
+  const size_t ncol = col_enabled ? (size_t)nep * qd.ncomp * 16 + 8 : 0;  // (+ 8: QData::d_col)
+  double *d_aff = nullptr, *d_col = nullptr;
   unsigned char *d_flag = nullptr;
   PA_HIP(hipMalloc(&d_aff, nrow * sizeof(double)));
   PA_HIP(hipMemset(d_aff, 0, nrow * sizeof(double)));
+  if (col_enabled) {
+    PA_HIP(hipMalloc(&d_col, ncol * sizeof(double)));
+    PA_HIP(hipMemset(d_col, 0, ncol * sizeof(double)));
+  }
   PA_HIP(hipMalloc(&d_flag, (size_t)nep));
   PA_HIP(hipMemset(d_flag, 0, (size_t)nep));
   const double tol = getenv("PALACE_AMD_AFFINE_TOL") ? atof(getenv("PALACE_AMD_AFFINE_TOL")) : 1e-13;
   hipLaunchKernelGGL(stream_affine_kernel, dim3(ne), dim3(64), 0, nullptr, ne, qd.ncomp, qd.metric ? 1 : 0, qd.d, w[0], w[1], tol, d_aff,
-                     d_flag);
+                     d_col, d_flag);
   PA_HIP(hipGetLastError());
   std::vector<unsigned char> flag((size_t)nep, 0);
   PA_HIP(hipMemcpy(flag.data(), d_flag, (size_t)nep, hipMemcpyDeviceToHost));
   (void)hipFree(d_flag);
+  qd.wq2[0] = w[0], qd.wq2[1] = w[1];
   qd.batch_aff.assign((size_t)nep / 4, 0);
-  for (int e = 0; e < ne; e++) qd.n_aff_elems += flag[e];
-  for (int b = 0; b < nep / 4; b++)
-    if (flag[4 * b] && flag[4 * b + 1] && flag[4 * b + 2] && flag[4 * b + 3]) qd.batch_aff[b] = 1, qd.n_aff_batch_elems += 4;
+  if (enabled) {
+    for (int e = 0; e < ne; e++) qd.n_aff_elems += flag[e] & 1;
+    for (int b = 0; b < nep / 4; b++)
+      if (flag[4 * b] & flag[4 * b + 1] & flag[4 * b + 2] & flag[4 * b + 3] & 1) qd.batch_aff[b] = 1, qd.n_aff_batch_elems += 4;
+  }
+  if (col_enabled) {
+    qd.batch_col.assign((size_t)nep / 4, 0);
+    for (int e = 0; e < ne; e++) qd.n_col_elems += (flag[e] >> 1) & 1;
+    for (int b = 0; b < nep / 4; b++)
+      if ((flag[4 * b] & flag[4 * b + 1] & flag[4 * b + 2] & flag[4 * b + 3] & 2) && !qd.batch_aff[b])
+        qd.batch_col[b] = 1, qd.n_col_batch_elems += 4;
+    if (qd.n_col_batch_elems == 0) {
+      (void)hipFree(d_col);
+      qd.batch_col.clear();
+    } else {
+      qd.d_col = d_col;
+    }
+  }
   if (qd.n_aff_batch_elems == 0) {
     (void)hipFree(d_aff);
     qd.batch_aff.clear();
     return;
   }
   qd.d_aff = d_aff;
-  qd.wq2[0] = w[0], qd.wq2[1] = w[1];
 }
 
 // Index arrays of the streaming kernel and the run form of the transpose map (after finalize_exclusive: needs the
@@ -922,6 +986,10 @@ void build_stream(SubOp &so) {
       if (so.qd->batch_aff[b])
         for (size_t e = 4 * b; e < 4 * b + 4; e++)
           for (int t = 0; t < 16; t++) pp[(e * (npk + 1) + npk) * 16 + t] |= streamhost::kAffBit;
+    for (size_t b = 0; b < so.qd->batch_col.size(); b++)  // (column-separable and not all-affine: QData::d_col)
+      if (so.qd->batch_col[b])
+        for (size_t e = 4 * b; e < 4 * b + 4; e++)
+          for (int t = 0; t < 16; t++) pp[(e * (npk + 1) + npk) * 16 + t] |= streamhost::kColBit;
   }
   so.h_perm_s = pp;
   if (so.fe_type == PA_FE_HCURL && !wide_form(so)) {
@@ -1115,7 +1183,8 @@ static void launch_p(const SubOp &so, const double *x, double *y, bool masked, h
   a.flagw = all ? so.d_flagw_all : (masked ? so.d_flagw_bc : so.d_flagw);
   a.slots = so.d_slots;
   a.qdata = so.qd->d;
-  a.qaff = so.qd->d_aff, a.wq2[0] = so.qd->wq2[0], a.wq2[1] = so.qd->wq2[1];
+  a.qaff = so.qd->d_aff, a.qcol = so.qd->d_col, a.wq2[0] = so.qd->wq2[0], a.wq2[1] = so.qd->wq2[1];
+  if (so.qd->d_col) a.wqi2[0] = 1.0 / so.qd->wq2[0], a.wqi2[1] = 1.0 / so.qd->wq2[1];
 #ifdef PA_METRIC6
   if (so.geom->w1.size() == 4) a.wq2[0] = so.geom->w1[0], a.wq2[1] = so.geom->w1[1];
 #endif
@@ -1218,7 +1287,9 @@ static void launch_complex_p(const SubOp &sr, const SubOp &si, const double *xr,
   a.flagw = masked ? sr.d_flagw_bc : sr.d_flagw;
   a.slots = sr.d_slots;
   a.qdata = sr.qd->d;
-  if (sr.qd->metric) a.qaff = sr.qd->d_aff, a.wq2[0] = sr.qd->wq2[0], a.wq2[1] = sr.qd->wq2[1];  // (affine batches: the metric form)
+  if (sr.qd->metric)  // (affine and column batches: the metric form)
+    a.qaff = sr.qd->d_aff, a.qcol = sr.qd->d_col, a.wq2[0] = sr.qd->wq2[0], a.wq2[1] = sr.qd->wq2[1];
+  if (sr.qd->metric && sr.qd->d_col) a.wqi2[0] = 1.0 / sr.qd->wq2[0], a.wqi2[1] = 1.0 / sr.qd->wq2[1];
   a.coef = sr.d_coef_s, a.coef1 = si.d_coef_s;
   a.xn = nullptr, a.gtab = nullptr;
   a.x = xr, a.x1 = xi, a.y = yr, a.y1 = yi, a.ye = sr.d_ye, a.ye1 = ye_i;

@@ -44,6 +44,9 @@ constexpr int kIdxPattern = 11;
 // flag words (four-point H(curl) kernel): bits 0-17 flip / exclusive, 18-26 essential; bit 31: the element's batch is affine
 // (QData::batch_aff: the kernel reads the compact D of QData::d_aff)
 constexpr uint32_t kAffBit = 1u << 31;
+// bit 30: the element's batch is column-separable and not affine (QData::batch_col: the kernel reads the compact D of
+// QData::d_col); never set together with kAffBit
+constexpr uint32_t kColBit = 1u << 30;
 
 inline int index_dof(const uint32_t *ic, int m, int start0 = kIdxStart0) {  // host model of the device decode (gather lambdas)
   const int r = m >> 4, t = m & 15;
