@@ -1616,8 +1616,10 @@ class MixedCurlOperatorOracle:
 # ---- native coarse solvers: the cycles restated on host matrices (checker for palace_amd/csrc/amg_solver.hip) ---------------
 # The reference calls HYPRE here (linalg/amg.cpp:12-49, linalg/ams.cpp:18-224); HYPRE is not in /root/reference, so there is no
 # reference output to pin these on: "parity unpinned" for the coarse solvers themselves.  What IS checked: the device cycle
-# equals this restatement on the very hierarchy the library built (tests/test_ams_gpu.py, 1e-10), the preconditioners are
-# symmetric positive definite, and the preconditioned solves reproduce sparse direct solutions.
+# equals this restatement on the very hierarchy the library built (tests/test_ams_gpu.py, 1e-10; every cycle option and the
+# simplex families: tests/test_amg_cycle_options_gpu.py), the preconditioners are symmetric positive definite, and the
+# preconditioned solves reproduce sparse direct solutions.  The functions below work on scipy / numpy float64 matrices and, for
+# measuring their own rounding, on dense np.longdouble ones alike.
 
 def cheb4_l1(A, b, x, order, zero_guess):
     """4th-kind Chebyshev smoothing (chebyshev.cpp:190-220) on D_l1^-1 A with lambda_max = 1, D_l1 = diag(sum_j |a_ij|)."""
@@ -1637,8 +1639,14 @@ def cheb4_l1(A, b, x, order, zero_guess):
 
 
 def amg_vcycle(A, P, cinv, b, order=2, level=0):
-    """One V-cycle from a zero guess over the hierarchy (A[l], P[l]) with the dense inverse `cinv` on the last level."""
+    """One V-cycle from a zero guess over the hierarchy (A[l], P[l]) with the dense inverse `cinv` on the last level; cinv None
+    (a last level too large for the direct solve, AmgSolver::Cycle): one smoothing from a zero guess, then three more."""
     if level + 1 == len(A):
+        if cinv is None:
+            x = cheb4_l1(A[level], b, None, order, True)
+            for _ in range(3):
+                x = cheb4_l1(A[level], b, x, order, False)
+            return x
         return cinv @ b
     x = cheb4_l1(A[level], b, None, order, True)
     r = b - A[level] @ x
@@ -1647,21 +1655,24 @@ def amg_vcycle(A, P, cinv, b, order=2, level=0):
     return cheb4_l1(A[level], b, x, order, False)
 
 
-def ams_cycle(A, G, Pi, amg_G, amg_Pi, b, order=2, singular=False):
-    """HYPRE AMS cycle type 14 (ams.cpp:24-28: 0 1 (3 + 4 + 5) 1 0) from a zero guess: smoothing on A, gradient-space
-    correction, additive scalar nodal-space corrections (one block-diagonal solve), gradient space, smoothing.
-    amg_G / amg_Pi: callables applying the auxiliary-space solves."""
-    x = cheb4_l1(A, b, None, order, True)
+def ams_cycle(A, G, Pi, amg_G, amg_Pi, b, order=2, singular=False, cycle_it=1, x0=None):
+    """HYPRE AMS cycle type 14 (ams.cpp:24-28: 0 1 (3 + 4 + 5) 1 0): smoothing on A, gradient-space correction, additive scalar
+    nodal-space corrections (one block-diagonal solve), gradient space, smoothing -- `cycle_it` times, from a zero guess or from
+    the iterate `x0`.  amg_G / amg_Pi: callables applying the auxiliary-space solves."""
 
     def correct(T, B, x):
         return x + T @ B(T.T @ (b - A @ x))
 
-    if not singular:
-        x = correct(G, amg_G, x)
-    x = correct(Pi, amg_Pi, x)
-    if not singular:
-        x = correct(G, amg_G, x)
-    return cheb4_l1(A, b, x, order, False)
+    x = x0
+    for it in range(cycle_it):
+        x = cheb4_l1(A, b, x, order, it == 0 and x0 is None)
+        if not singular:
+            x = correct(G, amg_G, x)
+        x = correct(Pi, amg_Pi, x)
+        if not singular:
+            x = correct(G, amg_G, x)
+        x = cheb4_l1(A, b, x, order, False)
+    return x
 
 
 def ams_nodal_interpolation(G, coords, ess_flag):

@@ -1229,13 +1229,14 @@ void ParOperator::Mult(const Vector &x, Vector &y) const {
                        policy_ == DiagonalPolicy::DIAG_ONE ? 1 : 0, y.Data(), n_true_);
     return;
   }
-  linalg::Copy(c, ty, y);
+  // (the essential rows are fixed in the scratch vector, before y is written: x may be y, and its essential entries are read here)
   if (n_ess_) {
     if (policy_ == DiagonalPolicy::DIAG_ONE)
-      linalg::SetSubVector(c, y, d_ess_, n_ess_, x);
+      linalg::SetSubVector(c, ty, d_ess_, n_ess_, x);
     else
-      linalg::SetSubVector(c, y, d_ess_, n_ess_, 0.0);
+      linalg::SetSubVector(c, ty, d_ess_, n_ess_, 0.0);
   }
+  linalg::Copy(c, ty, y);
 }
 
 void ParOperator::MultTranspose(const Vector &x, Vector &y) const {
@@ -1251,13 +1252,13 @@ void ParOperator::MultTranspose(const Vector &x, Vector &y) const {
   A_->MultTranspose(lx_, ly_);
   if (halo_) halo_->RestrictAdd(ly_.Data(), c.stream);
   Vector ty(ly_.Data(), n_true_);
-  linalg::Copy(c, ty, y);
-  if (n_ess_) {
+  if (n_ess_) {  // (before y is written, as in Mult: x may be y)
     if (policy_ == DiagonalPolicy::DIAG_ONE)
-      linalg::SetSubVector(c, y, d_ess_, n_ess_, x);
+      linalg::SetSubVector(c, ty, d_ess_, n_ess_, x);
     else
-      linalg::SetSubVector(c, y, d_ess_, n_ess_, 0.0);
+      linalg::SetSubVector(c, ty, d_ess_, n_ess_, 0.0);
   }
+  linalg::Copy(c, ty, y);
 }
 
 void ParOperator::AddMultTranspose(const Vector &x, Vector &y, double a) const {

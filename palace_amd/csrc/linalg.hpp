@@ -348,9 +348,12 @@ class CsrOperator : public Operator {
 public:
   CsrOperator(const Context &ctx, const pa_csr *m);
   ~CsrOperator() override;
+  // lanes that share one row in the product kernels (4, 8 or 16, from nnz / nrows at construction)
+  int Lanes() const { return lanes_; }
   // one rank: ParOperator's essential-dof handling folded into a copy of the values (rows and columns zeroed, diagonal
   // 1 | 0).  The copy belongs to the caller (hipFree): several wrappers with different essential lists can share one matrix,
-  // and this operator itself always applies the unconstrained values.
+  // and this operator itself always applies the unconstrained values.  Only stored entries are rewritten: an essential row
+  // without a stored diagonal entry gets no unit entry (it becomes a zero row whatever `diag_one` says).
   double *EliminatedValues(const int32_t *d_ess, int n_ess, bool diag_one) const;
   void MultValues(const double *d_vals, const Vector &x, Vector &y) const;  // y = A' x, A' = this pattern with `d_vals`
   // the same on split vectors (pa_op_mult_split's contract: true dofs in x / y, ghosts read from xg0 | xg1 by the parity of *sel
