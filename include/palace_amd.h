@@ -428,7 +428,9 @@ int pa_op_mult_complex(pa_op *op_r, pa_op *op_i, const double *xr, const double 
                        void *stream);
 /* 1 if y = A x runs on the streaming kernels (single tensor-product block; H(curl): Q1 = 4 with p <= 3 or Q1 = 5 with p <= 4, metric
  * form or packed symmetric q-data -- one term, or curl-curl + mass with twelve doubles per point): callers choosing between
- * pa_op_mult2 and two pa_op_mult calls prefer the latter then */
+ * pa_op_mult2 and two pa_op_mult calls prefer the latter then.  Q1 = 3 with p <= 2 (order 2 on its own rule) streams only when the
+ * operator was created with PALACE_AMD_STREAM3=1 in the environment (opt-in: the default there is the one-shot kernel); such an
+ * operator answers pa_op_supports_split and pa_op_prepare_fused_step like the other rules, and pa_op_complex_fused with 0. */
 int pa_op_streams(const pa_op *op);
 /* Affine-element compression of the streaming H(curl) hex kernel (round 6): an element with a constant Jacobian has
  * D(q) = w_q D_e, and a batch of four such elements reads 6 | 7 | 12 numbers per ELEMENT instead of per point (the reference
@@ -474,7 +476,7 @@ int pa_op_mult_essential_diag(pa_op *op, const double *x, double *y, int diag_po
  * masked on input and the rows are fixed on output as in pa_op_mult_essential_diag (1: y = x there, 0: y = 0); < 0: plain.
  * What the reference does with three copies around CeedOperatorApplyAdd (linalg/rap.cpp:195-234: tx = x, lx = P tx, ly = A lx,
  * y = P^T ly) when P is a halo exchange.  pa_op_supports_split: 1 for a single H(curl) hexahedral block on the
- * streaming kernels (four or five points per direction: orders 1-4), 0 otherwise (the caller keeps the L-vector path). */
+ * streaming kernels (four or five points per direction: orders 1-4; three with PALACE_AMD_STREAM3=1), 0 otherwise (the caller keeps the L-vector path). */
 /* One step of a polynomial smoother consumed inside E^T (round 6).  The accumulated form of the Chebyshev recurrence of
  * linalg/chebyshev.cpp:204-218 (e_k = d_0 + ... + d_{k-1}) needs t = A e_k only once, in
  *     out (+)= e_k + sd (e_k - e_prev) + sr dinv .* (r0 - t);
@@ -482,7 +484,7 @@ int pa_op_mult_essential_diag(pa_op *op, const double *x, double *y, int diag_po
  * x or 0 by diag_policy, as pa_op_mult_essential_diag) and evaluates that line in the epilogue of the E^T gather, which then owns
  * every dof: t is never stored or re-read.  e_prev may be NULL (zero); out may be e_prev's buffer; add != 0: out += ...
  * pa_op_prepare_fused_step builds the index copies this needs, once, outside any stream capture: *available = 0 when the operator
- * has no such form (anything but one tensor H(curl) block on the four-point streaming kernel), and the caller keeps
+ * has no such form (anything but one tensor H(curl) or H1 block on a streaming kernel), and the caller keeps
  * pa_op_mult_essential_diag + its own vector kernel. */
 typedef struct {
   double sd, sr;

@@ -1382,11 +1382,12 @@ int pa_op_prepare_fused_step(pa_op *op, int *available) {
     }
     if (op->subs.size() != 1 || !op->dsubs.empty()) return;
     SubOp *so = op->subs[0];
-    // (four points per direction: pa_nd_hex_stream.hip; five: pa_nd_hex_stream5.hip -- nd_hex_stream_ok covers both; H1 blocks
-    // whose y = A x runs on the streaming kernel: pa_h1_hex_stream.hip)
+    // (four points per direction: pa_nd_hex_stream.hip; five: pa_nd_hex_stream5.hip; three, where PALACE_AMD_STREAM3=1 built the
+    // tables: pa_nd_hex_stream3.hip -- nd_hex_stream_ok covers them all; H1 blocks whose y = A x runs on the streaming kernel:
+    // pa_h1_hex_stream.hip)
     if (so->fe_type == PA_FE_H1) {
       if (!so->d_idxc || !so->stream_default || !so->d_perm_s_bc || !h1_hex_stream_ok(*so)) return;
-    } else if (so->fe_type != PA_FE_HCURL || (so->q1d != 4 && so->q1d != 5) || !so->d_idxc || !so->d_perm_s_bc || !nd_hex_stream_ok(*so)) {
+    } else if (so->fe_type != PA_FE_HCURL || (so->q1d != 3 && so->q1d != 4 && so->q1d != 5) || !so->d_idxc || !so->d_perm_s_bc || !nd_hex_stream_ok(*so)) {
       return;
     }
     *available = stream_build_all(*so) ? 1 : 0;

@@ -375,6 +375,10 @@ void launch_nd_hex_stream_all(const SubOp &so, const double *x, hipStream_t s, c
 void launch_et_run_gather_step(const SubOp &so, const double *x, const GatherStep &step, int ess_policy, hipStream_t s,
                                const SplitIO *split = nullptr);
 bool nd_hex_stream5_ok(const SubOp &so);
+// pa_nd_hex_stream3.hip: three points per direction (orders 1 and 2), opt-in with PALACE_AMD_STREAM3=1 at operator creation
+bool nd_hex_stream3_ok(const SubOp &so);
+void launch_nd_hex_stream3(const SubOp &so, const double *x, double *y, bool masked, hipStream_t s, const SplitIO *split = nullptr,
+                           bool all = false);
 void launch_nd_hex_stream5(const SubOp &so, const double *x, double *y, bool masked, hipStream_t s, const SplitIO *split = nullptr,
                            bool all = false);
 void launch_nd_hex_stream5_complex(const SubOp &sr, const SubOp &si, const double *xr, const double *xi, double *yr, double *yi,

@@ -775,11 +775,16 @@ bool nd_hex_stream_ok(const SubOp &so) {
   static const bool enabled = !(getenv("PALACE_AMD_STREAM") && atoi(getenv("PALACE_AMD_STREAM")) == 0);
   if (!enabled) return false;
   if (so.q1d == 5) return nd_hex_stream5_ok(so);  // five points per direction: pa_nd_hex_stream5.hip
+  if (so.q1d == 3) return nd_hex_stream3_ok(so);  // three (opt-in, PALACE_AMD_STREAM3=1): pa_nd_hex_stream3.hip
   if (so.fe_type != PA_FE_HCURL || so.q1d != 4 || so.p > 3 || !so.qd || !so.d_ye || !so.d_perm_x) return false;
   return so.qd->metric || so.qd->ncomp == 6 || (so.qd->ncomp == 12 && so.qf == PA_QF_HDIVMASS_33);
 }
 
 static bool wide_form(const SubOp &so) { return so.fe_type == PA_FE_HCURL && so.q1d == 5; }
+// three points per direction (pa_nd_hex_stream3.hip): sixteen lanes per element as at four points, so every table below -- the
+// index blocks of pack_index, the flag words, the slot patterns, the run lists and their masked / `all` copies -- is built the
+// same way for both; only the element kernel differs
+static bool three_point_form(const SubOp &so) { return so.fe_type == PA_FE_HCURL && so.q1d == 3; }
 
 // Scalar mass / curl-curl coefficient of every element (coeff_3_qf.h:9-24 resolved on the host; isotropic materials): what the
 // metric form multiplies its geometric matrices with, [ne padded to 4][2]
@@ -1229,6 +1234,7 @@ void launch_nd_hex_stream_all(const SubOp &so, const double *x, hipStream_t s, c
   double *unused = so.d_ye;  // (no entry is exclusive in this form: y is never written)
   if (so.fe_type == PA_FE_H1) return launch_h1_hex_stream(so, x, unused, true, s, split, true);
   if (wide_form(so)) return launch_nd_hex_stream5(so, x, unused, true, s, split, true);
+  if (three_point_form(so)) return launch_nd_hex_stream3(so, x, unused, true, s, split, true);
   switch (so.p) {
     case 1: launch_p<1>(so, x, unused, true, s, split, true); break;
     case 2: launch_p<2>(so, x, unused, true, s, split, true); break;
@@ -1238,11 +1244,13 @@ void launch_nd_hex_stream_all(const SubOp &so, const double *x, hipStream_t s, c
 }
 
 bool nd_hex_stream_split_ok(const SubOp &so) {
-  return so.fe_type == PA_FE_HCURL && so.d_idxc && (so.q1d == 4 || (wide_form(so) && nd_hex_stream5_ok(so)));
+  return so.fe_type == PA_FE_HCURL && so.d_idxc &&
+         (so.q1d == 4 || (wide_form(so) && nd_hex_stream5_ok(so)) || (three_point_form(so) && nd_hex_stream3_ok(so)));
 }
 
 void launch_nd_hex_stream(const SubOp &so, const double *x, double *y, bool masked, hipStream_t s, const SplitIO *split) {
   if (wide_form(so)) return launch_nd_hex_stream5(so, x, y, masked, s, split);
+  if (three_point_form(so)) return launch_nd_hex_stream3(so, x, y, masked, s, split);
   switch (so.p) {
     case 1: launch_p<1>(so, x, y, masked, s, split); break;
     case 2: launch_p<2>(so, x, y, masked, s, split); break;
