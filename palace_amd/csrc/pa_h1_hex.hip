@@ -270,7 +270,7 @@ __global__ __launch_bounds__(64 * kH1Waves, 2) void h1_hex_apply_kernel(const H1
 }
 
 // QFunction id -> the terms (mass: values, diffusion: gradient) and their coefficients
-static void h1_terms(const SubOp &so, bool &use_v, bool &use_g, CoeffDev &cm, CoeffDev &cd) {
+void h1_terms(const SubOp &so, bool &use_v, bool &use_g, CoeffDev &cm, CoeffDev &cd) {
   use_v = so.qf == PA_QF_H1_1 || so.qf == PA_QF_HCURLMASS_33;
   use_g = so.qf == PA_QF_HCURL_33 || so.qf == PA_QF_HCURLMASS_33;
   if (!use_v && !use_g) throw Error("QFunction not available for H1 hexahedra");
@@ -316,6 +316,7 @@ static void h1_launch_pq(const SubOp &so, const double *x, bool masked, hipStrea
 // writes the E-vector so.d_ye; the caller follows with launch_et_gather
 void launch_h1_hex_apply(const SubOp &so, const double *x, bool masked, hipStream_t s) {
   PA_REQUIRE(so.d_ye, "H1 blocks use the gather form of E^T");
+  if (so.q1d == 6) return launch_h1_hex_q6(so, x, masked, s);  // six points per direction: pa_h1_hex_q6.hip
   PA_HEX_DISPATCH(h1_launch_pq, "H1", so, x, masked, s)
 }
 

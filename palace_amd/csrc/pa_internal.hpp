@@ -326,6 +326,13 @@ void launch_et_gather(const SubOp &so, double *y, bool accumulate, hipStream_t s
 void launch_nd_hex_qdata(SubOp &so, hipStream_t s);
 void launch_nd_hex_metric(SubOp &so, hipStream_t s);
 void launch_nd_hex_diag(const SubOp &so, double *diag, hipStream_t s);
+// QFunction id of an H(curl) hex block -> its terms and their coefficients (cross 1 / 2: the mixed curl forms)
+void nd_terms(const SubOp &so, bool &use_u, bool &use_c, CoeffDev &cm, CoeffDev &cc, int &cross);
+// ... of an H1 hex block (mass: values, diffusion: gradient)
+void h1_terms(const SubOp &so, bool &use_v, bool &use_g, CoeffDev &cm, CoeffDev &cd);
+// pa_nd_hex_q6.hip / pa_h1_hex_q6.hip: six points per direction (PA_HEX_Q6_LIST); launch_nd_hex_apply / launch_h1_hex_apply route here
+void launch_nd_hex_q6(const SubOp &so, const double *x, double *y, double *ye, bool masked, hipStream_t s);
+void launch_h1_hex_q6(const SubOp &so, const double *x, bool masked, hipStream_t s);
 // pa_nd_hex_stream.hip
 struct SplitIO;
 bool h1_hex_stream_ok(const SubOp &so);       // the streaming form is the default for y = A x

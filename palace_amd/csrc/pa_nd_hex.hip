@@ -363,7 +363,7 @@ static void launch_iso(const NDArgs<P1, Q1> &a, bool iso, dim3 grid, dim3 block,
 // QFunction id -> the terms (mass: values, curl-curl: curls) and their coefficients; the mixed curl forms of
 // hcurlhdiv_33_qf.h set neither flag but cross = 1 (f_apply_hcurlhdiv_33: values in, curl test functions out) / 2
 // (f_apply_hdivhcurl_33), with their coefficient in cm
-static void nd_terms(const SubOp &so, bool &use_u, bool &use_c, CoeffDev &cm, CoeffDev &cc, int &cross) {
+void nd_terms(const SubOp &so, bool &use_u, bool &use_c, CoeffDev &cm, CoeffDev &cc, int &cross) {
   use_u = so.qf == PA_QF_HCURL_33 || so.qf == PA_QF_HDIVMASS_33;
   use_c = so.qf == PA_QF_HDIV_33 || so.qf == PA_QF_HDIVMASS_33;
   cross = so.qf == PA_QF_HCURLHDIV_33 ? 1 : so.qf == PA_QF_HDIVHCURL_33 ? 2 : 0;
@@ -425,6 +425,10 @@ bool nd_hex_supports_two_rhs(const SubOp &so) { return so.fe_type == PA_FE_HCURL
 
 void launch_nd_hex_apply(const SubOp &so, const double *x, double *y, double *ye, bool masked, hipStream_t s,
                          bool accumulate, int ess_policy, const double *x1, double *y1, double *ye1) {
+  if (so.q1d == 6) {  // six points per direction: pa_nd_hex_q6.hip (no exclusive-dof store, one right-hand side)
+    PA_REQUIRE(!x1, "two right-hand sides stop at four points per direction");
+    return launch_nd_hex_q6(so, x, y, ye, masked, s);
+  }
   PA_HEX_DISPATCH(launch_pq, "H(curl)", so, x, y, ye, masked, s, accumulate, ess_policy, x1, y1, ye1)
 }
 
