@@ -306,7 +306,7 @@ static SubOp *make_sub(pa_geom *geom, const pa_restriction_desc &r, const pa_bas
     PA_REQUIRE(need != 0 && trial_ops == need && test_ops == need,
                "H(div) hexahedra: the mass operator (PA_QF_HDIV_33, Interp), div-div (PA_QF_L2_1, Div) and div-div + mass "
                "(PA_QF_L2MASS_33, Interp | Div) are supported");
-    if (!hex_pq_supported(b.order, b.q1d)) throw hex_pq_error("H(div)", b.order, b.q1d);
+    if (!hex_pq_supported(b.order, b.q1d) && !hex_q6_supported(b.order, b.q1d)) throw hex_pq_error("H(div)", b.order, b.q1d);
     PA_REQUIRE(!shared_qd, "H(div) blocks have no coarsened form");
   } else if (cross) {  // integ/mixedveccurl.cpp:21-120 on one H(curl) space
     PA_REQUIRE(b.fe_type == PA_FE_HCURL, "the mixed curl QFunctions need an H(curl) space");
@@ -455,7 +455,7 @@ MixedSub *make_mixed_hex_sub(pa_geom *geom, const pa_restriction_desc &r1, const
   PA_REQUIRE(!r1.curl_orients && !r2.curl_orients, "the curl-oriented restriction needs the dense-table path (pa_op_add_sub_dense_mixed)");
   PA_REQUIRE(b1.order == b2.order, "the two spaces of a tensor-product mixed-space operator have the same order");
   PA_REQUIRE(b1.q1d == geom->q1d && b2.q1d == geom->q1d, "basis and geometry data use different quadrature rules");
-  if (!hex_pq_supported(b1.order, b1.q1d)) throw hex_pq_error("H(curl) - H(div)", b1.order, b1.q1d);
+  if (!hex_pq_supported(b1.order, b1.q1d) && !hex_q6_supported(b1.order, b1.q1d)) throw hex_pq_error("H(curl) - H(div)", b1.order, b1.q1d);
   PA_REQUIRE(b1.Bc && b1.Gc && b1.Bo && b2.Bc && b2.Gc && b2.Bo, "1-D basis tables missing");
   PA_REQUIRE(r1.elem_size == expected_P(b1.fe_type, b1.order) && r2.elem_size == expected_P(b2.fe_type, b2.order) && r1.offsets &&
                  r2.offsets && r1.lsize > 0 && r2.lsize > 0,

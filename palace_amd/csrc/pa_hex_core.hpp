@@ -65,14 +65,20 @@ using H1Layout = HexLayout<P1, Q1, 0, 2, 3>;
 #define PA_HEX_PQ_CALL(P, Q, FN, ...) case P * 16 + Q: FN<P, Q>(__VA_ARGS__); break;
 
 // Six points per direction: the order-5 operators and the coarser levels of their p-multigrid hierarchy.  A list of its own
-// -- only the H(curl) and H1 apply kernels serve these pairs (pa_nd_hex_q6.hip, the last block of pa_h1_hex.hip); the H(div)
-// and two-space kernels, which take their support from hex_pq_supported, stop at five points.
+// -- every family serves these pairs with kernels fitted to 36 lanes per element (pa_nd_hex_q6.hip, pa_h1_hex_q6.hip,
+// pa_rt_hex_q6.hip, pa_mixed_hex_q6.hip); the both-parts-per-pass kernels (pa_rt_hex2.hip, pa_mixed_hex2.hip) stop at five points.
 #define PA_HEX_Q6_LIST(X, ...) \
   X(1, 6, __VA_ARGS__) X(2, 6, __VA_ARGS__) X(3, 6, __VA_ARGS__) X(4, 6, __VA_ARGS__) X(5, 6, __VA_ARGS__)
 
 inline bool hex_pq_supported(int p, int q1d) {
   switch (p * 16 + q1d) {
     PA_HEX_PQ_LIST(PA_HEX_PQ_LABEL, ) return true;
+  }
+  return false;
+}
+inline bool hex_q6_supported(int p, int q1d) {
+  switch (p * 16 + q1d) {
+    PA_HEX_Q6_LIST(PA_HEX_PQ_LABEL, ) return true;
   }
   return false;
 }

@@ -401,6 +401,7 @@ void launch_h1_hex_qdata(SubOp &so, hipStream_t s);
 void launch_h1_hex_diag(const SubOp &so, double *diag, hipStream_t s);
 // pa_rt_hex.hip: Raviart-Thomas hexahedra (mass, div-div, div-div + mass); the E-vector + gather form of E^T only
 void launch_rt_hex_apply(const SubOp &so, const double *x, bool masked, hipStream_t s);
+void launch_rt_hex_q6(const SubOp &so, const double *x, bool masked, hipStream_t s);  // six points per direction: pa_rt_hex_q6.hip
 void launch_rt_hex_qdata(SubOp &so, hipStream_t s);
 void launch_rt_hex_diag(const SubOp &so, double *diag, hipStream_t s);
 // two right-hand sides per pass (packed D, a compiled pair, PALACE_AMD_TWO_PART != 0): the E-vectors d_ye and d_ye2
@@ -463,6 +464,9 @@ MixedSub *make_mixed_hex_sub(pa_geom *geom, const pa_restriction_desc &r1, const
 void free_sub(SubOp *so);
 // pa_mixed_hex.hip: x1 -> the E-vector of the output block (apply; transpose: hex2 -> hex1) or x1, x2 -> out (error)
 void launch_mixed_hex(const MixedSub &ms, const double *x1, const double *x2, double *out, hipStream_t s, bool transpose);
+// six points per direction (pa_mixed_hex_q6.hip): so / s2 the input and the other block, kind with the transpose resolved
+void launch_mixed_hex_q6(const SubOp &so, const SubOp &s2, const MixedSub &ms, int kind, const double *x1, const double *x2,
+                         double *out, hipStream_t s);
 // both parts of a complex field in one launch (a compiled pair, PALACE_AMD_TWO_PART != 0)
 bool mixed_hex_two_part(const MixedSub &ms);
 void launch_mixed_hex2(const MixedSub &ms, const double *x1, const double *x2, const double *x1i, const double *x2i, double *out,

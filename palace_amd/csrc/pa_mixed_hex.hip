@@ -181,6 +181,7 @@ void launch_mixed_hex(const MixedSub &ms, const double *x1, const double *x2, do
   const SubOp &so = transpose ? *ms.hex2 : *ms.hex1, &s2 = transpose ? *ms.hex1 : *ms.hex2;
   const int kind = !transpose ? ms.kind : 1 - ms.kind;
   PA_REQUIRE(ms.error || s2.d_ye, "two-space blocks use the gather form of E^T");
+  if (so.q1d == 6) return launch_mixed_hex_q6(so, s2, ms, kind, x1, x2, out, s);  // six points per direction: pa_mixed_hex_q6.hip
   PA_HEX_DISPATCH(mh_launch_pq, "H(curl) - H(div)", so, s2, ms, kind, x1, x2, out, s)
 }
 

@@ -1,5 +1,5 @@
 // Device helpers the two-space hexahedron kernels share (pa_mixed_hex.hip: one right-hand side / one pair of inputs;
-// pa_mixed_hex2.hip: both parts of a complex field per launch): the half tables, the LDS layout, the value passes of one
+// pa_mixed_hex2.hip: both parts of a complex field per launch; pa_mixed_hex_q6.hip: six points per direction): the half tables, the LDS layout, the value passes of one
 // component, E of one space and the geometry rows of a point.  The mapping is described at the top of pa_mixed_hex.hip.
 #pragma once
 
@@ -42,9 +42,10 @@ constexpr int mh_ndofs() {
   return 3 * MHComp<P1, 0, OPEN>::NL * MHComp<P1, 0, OPEN>::NT * MHComp<P1, 0, OPEN>::NT;
 }
 
-// Forward value passes of component C: dofs (LDS, tensor order) -> V[qz] of lane (qx, qy) = (ta, tb)
-template <int P1, int Q1, int C, bool OPEN>
-__device__ __forceinline__ void mh_fwd_comp(const MHTab<P1, Q1> &tab, double *sm, const int ta, const int tb, const bool lane_ok,
+// Forward value passes of component C: dofs (LDS, tensor order) -> V[qz] of lane (qx, qy) = (ta, tb).  Tab: anything with the
+// half tables Bo, Bc as arrays or pointers -- MHTab (kernel arguments) or the LDS view of pa_mixed_hex_q6.hip.
+template <int P1, int Q1, int C, bool OPEN, class Tab>
+__device__ __forceinline__ void mh_fwd_comp(const Tab &tab, double *sm, const int ta, const int tb, const bool lane_ok,
                                             double V[Q1]) {
   using L = MHLayout<P1, Q1>;
   using D = MHComp<P1, C, OPEN>;
@@ -97,8 +98,8 @@ __device__ __forceinline__ void mh_fwd_comp(const MHTab<P1, Q1> &tab, double *sm
 }
 
 // Transposed value passes of component C: W[qz] of lane (qx, qy) -> the component's dofs in tensor order (LDS)
-template <int P1, int Q1, int C, bool OPEN>
-__device__ __forceinline__ void mh_bwd_comp(const MHTab<P1, Q1> &tab, double *sm, const int ta, const int tb, const bool lane_ok,
+template <int P1, int Q1, int C, bool OPEN, class Tab>
+__device__ __forceinline__ void mh_bwd_comp(const Tab &tab, double *sm, const int ta, const int tb, const bool lane_ok,
                                             const double W[Q1]) {
   using L = MHLayout<P1, Q1>;
   using D = MHComp<P1, C, OPEN>;
@@ -180,8 +181,8 @@ __device__ __forceinline__ void mh_gather(const int32_t *__restrict__ sidx, cons
 }
 
 // the three components of one space at the lane's Q1 points
-template <int P1, int Q1, bool OPEN>
-__device__ __forceinline__ void mh_forward(const MHTab<P1, Q1> &tab, double *sm, const int ta, const int tb, const bool lane_ok,
+template <int P1, int Q1, bool OPEN, class Tab>
+__device__ __forceinline__ void mh_forward(const Tab &tab, double *sm, const int ta, const int tb, const bool lane_ok,
                                            double V[3][Q1]) {
   mh_fwd_comp<P1, Q1, 0, OPEN>(tab, sm, ta, tb, lane_ok, V[0]);
   mh_fwd_comp<P1, Q1, 1, OPEN>(tab, sm, ta, tb, lane_ok, V[1]);

@@ -154,6 +154,7 @@ static void rt_launch_pq(const SubOp &so, const double *x, bool masked, hipStrea
 void launch_rt_hex_apply(const SubOp &so, const double *x, bool masked, hipStream_t s) {
   PA_REQUIRE(so.d_ye, "H(div) blocks use the gather form of E^T");
   PA_REQUIRE(!masked || so.d_sidx_bc, "pa_op_set_essential has not been called");
+  if (so.q1d == 6) return launch_rt_hex_q6(so, x, masked, s);  // six points per direction: pa_rt_hex_q6.hip
   PA_HEX_DISPATCH(rt_launch_pq, "H(div)", so, x, masked, s)
 }
 
@@ -324,7 +325,7 @@ __global__ void rt_hex_diag_kernel(const RTDiagArgs a) {
 
 void launch_rt_hex_diag(const SubOp &so, double *diag, hipStream_t s) {
   PA_REQUIRE(so.d_ye && so.d_tptr && so.d_perm, "H(div) blocks use the gather form of E^T");
-  PA_REQUIRE(hex_pq_supported(so.p, so.q1d), "no H(div) hex kernel for this order and quadrature rule");
+  PA_REQUIRE(hex_pq_supported(so.p, so.q1d) || hex_q6_supported(so.p, so.q1d), "no H(div) hex kernel for this order and quadrature rule");
   RTDiagArgs a{};
   a.ne = so.ne, a.p = so.p, a.q1 = so.q1d;
   a.sidx = so.d_sidx, a.perm = so.d_perm, a.ye = so.d_ye;

@@ -1,5 +1,5 @@
 // Device helpers the Raviart-Thomas hexahedron kernels share (pa_rt_hex.hip: one right-hand side; pa_rt_hex2.hip: two per
-// pass): the half tables, the kernel arguments, the LDS layout and the forward / transposed passes of one component.  The
+// pass; pa_rt_hex_q6.hip: six points per direction): the half tables, the kernel arguments, the LDS layout and the forward / transposed passes of one component.  The
 // element and the mapping are described at the top of pa_rt_hex.hip.
 #pragma once
 
@@ -48,9 +48,10 @@ constexpr int kRTWaves = 4;
 
 // Forward passes of component C: dofs (LDS, tensor order) -> V[qz] (value, USE_V) and DV[qz] += divergence (USE_DIV) of
 // lane (qx, qy) = (ta, tb).  Before the pass along C there is one chain (field 0); that pass splits it into the value (Bc,
-// field 0) and the derivative (Gc, field 1); the passes after it apply Bo to both.
-template <int P1, int Q1, int C, bool USE_V, bool USE_DIV>
-__device__ __forceinline__ void rt_fwd_comp(const RTTab<P1, Q1> &tab, double *sm, const int ta, const int tb, const bool lane_ok,
+// field 0) and the derivative (Gc, field 1); the passes after it apply Bo to both.  Tab: anything with the half tables Bo, Bc,
+// Gc as arrays or pointers -- RTTab (kernel arguments) or the LDS view of pa_rt_hex_q6.hip.
+template <int P1, int Q1, int C, bool USE_V, bool USE_DIV, class Tab>
+__device__ __forceinline__ void rt_fwd_comp(const Tab &tab, double *sm, const int ta, const int tb, const bool lane_ok,
                                             double V[Q1], double DV[Q1]) {
   using L = RTLayout<P1, Q1>;
   constexpr int NC = L::NC;
@@ -143,8 +144,8 @@ __device__ __forceinline__ void rt_fwd_comp(const RTTab<P1, Q1> &tab, double *sm
 
 // Transposed passes of component C: W[qz] (the D stage's value output of this component) and DW[qz] (its divergence
 // output) of lane (qx, qy) -> the component's dofs in tensor order (LDS).  The pass along C merges the two chains.
-template <int P1, int Q1, int C, bool USE_V, bool USE_DIV>
-__device__ __forceinline__ void rt_bwd_comp(const RTTab<P1, Q1> &tab, double *sm, const int ta, const int tb, const bool lane_ok,
+template <int P1, int Q1, int C, bool USE_V, bool USE_DIV, class Tab>
+__device__ __forceinline__ void rt_bwd_comp(const Tab &tab, double *sm, const int ta, const int tb, const bool lane_ok,
                                             const double W[Q1], const double DW[Q1]) {
   using L = RTLayout<P1, Q1>;
   constexpr int NC = L::NC;
