@@ -120,6 +120,48 @@ int pa_par_op_add_mult(pa_par_op *A, const double *x, double *y, double a);
 int pa_par_op_eliminate_rhs(pa_par_op *A, const double *x, double *b);
 int pa_par_op_assemble_diagonal(pa_par_op *A, double *diag);
 
+/* --- conforming prolongation with hanging-entity constraints (one rank) ------------------------
+ * After a nonconforming refinement of tensor elements (utils/geodata.cpp:174-186) the reference's conforming prolongation is a
+ * sparse operator, and every ParOperator is P^T A P with it (linalg/rap.cpp:65, :212-216).  Local vector layout as for a
+ * halo: true dofs [0, n_true), then the constrained dofs; P = [I; C].
+ *   row_ptr [n_local - n_true + 1], col, val   C in CSR (host arrays); every column must be a true dof (one-irregular meshes
+ *                                              have no chains of constraints)
+ * The transposed product gathers through an inverted index built here (per touched true dof its (slave, value) pairs in
+ * ascending slave order): no atomics, bitwise reproducible.  A halo and a conforming prolongation together are not supported. */
+typedef struct pa_conform pa_conform;
+int pa_conform_create(pa_context *ctx, int n_true, int n_local, const int *row_ptr, const int32_t *col, const double *val,
+                      pa_conform **c);
+void pa_conform_destroy(pa_conform *c);
+/* lx[0, n_true) = x (0 where ess_mask, one byte per true dof, is set; ess_mask may be NULL), lx[n_true + r] = sum_j C[r, j] x[j]
+ * with x masked the same way.  One launch; device pointers. */
+int pa_conform_prolongate(pa_context *ctx, pa_conform *c, const double *x_true, double *lx, const uint8_t *ess_mask);
+/* y[i] = ly[i] + sum_r C[r, i] ly[n_true + r].  One launch.  flags: */
+enum pa_conform_flags {
+  PA_CONFORM_ADD = 1,      /* y += a (...) instead of y = (...) */
+  PA_CONFORM_ABS = 2,      /* |C|^T: the diagonal of an AMR mesh (rap.cpp:163-175 uses AbsMultTranspose) */
+  PA_CONFORM_FIX_ONE = 4,  /* the essential rows of ParOperator::Mult: where ess_mask is set the value is x_ess[i] ... */
+  PA_CONFORM_FIX_ZERO = 8  /* ... or 0 */
+};
+int pa_conform_restrict(pa_context *ctx, pa_conform *c, const double *ly, double *y_true, int flags, double a,
+                        const uint8_t *ess_mask, const double *x_ess);
+/* lanes that share one row of C (which = 0) or of C^T (1): a power of two sized from the longest row */
+int pa_conform_lanes(const pa_conform *c, int which);
+/* pa_par_op_create / pa_par_sum_op_create / pa_complex_par_op_create / pa_interp_create / pa_gradient_create with a conforming
+ * prolongation in place of the halo (the domain space's for the two transfers: the true-dof operator is R_f I P_c, its transpose
+ * P_c^T I^T R_f^T with a zero-filled tail).  Such a ParOperator applies P (masked), the local operator and P^T (with the
+ * essential rows) in three launches; its fused and split forms are not available, so smoothers and PCG take their plain paths. */
+int pa_par_op_create_conforming(pa_context *ctx, pa_op *local, int n_true, const int32_t *ess_tdofs, int n_ess,
+                                int diag_policy, pa_conform *conf, pa_par_op **A);
+int pa_par_sum_op_create_conforming(pa_context *ctx, int nterms, pa_op *const *locals, const double *coeffs, int n_true,
+                                    const int32_t *ess_tdofs, int n_ess, int diag_policy, pa_conform *conf, pa_par_op **A);
+/* 1 when the operator fuses its essential dofs into the local apply (a pure query; 0 with a conforming P) */
+int pa_par_op_fuses_essential(const pa_par_op *A);
+/* ParOperator::PrepareChebyStep(): 1 when the operator has the fused smoother step.  NOT a pure query: like the C++ method it is
+ * a set-up call -- where the form exists it is prepared on the way (the local operator builds the index tables of its fused
+ * step, as a Chebyshev smoother's SetOperator would), so call it at set-up time, never inside a recorded sequence.  With a
+ * conforming P it returns 0 and touches nothing. */
+int pa_par_op_prepare_cheby_step(pa_par_op *A);
+
 /* --- vectors (linalg/vector.cpp) ------------------------------------------------------------- */
 int pa_vec_dot(pa_context *ctx, const double *x, const double *y, int n, double *result);
 /* linalg::Sum (global sum of the entries; LocalSum vector.cpp:687-699 + Mpi::GlobalSum; a ComplexVector's sum is the
@@ -336,6 +378,9 @@ void pa_complex_smoother_destroy(pa_cprecond *P);
  *     MultHermitianTranspose); add != 0 is the AddMult* form y += a op(A) x with complex a.  `local_mult` applies the
  *     local ComplexWrapperOperator (linalg/operator.cpp:58-413) on L-vectors. */
 int pa_complex_par_op_create(pa_context *ctx, pa_op *Ar, pa_op *Ai, int n_true, pa_halo *halo, pa_complex_par_op **A);
+/* the same with a conforming prolongation (hanging nodes, one rank) in place of the halo */
+int pa_complex_par_op_create_conforming(pa_context *ctx, pa_op *Ar, pa_op *Ai, int n_true, pa_conform *conf,
+                                        pa_complex_par_op **A);
 int pa_complex_par_op_set_essential(pa_complex_par_op *A, const int32_t *ess, int n_ess, int policy);
 int pa_complex_par_op_mult(pa_complex_par_op *A, int mode, int add, double a_re, double a_im, const double *xr,
                            const double *xi, double *yr, double *yi);
@@ -382,6 +427,15 @@ int pa_interp_create(pa_context *ctx, const pa_restriction_desc *coarse_restr,
 int pa_gradient_create(pa_context *ctx, const pa_restriction_desc *h1_restr, const pa_basis_desc *h1_basis,
                        const pa_restriction_desc *nd_restr, const pa_basis_desc *nd_basis, const double *Dg,
                        pa_halo *h1_halo, int n_true_h1, int n_true_nd, pa_interp **G);
+/* pa_interp_create / pa_gradient_create with the conforming prolongation of the domain (coarse / H1) space in place of its
+ * halo: R_f I P_c and P_c^T I^T R_f^T on true-dof vectors (the range space's constraints are its layout alone). */
+int pa_interp_create_conforming(pa_context *ctx, const pa_restriction_desc *coarse_restr,
+                                const pa_basis_desc *coarse_basis, const pa_restriction_desc *fine_restr,
+                                const pa_basis_desc *fine_basis, const double *Ic, const double *Io,
+                                pa_conform *coarse_conf, int n_true_coarse, int n_true_fine, pa_interp **P);
+int pa_gradient_create_conforming(pa_context *ctx, const pa_restriction_desc *h1_restr, const pa_basis_desc *h1_basis,
+                                  const pa_restriction_desc *nd_restr, const pa_basis_desc *nd_basis, const double *Dg,
+                                  pa_conform *h1_conf, int n_true_h1, int n_true_nd, pa_interp **G);
 /* Discrete curl C : ND(p) -> RT(p) on the same tensor hexahedra (the flux B = curl A; fem/fespace.cpp:199-206 builds it with
  * the curl interpolator on the Raviart-Thomas space, fem/libceed/basis.cpp:139-150 asks for its element matrix).  With the
  * nodal tensor bases that matrix is RT_c = D_d ND_e - D_e ND_d over the cyclic triples (c, d, e), D_d being Dg along d and the

@@ -337,7 +337,7 @@ ComplexWrapperOperator::ComplexWrapperOperator(const Context &ctx, const Operato
   const auto *cr = dynamic_cast<const ceed::Operator *>(Ar), *ci = dynamic_cast<const ceed::Operator *>(Ai);
   fused_ = cr && ci && ceed::Operator::ComplexFused(*cr, *ci) != 0;
   const auto *pr = dynamic_cast<const ParOperator *>(Ar), *pi = dynamic_cast<const ParOperator *>(Ai);
-  if (pr && pi && !pr->GetHalo() && !pi->GetHalo()) {
+  if (pr && pi && !pr->GetHalo() && !pi->GetHalo() && !pr->GetConforming() && !pi->GetConforming()) {
     const auto *lr = dynamic_cast<const ceed::Operator *>(&pr->LocalOperator());
     const auto *li = dynamic_cast<const ceed::Operator *>(&pi->LocalOperator());
     const int ne = pr->NumEssentialTrueDofs();
@@ -495,14 +495,16 @@ void ComplexWrapperOperator::AddMultHermitianTranspose(const ComplexVector &x, C
 }
 
 // ---- ComplexParOperator (rap.cpp:393-749) --------------------------------------------------------------------------
-ComplexParOperator::ComplexParOperator(const Context &ctx, const Operator *Ar, const Operator *Ai, int n_true, const Halo *halo)
-    : ComplexOperator(n_true, n_true), ctx_(&ctx), Ar_(Ar), Ai_(Ai), halo_(halo), n_true_(n_true) {
+ComplexParOperator::ComplexParOperator(const Context &ctx, const Operator *Ar, const Operator *Ai, int n_true, const Halo *halo,
+                                       const Conforming *conf)
+    : ComplexOperator(n_true, n_true), ctx_(&ctx), Ar_(Ar), Ai_(Ai), halo_(halo), conf_(conf), n_true_(n_true) {
   A_ = std::make_unique<ComplexWrapperOperator>(ctx, Ar, Ai);
   PA_REQUIRE(A_->Height() == A_->Width(), "ComplexParOperator needs square local operators");
   n_local_ = A_->Height();
-  PA_REQUIRE(n_true <= n_local_ && (halo || n_true == n_local_), "local != true dofs requires a halo plan");
-  if (Ar) RAPr_ = std::make_unique<ParOperator>(ctx, *Ar, n_true, nullptr, 0, ParOperator::DiagonalPolicy::DIAG_ONE, halo);
-  if (Ai) RAPi_ = std::make_unique<ParOperator>(ctx, *Ai, n_true, nullptr, 0, ParOperator::DiagonalPolicy::DIAG_ZERO, halo);
+  PA_REQUIRE(!(halo && conf), "ComplexParOperator: a halo and a conforming prolongation together are not supported");
+  PA_REQUIRE(n_true <= n_local_ && (halo || conf || n_true == n_local_), "local != true dofs requires a halo plan or a conforming prolongation");
+  if (Ar) RAPr_ = std::make_unique<ParOperator>(ctx, *Ar, n_true, nullptr, 0, ParOperator::DiagonalPolicy::DIAG_ONE, halo, conf);
+  if (Ai) RAPi_ = std::make_unique<ParOperator>(ctx, *Ai, n_true, nullptr, 0, ParOperator::DiagonalPolicy::DIAG_ZERO, halo, conf);
   RAP_ = std::make_unique<ComplexWrapperOperator>(ctx, RAPr_.get(), RAPi_.get());
   lx_.SetSize(n_local_), ly_.SetSize(n_local_);
   UpdateFused();
@@ -510,7 +512,7 @@ ComplexParOperator::ComplexParOperator(const Context &ctx, const Operator *Ar, c
 void ComplexParOperator::UpdateFused() {
   fused_r_ = fused_i_ = nullptr;
   const auto *cr = dynamic_cast<const ceed::Operator *>(Ar_), *ci = dynamic_cast<const ceed::Operator *>(Ai_);
-  const int kind = (!halo_ && cr && ci) ? ceed::Operator::ComplexFused(*cr, *ci) : 0;
+  const int kind = (!halo_ && !conf_ && cr && ci) ? ceed::Operator::ComplexFused(*cr, *ci) : 0;
   if (!kind) return;
   // essential dofs inside the kernel (hexahedral form; round 5: dense blocks too, through the flagged index copy of Ar's block and
   // its gathers): only if this wrapper's list is the one fused into Ar
@@ -532,8 +534,8 @@ void ComplexParOperator::SetEssentialTrueDofs(const int32_t *ess_host, int n_ess
   d_ess_ = n_ess ? pa::dev_upload(ess_host, (size_t)n_ess, ctx_->stream) : nullptr;
   n_ess_ = n_ess, policy_ = policy;
   // the real ParOperators are rebuilt with the list (real part: the policy; imaginary part: DIAG_ZERO, rap.cpp:450-457)
-  if (Ar_) RAPr_ = std::make_unique<ParOperator>(*ctx_, *Ar_, n_true_, ess_host, n_ess, policy, halo_);
-  if (Ai_) RAPi_ = std::make_unique<ParOperator>(*ctx_, *Ai_, n_true_, ess_host, n_ess, ParOperator::DiagonalPolicy::DIAG_ZERO, halo_);
+  if (Ar_) RAPr_ = std::make_unique<ParOperator>(*ctx_, *Ar_, n_true_, ess_host, n_ess, policy, halo_, conf_);
+  if (Ai_) RAPi_ = std::make_unique<ParOperator>(*ctx_, *Ai_, n_true_, ess_host, n_ess, ParOperator::DiagonalPolicy::DIAG_ZERO, halo_, conf_);
   RAP_ = std::make_unique<ComplexWrapperOperator>(*ctx_, RAPr_.get(), RAPi_.get());
   UpdateFused();
 }
@@ -579,6 +581,7 @@ void ComplexParOperator::RestrictFix(const ComplexVector &x, ComplexVector &ly, 
 void ComplexParOperator::Mult(const ComplexVector &x, ComplexVector &y) const {
   // rap.cpp:483-519.  One rank: the same result through the two real ParOperators (yr = RAPr xr - RAPi xi has xr on the
   // essential rows, yi = RAPi xr + RAPr xi has xi, with RAPi's rows zero), BC masking fused into the element kernels.
+  if (conf_) return RAP_->Mult(x, y);  // hanging nodes: P, the local apply and P^T of the two real ParOperators
   if (!halo_ && x.Real().Data() != y.Real().Data()) {
     if (fused_r_) {  // essential dofs handled inside the fused kernel and its gathers
       ceed::Operator::MultComplex(*fused_r_, *fused_i_, x.Real(), x.Imag(), y.Real(), y.Imag(),
@@ -595,6 +598,7 @@ void ComplexParOperator::Mult(const ComplexVector &x, ComplexVector &y) const {
 
 void ComplexParOperator::MultTranspose(const ComplexVector &x, ComplexVector &y) const {
   // rap.cpp:521-556 (conforming spaces: the restriction transposed is the prolongation)
+  if (conf_) return RAP_->MultTranspose(x, y);
   Prolongate(x, ly_);
   A_->MultTranspose(ly_, lx_);
   RestrictFix(x, lx_, y);
@@ -602,6 +606,7 @@ void ComplexParOperator::MultTranspose(const ComplexVector &x, ComplexVector &y)
 
 void ComplexParOperator::MultHermitianTranspose(const ComplexVector &x, ComplexVector &y) const {
   // rap.cpp:558-593
+  if (conf_) return RAP_->MultHermitianTranspose(x, y);
   Prolongate(x, ly_);
   A_->MultHermitianTranspose(ly_, lx_);
   RestrictFix(x, lx_, y);

@@ -177,6 +177,7 @@ class ComplexParOperator : public ComplexOperator {
   const Context *ctx_;
   const Operator *Ar_, *Ai_;
   const Halo *halo_;
+  const Conforming *conf_ = nullptr;  // hanging-node constraints (one rank): every product goes through the two real ParOperators
   int n_true_, n_local_;
   std::unique_ptr<ComplexWrapperOperator> A_;  // local (L-vector) operator
   std::unique_ptr<ParOperator> RAPr_, RAPi_;
@@ -191,7 +192,8 @@ class ComplexParOperator : public ComplexOperator {
   void RestrictFix(const ComplexVector &x, ComplexVector &ly, ComplexVector &y) const;  // y = P^T ly, y[ess] = x | 0
 
 public:
-  ComplexParOperator(const Context &ctx, const Operator *Ar, const Operator *Ai, int n_true, const Halo *halo = nullptr);
+  ComplexParOperator(const Context &ctx, const Operator *Ar, const Operator *Ai, int n_true, const Halo *halo = nullptr,
+                     const Conforming *conf = nullptr);
   ~ComplexParOperator() override;
   // rap.cpp:436-462
   void SetEssentialTrueDofs(const int32_t *ess_host, int n_ess, ParOperator::DiagonalPolicy policy);

@@ -10,6 +10,20 @@ namespace palace {
 Operator *make_interp_operator(const Context &ctx, const pa_restriction_desc &rc, const pa_basis_desc &bc,
                                const pa_restriction_desc &rf, const pa_basis_desc &bf, const double *Ic,
                                const double *Io, const Halo *halo_c, int nt_c, int nt_f, int kind);
+Operator *make_conforming_interp_operator(const Context &ctx, const pa_restriction_desc &rc, const pa_basis_desc &bc,
+                                          const pa_restriction_desc &rf, const pa_basis_desc &bf, const double *Ic,
+                                          const double *Io, const Conforming *conf_c, int nt_c, int nt_f, int kind);
+
+namespace {
+// the p-prolongation / discrete interpolator from `dom`: through its halo, or through its hanging-node constraints
+Operator *make_interp_from(const FiniteElementSpace &dom, const pa_restriction_desc &rc, const pa_basis_desc &bc,
+                           const pa_restriction_desc &rf, const pa_basis_desc &bf, const double *Ic, const double *Io, int nt_f,
+                           int kind) {
+  if (dom.GetConforming())
+    return make_conforming_interp_operator(dom.GetContext(), rc, bc, rf, bf, Ic, Io, dom.GetConforming(), dom.GetTrueVSize(), nt_f, kind);
+  return make_interp_operator(dom.GetContext(), rc, bc, rf, bf, Ic, Io, dom.GetHalo(), dom.GetTrueVSize(), nt_f, kind);
+}
+}  // namespace
 
 Operator *make_dense_interp_operator(const Context &ctx, const pa_restriction_desc &rd, const pa_restriction_desc &rr,
                                      const double *M, const Halo *halo_d, int nt_d, int nt_r, int nmat, const uint8_t *mat_id);
@@ -479,7 +493,7 @@ const Operator &FiniteElementSpace::GetDiscreteInterpolator(const FiniteElementS
     const auto rn = aux.GetCeedElemRestriction(), rr = GetCeedElemRestriction();
     const auto bn = aux.GetCeedBasis(), br = GetCeedBasis();
     auto &slot = G_[&aux];
-    slot.reset(make_interp_operator(*ctx_, rn, bn, rr, br, nullptr, Dg.data(), aux.halo_, aux.true_vsize_, true_vsize_, 2));
+    slot.reset(make_interp_from(aux, rn, bn, rr, br, nullptr, Dg.data(), true_vsize_, 2));
     return *slot;
   }
   const int n = order_ + 1;
@@ -488,8 +502,18 @@ const Operator &FiniteElementSpace::GetDiscreteInterpolator(const FiniteElementS
   const auto rh = aux.GetCeedElemRestriction(), rn = GetCeedElemRestriction();
   const auto bh = aux.GetCeedBasis(), bn = GetCeedBasis();
   auto &slot = G_[&aux];
-  slot.reset(make_interp_operator(*ctx_, rh, bh, rn, bn, I.data(), Dg.data(), aux.halo_, aux.true_vsize_, true_vsize_, 1));
+  slot.reset(make_interp_from(aux, rh, bh, rn, bn, I.data(), Dg.data(), true_vsize_, 1));
   return *slot;
+}
+
+void FiniteElementSpace::SetConformingProlongation(int n_true, const int *row_ptr, const int32_t *col, const double *val) {
+  PA_REQUIRE(!halo_, "a halo and a conforming prolongation together are not supported (hanging nodes: one rank)");
+  PA_REQUIRE(n_true >= 0 && n_true <= vsize_, "conforming prolongation: more true dofs than local dofs");
+  for (const int32_t d : ess_tdofs_) PA_REQUIRE(d < n_true, "the essential true dofs set before do not fit the constrained space");
+  StreamGraph::Invalidate();
+  G_.clear();  // (interpolators built before carry the old true-dof count)
+  conf_ = std::make_unique<Conforming>(*ctx_, n_true, vsize_, row_ptr, col, val);
+  true_vsize_ = n_true;
 }
 
 const Operator &FiniteElementSpaceHierarchy::BuildProlongationAtLevel(std::size_t l) const {
@@ -505,6 +529,7 @@ const Operator &FiniteElementSpaceHierarchy::BuildProlongationAtLevel(std::size_
     PA_REQUIRE(c.GetFEType() == f.GetFEType() && c.GetMaxElementOrder() == f.GetMaxElementOrder() && c.GetElemSize() == f.GetElemSize(),
                "h-levels carry the same finite element collection on every mesh (fem/multigrid.hpp:103-112)");
     PA_REQUIRE(c.IsDense() == f.IsDense() && !c.GetHalo() && !f.GetHalo(), "refinement transfer: one rank, one kind of space");
+    PA_REQUIRE(!c.GetConforming() && !f.GetConforming(), "refinement transfer between spaces with hanging-node constraints is not built");
     const int P = f.GetElemSize(), nef = mf.GetNE(), nmat = mf.GetNumPointMatrices(), p = f.GetMaxElementOrder();
     std::vector<double> M;
     if (f.IsDense()) {
@@ -594,8 +619,7 @@ const Operator &FiniteElementSpaceHierarchy::BuildProlongationAtLevel(std::size_
   fem::LagrangeEval(xc, xf, Io, tmp);
   const auto rc = c.GetCeedElemRestriction(), rf = f.GetCeedElemRestriction();
   const auto bc = c.GetCeedBasis(), bf = f.GetCeedBasis();
-  P_[l].reset(make_interp_operator(c.GetContext(), rc, bc, rf, bf, Ic.data(), Io.data(), c.GetHalo(), c.GetTrueVSize(),
-                                   f.GetTrueVSize(), 0));
+  P_[l].reset(make_interp_from(c, rc, bc, rf, bf, Ic.data(), Io.data(), f.GetTrueVSize(), 0));
   return *P_[l];
 }
 
@@ -895,14 +919,14 @@ FespaceParOperator::FespaceParOperator(std::unique_ptr<Operator> &&A, const Fini
   PA_REQUIRE(local_ && local_->Height() == fespace.GetVSize() && local_->Width() == fespace.GetVSize(),
              "the local operator does not match the finite element space");
   par_ = std::make_unique<ParOperator>(*ctx_, *local_, fespace.GetTrueVSize(), nullptr, 0, ParOperator::DiagonalPolicy::DIAG_ONE,
-                                       fespace.GetHalo());
+                                       fespace.GetHalo(), fespace.GetConforming());
 }
 
 void FespaceParOperator::SetEssentialTrueDofs(const std::vector<int32_t> &tdofs, ParOperator::DiagonalPolicy policy) {
   ess_tdofs_ = tdofs;
   par_.reset();  // (releases the fused essential list of the local operator before a new wrapper claims it)
   par_ = std::make_unique<ParOperator>(*ctx_, *local_, fespace_->GetTrueVSize(), tdofs.data(), (int)tdofs.size(), policy,
-                                       fespace_->GetHalo());
+                                       fespace_->GetHalo(), fespace_->GetConforming());
 }
 
 }  // namespace palace

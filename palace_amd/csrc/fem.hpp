@@ -186,6 +186,13 @@ public:
     return offsets_[(size_t)e * elem_size_ + j];
   }
   const Halo *GetHalo() const { return halo_; }
+  // Hanging-node constraints of a space on a nonconforming mesh (one rank; what mfem::FiniteElementSpace::
+  // GetConformingProlongation() is after a nonconformal refinement): the local vector holds the n_true true dofs first, then
+  // the constrained ones, and P = [I; C] with C [GetVSize() - n_true][n_true] in CSR (host arrays; every column a true dof).
+  // Every ParOperator and transfer built from this space (BilinearForm::Assemble -> FespaceParOperator, the hierarchy's
+  // prolongations, the discrete interpolators) then applies P and P^T.  Not together with a halo.
+  void SetConformingProlongation(int n_true, const int *row_ptr, const int32_t *col, const double *val);
+  const Conforming *GetConforming() const { return conf_.get(); }
   pa_restriction_desc GetCeedElemRestriction() const;
   pa_basis_desc GetCeedBasis() const;
   // essential true dofs of the boundary conditions on this space (what FiniteElementSpace::GetEssentialTrueDofs
@@ -206,6 +213,7 @@ public:
 
 private:
   std::vector<double> local_interp_;
+  std::unique_ptr<Conforming> conf_;
 };
 
 // vdim copies of a scalar space -- mfem::FiniteElementSpace(mesh, fec, vdim, ordering) as far as GradientIntegrator needs it: the

@@ -46,6 +46,8 @@ amg::HostCsr AssembledLevelMatrix(const Operator &op, std::vector<char> &ess_fla
   PA_REQUIRE(par, "the algebraic coarse solvers need a ParOperator (the level operator of the multigrid hierarchy)");
   PA_REQUIRE(!par->GetHalo(), "the native AMG / AMS coarse solvers run on one rank (multi-rank: JACOBI_PCG or "
                               "CHEBYSHEV_JACOBI)");
+  PA_REQUIRE(!par->GetConforming(), "BOOMER_AMG / AMS on a level with hanging-node constraints need the assembled P^T A P (a sparse triple "
+                                    "product that is not built): use JACOBI, CHEBYSHEV_JACOBI or JACOBI_PCG at level 0");
   const auto &ess = par->GetEssentialTrueDofsHost();
   ess_flag.assign((size_t)op.Height(), 0);
   for (const int32_t d : ess) ess_flag[d] = 1;

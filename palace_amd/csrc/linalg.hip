@@ -1072,13 +1072,16 @@ __global__ void k_copy_fix(const double *__restrict__ ly, const double *__restri
 }  // namespace
 
 ParOperator::ParOperator(const Context &ctx, const Operator &A, int n_true, const int32_t *ess_host, int n_ess,
-                         DiagonalPolicy policy, const Halo *halo)
-    : Operator(n_true, n_true), ctx_(&ctx), A_(&A), halo_(halo), n_true_(n_true), n_local_(A.Height()),
+                         DiagonalPolicy policy, const Halo *halo, const Conforming *conf)
+    : Operator(n_true, n_true), ctx_(&ctx), A_(&A), halo_(halo), conf_(conf), n_true_(n_true), n_local_(A.Height()),
       n_ess_(n_ess), policy_(policy) {
   PA_REQUIRE(A.Height() == A.Width(), "ParOperator needs a square local operator");
   PA_REQUIRE(n_true <= n_local_, "more true dofs than local dofs");
-  PA_REQUIRE(halo != nullptr || n_true == n_local_, "local != true dofs requires a halo plan");
+  PA_REQUIRE(!(halo && conf), "ParOperator: a halo and a conforming prolongation together are not supported (hanging nodes: one rank)");
+  PA_REQUIRE(halo != nullptr || conf != nullptr || n_true == n_local_, "local != true dofs requires a halo plan or a conforming prolongation");
   if (halo) halo->Validate(n_true, n_local_);
+  if (conf)
+    PA_REQUIRE(conf->NumTrue() == n_true && conf->NumLocal() == n_local_, "the conforming prolongation does not match the operator's sizes");
   for (int i = 0; i < n_ess; i++) PA_REQUIRE(ess_host[i] >= 0 && ess_host[i] < n_true, "essential dof out of range");
   if (n_ess) d_ess_ = pa::dev_upload(ess_host, (size_t)n_ess, ctx.stream);
   if (n_ess) ess_host_.assign(ess_host, ess_host + n_ess);
@@ -1088,7 +1091,14 @@ ParOperator::ParOperator(const Context &ctx, const Operator &A, int n_true, cons
   // in place, instead of copying x and y through the L-vectors.
   // (the flagged index tables belong to the local operator: if another wrapper has fused a different list into it,
   // this one masks and fixes its rows outside the kernels instead of overwriting that list)
-  if (!halo && n_ess) {
+  // (with hanging-node constraints the local operator sees P tx, not x: nothing is fused, every path below is left alone and
+  // Mult is masked P / local apply / P^T with the essential rows)
+  if (conf && n_ess) {
+    std::vector<uint8_t> mask((size_t)n_true, 0);
+    for (int i = 0; i < n_ess; i++) mask[ess_host[i]] = 1;
+    d_ess_mask_ = pa::dev_upload(mask.data(), mask.size(), ctx.stream);
+  }
+  if (!halo && !conf && n_ess) {
     if (auto *c = dynamic_cast<const ceed::Operator *>(&A)) {
       const int st = pa_op_essential_state(c->Handle(), ess_host, n_ess);
       if (st == 0) const_cast<ceed::Operator *>(c)->SetEssential(ess_host, n_ess);
@@ -1125,7 +1135,7 @@ ParOperator::ParOperator(const Context &ctx, const Operator &A, int n_true, cons
       if (d < n_true) mask[d] |= 2;
     d_ess_mask_ = pa::dev_upload(mask.data(), mask.size(), ctx.stream);
   }
-  if (!halo) {
+  if (!halo && !conf) {
     if (auto *m = dynamic_cast<const CsrOperator *>(&A)) {
       d_csr_bc_ = m->EliminatedValues(d_ess_, n_ess, policy == DiagonalPolicy::DIAG_ONE);
       if (d_csr_bc_) A_csr_ = m;
@@ -1139,6 +1149,7 @@ ParOperator::~ParOperator() {
 }
 
 bool ParOperator::PrepareChebyStep() const {
+  if (conf_) return false;  // the step would have to run behind P^T: smoothers apply A and run the vector kernel
   if (A_fused_ && !halo_) return A_fused_->PrepareFusedStep();
   if (A_csr_ && !halo_) return A_csr_->PrepareChebyStep();  // assembled local operator, one rank: the step in the sparse product (csr_op.hip)
   // several ranks, direct form of the peer transport (round 6): the local gather consumes the dofs no other rank shares, the merged
@@ -1157,6 +1168,7 @@ void ParOperator::SplitStep(const Vector &x, const pa_split_step &st0, const Hal
   halo_->RestrictAddDirectStep(d_ess_mask_, ly_.Data(), hs, c.stream);
 }
 void ParOperator::MultChebyStep(const Vector &x, const ChebyStepArgs &a) const {
+  PA_REQUIRE(!conf_, "MultChebyStep is not available with a conforming prolongation (PrepareChebyStep() says so)");
   if (A_fused_ && !halo_) return A_fused_->MultChebyStepEssential(x, a, policy_ == DiagonalPolicy::DIAG_ONE);
   if (A_csr_ && !halo_) return A_csr_->MultChebyStepValues(d_csr_bc_, x, a);  // (essential rows / columns live in the values)
   PA_REQUIRE(A_split_ && halo_, "MultChebyStep: PrepareChebyStep found no fused form");
@@ -1165,6 +1177,7 @@ void ParOperator::MultChebyStep(const Vector &x, const ChebyStepArgs &a) const {
             HaloStep{1, a.sd, a.sr, a.dinv->Data(), a.r0->Data(), x.Data(), ep, a.out->Data(), a.add ? 1 : 0, nullptr});
 }
 void ParOperator::MultResidual(const Vector &y, const Vector &b, Vector *res, const Vector *dinv, double c0, Vector *d0) const {
+  PA_REQUIRE(!conf_, "MultResidual is not available with a conforming prolongation (PrepareChebyStep() says so)");
   if (A_fused_ && !halo_) return A_fused_->MultResidualEssential(y, b, res, dinv, c0, d0, policy_ == DiagonalPolicy::DIAG_ONE);
   if (A_csr_ && !halo_) return A_csr_->MultResidualValues(d_csr_bc_, y, b, res, dinv, c0, d0);
   PA_REQUIRE(A_split_ && halo_, "MultResidual: PrepareChebyStep found no fused form");
@@ -1173,9 +1186,23 @@ void ParOperator::MultResidual(const Vector &y, const Vector &b, Vector *res, co
   SplitStep(y, pa_split_step{2, 0.0, c0, di, b.Data(), nullptr, o, 0, r, nullptr, nullptr},
             HaloStep{2, 0.0, c0, di, b.Data(), nullptr, nullptr, o, 0, r});
 }
+void ParOperator::MultConforming(const Vector &x, Vector &y, bool transpose, bool add, double a) const {
+  // rap.cpp:195-361 with a sparse P: lx = P tx (tx = x, tx[ess] = 0, masked inside the kernel), ly = A lx, y (+)= a P^T ly with
+  // the essential rows x[ess] | 0.  (x may be y: P has read all of x before P^T writes, and P^T reads x[i] only where it writes y[i])
+  const Context &c = *ctx_;
+  conf_->Prolongate(x.Data(), lx_.Data(), d_ess_mask_, c.stream);
+  if (transpose)
+    A_->MultTranspose(lx_, ly_);
+  else
+    A_->Mult(lx_, ly_);
+  const int fix = n_ess_ ? (policy_ == DiagonalPolicy::DIAG_ONE ? Conforming::FIX_ONE : Conforming::FIX_ZERO) : 0;
+  conf_->Restrict(ly_.Data(), y.Data(), fix | (add ? Conforming::ADD : 0), a, d_ess_mask_, x.Data(), c.stream);
+}
+
 void ParOperator::Mult(const Vector &x, Vector &y) const {
   // rap.cpp:195-234.  tx = x, tx[ess] = 0; lx = P tx; ly = A lx; y = P^T ly; y[ess] = x[ess] | 0
   const Context &c = *ctx_;
+  if (conf_) return MultConforming(x, y, false, false, 1.0);
   if (A_fused_ && x.Data() != y.Data()) {
     if (A_fused_->MultEssentialDiag(x, y, policy_ == DiagonalPolicy::DIAG_ONE)) return;
     if (policy_ == DiagonalPolicy::DIAG_ONE)
@@ -1242,6 +1269,7 @@ void ParOperator::Mult(const Vector &x, Vector &y) const {
 void ParOperator::MultTranspose(const Vector &x, Vector &y) const {
   // rap.cpp:236-275.  ty = x, ty[ess] = 0; ly = P ty; lx = A^T ly; y = P^T lx; y[ess] = x[ess] | 0
   if (A_->IsSymmetric()) return Mult(x, y);
+  if (conf_) return MultConforming(x, y, true, false, 1.0);
   const Context &c = *ctx_;
   Vector tx(lx_.Data(), n_true_);
   linalg::Copy(c, x, tx);
@@ -1262,6 +1290,7 @@ void ParOperator::MultTranspose(const Vector &x, Vector &y) const {
 }
 
 void ParOperator::AddMultTranspose(const Vector &x, Vector &y, double a) const {
+  if (conf_) return MultConforming(x, y, !A_->IsSymmetric(), true, a);  // (the sum rides in the epilogue of P^T)
   if (tt_.Size() != n_true_) tt_.SetSize(n_true_);
   MultTranspose(x, tt_);
   linalg::AXPY(*ctx_, a, tt_, y);
@@ -1286,6 +1315,7 @@ void ParOperator::Mult2(const Vector &x0, const Vector &x1, Vector &y0, Vector &
 }
 
 void ParOperator::AddMult(const Vector &x, Vector &y, double a) const {
+  if (conf_) return MultConforming(x, y, false, true, a);
   if (tt_.Size() != n_true_) tt_.SetSize(n_true_);
   Mult(x, tt_);
   linalg::AXPY(*ctx_, a, tt_, y);
@@ -1294,6 +1324,22 @@ void ParOperator::AddMult(const Vector &x, Vector &y, double a) const {
 void ParOperator::EliminateRHS(const Vector &x, Vector &b) const {
   // rap.cpp:56-82: tx = 0, tx[ess] = x[ess]; b -= P^T A P tx (unconstrained A); b[ess] = x[ess] | 0
   const Context &c = *ctx_;
+  if (conf_) {
+    // tx lives in a T-vector of its own: P reads it while it writes the local vector
+    if (tt_.Size() != n_true_) tt_.SetSize(n_true_);
+    linalg::Fill(c, tt_, 0.0);
+    if (n_ess_) linalg::SetSubVector(c, tt_, d_ess_, n_ess_, x);
+    conf_->Prolongate(tt_.Data(), lx_.Data(), nullptr, c.stream);
+    A_->Mult(lx_, ly_);
+    conf_->Restrict(ly_.Data(), b.Data(), Conforming::ADD, -1.0, nullptr, nullptr, c.stream);
+    if (n_ess_) {
+      if (policy_ == DiagonalPolicy::DIAG_ONE)
+        linalg::SetSubVector(c, b, d_ess_, n_ess_, x);
+      else
+        linalg::SetSubVector(c, b, d_ess_, n_ess_, 0.0);
+    }
+    return;
+  }
   Vector tx(lx_.Data(), n_true_);
   linalg::Fill(c, tx, 0.0);
   if (n_ess_) linalg::SetSubVector(c, tx, d_ess_, n_ess_, x);
@@ -1316,6 +1362,13 @@ void ParOperator::AssembleDiagonal(Vector &diag) const {
   // rap.cpp:154-193 (conforming meshes: |P|^T = P^T)
   const Context &c = *ctx_;
   A_->AssembleDiagonal(ly_);
+  if (conf_) {
+    // an AMR mesh: |P|^T d, entry-wise absolute values, as the reference (rap.cpp:163-175, AbsMultTranspose) -- the signed
+    // product does not give a convergent diagonal
+    conf_->Restrict(ly_.Data(), diag.Data(), Conforming::ABS, 1.0, nullptr, nullptr, c.stream);
+    if (n_ess_) linalg::SetSubVector(c, diag, d_ess_, n_ess_, policy_ == DiagonalPolicy::DIAG_ONE ? 1.0 : 0.0);
+    return;
+  }
   if (halo_) halo_->RestrictAdd(ly_.Data(), c.stream);
   Vector ty(ly_.Data(), n_true_);
   linalg::Copy(c, ty, diag);

@@ -376,9 +376,45 @@ public:
   void MultResidualValues(const double *d_vals, const Vector &y, const Vector &b, Vector *res, const Vector *dinv, double c0, Vector *d0) const;
 };
 
+// Conforming prolongation of a space with hanging-entity constraints on one rank (nonconforming refinement of tensor elements,
+// utils/geodata.cpp:174-186: the reference's P is then a sparse matrix, not only a halo; linalg/rap.cpp:65, :212-216).  Local
+// vector layout as for a halo: true dofs [0, n_true), then the constrained dofs; P = [I; C] with C [n_local - n_true, n_true] in
+// CSR.  Both products are one launch each (pa_conform.hip), allocate nothing and never synchronise, so they can be recorded
+// into the solvers' graphs; the transposed product gathers through an inverted index in a fixed order (no atomics: bitwise
+// reproducible).
+class Conforming {
+  int n_true_, n_con_;
+  int fwd_lanes_ = 1, tr_lanes_ = 1;  // lanes that share one row (powers of two, from the longest row)
+  int n_touched_ = 0;                 // true dofs with at least one constrained dof hanging on them
+  int *d_row_ptr_ = nullptr, *d_t_ptr_ = nullptr;
+  int32_t *d_col_ = nullptr, *d_t_dof_ = nullptr, *d_t_slave_ = nullptr;
+  double *d_val_ = nullptr, *d_t_val_ = nullptr;
+  uint8_t *d_touched_ = nullptr;  // one byte per true dof: its row of C^T is not empty (the copy part of Restrict leaves it alone)
+  void Free();
+
+public:
+  enum : int { ADD = 1, ABS = 2, FIX_ONE = 4, FIX_ZERO = 8 };
+  Conforming(const Context &ctx, int n_true, int n_local, const int *row_ptr, const int32_t *col, const double *val);
+  ~Conforming();
+  Conforming(const Conforming &) = delete;
+  Conforming &operator=(const Conforming &) = delete;
+  int NumTrue() const { return n_true_; }
+  int NumLocal() const { return n_true_ + n_con_; }
+  int ForwardLanes() const { return fwd_lanes_; }
+  int TransposeLanes() const { return tr_lanes_; }
+  // lx = P tx, tx = x with the entries flagged in ess_mask (one byte per true dof, bit 1; may be nullptr) read as zero
+  void Prolongate(const double *x, double *lx, const uint8_t *ess_mask, hipStream_t stream) const;
+  // y = P^T ly (ABS: |P|^T ly; ADD: y += a P^T ly), then the essential rows of ParOperator::Mult: where ess_mask is set the
+  // value is x_ess[i] (FIX_ONE) or 0 (FIX_ZERO) instead.  y may be x_ess; y must not overlap ly.
+  void Restrict(const double *ly, double *y, int flags, double a, const uint8_t *ess_mask, const double *x_ess,
+                hipStream_t stream) const;
+};
+
 // ParOperator (rap.cpp:154-234): y = P^T A P x with essential-dof handling.  True dofs of this
 // rank are the first n_true entries of the local (L-) vector; shared dofs owned elsewhere follow
-// (see comm.hpp); with one rank P is the identity.
+// (see comm.hpp); with one rank P is the identity, or the Conforming prolongation of a space with
+// hanging nodes (then Mult is three launches -- masked P, the local apply, P^T with the essential rows --
+// and the fused and split forms are not available: smoothers and PCG take their plain paths).
 class ParOperator : public Operator {
 public:
   enum class DiagonalPolicy { DIAG_ZERO = 0, DIAG_ONE = 1 };
@@ -394,6 +430,7 @@ private:
   const CsrOperator *A_csr_ = nullptr;       // single rank, assembled local operator: BCs eliminated in the matrix values
   double *d_csr_bc_ = nullptr;               // ... this wrapper's copy of them (CsrOperator::EliminatedValues)
   const Halo *halo_;
+  const Conforming *conf_ = nullptr;  // hanging-node constraints (one rank; never together with a halo)
   int n_true_, n_local_;
   int32_t *d_ess_ = nullptr;
   int n_ess_ = 0;
@@ -404,7 +441,7 @@ private:
 
 public:
   ParOperator(const Context &ctx, const Operator &A, int n_true, const int32_t *ess_host, int n_ess,
-              DiagonalPolicy policy, const Halo *halo = nullptr);
+              DiagonalPolicy policy, const Halo *halo = nullptr, const Conforming *conf = nullptr);
   ~ParOperator() override;
   const int32_t *GetEssentialTrueDofs() const { return d_ess_; }
   int NumEssentialTrueDofs() const { return n_ess_; }
@@ -425,6 +462,7 @@ public:
                     Vector *d0 = nullptr) const override;  // the essential list lives in the local operator's index tables
   DiagonalPolicy GetDiagonalPolicy() const { return policy_; }
   const Halo *GetHalo() const { return halo_; }
+  const Conforming *GetConforming() const { return conf_; }
   void Mult(const Vector &x, Vector &y) const override;
   // rap.cpp:236-275: y = P^T A^T P x with the same essential-dof handling (a symmetric local operator takes the fused
   // forward path)
@@ -441,6 +479,8 @@ public:
 
 private:
   mutable Vector tt_;
+  // y (+)= a P^T A(^T) P x with the essential handling, P the conforming prolongation: three launches
+  void MultConforming(const Vector &x, Vector &y, bool transpose, bool add, double a) const;
 };
 
 // Solver<Operator> (solver.hpp:21-65)

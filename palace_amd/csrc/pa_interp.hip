@@ -1050,6 +1050,7 @@ void launch_rt_prolong_hex(bool transpose, int pc, int pf, int ne, const int32_t
 class InterpOperator : public Operator {
   const Context *ctx_;
   const Halo *halo_c_;
+  const Conforming *conf_c_ = nullptr;  // hanging-node constraints of the coarse (domain) space: P_c is a sparse product
   int kind_ = 0;
   int fe_type_, pc_, pf_, ne_, nl_c_, nl_f_, nt_c_, nt_f_;
   int32_t *d_lidx_c_ = nullptr, *d_lidx_f_ = nullptr;
@@ -1099,8 +1100,8 @@ class InterpOperator : public Operator {
 public:
   InterpOperator(const Context &ctx, const pa_restriction_desc &rc, const pa_basis_desc &bc,
                  const pa_restriction_desc &rf, const pa_basis_desc &bf, const double *Ic, const double *Io,
-                 const Halo *halo_c, int nt_c, int nt_f, int kind)
-      : Operator(nt_f, nt_c), ctx_(&ctx), halo_c_(halo_c), kind_(kind), fe_type_(bc.fe_type), pc_(bc.order),
+                 const Halo *halo_c, int nt_c, int nt_f, int kind, const Conforming *conf_c = nullptr)
+      : Operator(nt_f, nt_c), ctx_(&ctx), halo_c_(halo_c), conf_c_(conf_c), kind_(kind), fe_type_(bc.fe_type), pc_(bc.order),
         pf_(bf.order), ne_(rc.num_elem), nl_c_(rc.lsize), nl_f_(rf.lsize), nt_c_(nt_c), nt_f_(nt_f) {
     if (kind == 1) {
       PA_REQUIRE(bc.fe_type == PA_FE_H1 && bf.fe_type == PA_FE_HCURL && bc.order == bf.order,
@@ -1124,7 +1125,9 @@ public:
     PA_REQUIRE(pf_ + 1 <= kMaxN && pc_ <= pf_, "unsupported orders for prolongation");
     PA_REQUIRE((Ic || kind == 2) && (kind == 0 && fe_type_ == PA_FE_H1 ? true : Io != nullptr), "1-D interpolation matrices missing");
     PA_REQUIRE(nt_c <= nl_c_ && nt_f <= nl_f_, "true dof counts exceed local sizes");
-    PA_REQUIRE(halo_c || nt_c == nl_c_, kind == 2 ? "ghost dofs on the Nedelec side need a halo plan" : "ghost dofs on the coarse level need a halo plan");
+    PA_REQUIRE(!(halo_c && conf_c), "a halo and a conforming prolongation together are not supported (hanging nodes: one rank)");
+    PA_REQUIRE(!conf_c || (conf_c->NumTrue() == nt_c && conf_c->NumLocal() == nl_c_), "the conforming prolongation does not match the domain space");
+    PA_REQUIRE(halo_c || conf_c || nt_c == nl_c_, kind == 2 ? "ghost dofs on the Nedelec side need a halo plan" : "ghost dofs on the coarse level need a halo plan");
     const int Pc = bc.fe_type == PA_FE_HCURL  ? 3 * pc_ * (pc_ + 1) * (pc_ + 1)
                    : bc.fe_type == PA_FE_HDIV ? 3 * pc_ * pc_ * (pc_ + 1)
                                               : (pc_ + 1) * (pc_ + 1) * (pc_ + 1);
@@ -1188,7 +1191,10 @@ public:
       return;
     }
     Vector tc(lc_.Data(), nt_c_);
-    linalg::Copy(c, x, tc);
+    if (conf_c_)
+      conf_c_->Prolongate(x.Data(), lc_.Data(), nullptr, c.stream);  // copy and constrained tail in one launch
+    else
+      linalg::Copy(c, x, tc);
     if (halo_c_) halo_c_->Prolongate(lc_.Data(), c.stream);
     launch<false>(lc_.Data(), lf_.Data());  // every fine local dof is stored exactly once
     Vector tf(lf_.Data(), nt_f_);
@@ -1212,10 +1218,22 @@ public:
     launch_k_gather(nl_c_, d_tptr_c_, d_tent_c_, d_ye_c_, lc_.Data(), c.stream);
     PA_HIP(hipGetLastError());
     if (halo_c_) halo_c_->RestrictAdd(lc_.Data(), c.stream);
+    if (conf_c_) {  // x_c = P_c^T (...): the fine side's constrained tail was zero-filled above (R_f^T)
+      conf_c_->Restrict(lc_.Data(), y.Data(), 0, 1.0, nullptr, nullptr, c.stream);
+      return;
+    }
     Vector tc(lc_.Data(), nt_c_);
     linalg::Copy(c, tc, y);
   }
 };
+
+// the same with hanging-node constraints on the domain space (the range space's are its layout alone: R_f takes the head of the
+// local vector, R_f^T fills the tail with zeros): the true-dof operator is R_f I P_c
+Operator *make_conforming_interp_operator(const Context &ctx, const pa_restriction_desc &rc, const pa_basis_desc &bc,
+                                          const pa_restriction_desc &rf, const pa_basis_desc &bf, const double *Ic,
+                                          const double *Io, const Conforming *conf_c, int nt_c, int nt_f, int kind) {
+  return new InterpOperator(ctx, rc, bc, rf, bf, Ic, Io, nullptr, nt_c, nt_f, kind, conf_c);
+}
 
 Operator *make_interp_operator(const Context &ctx, const pa_restriction_desc &rc, const pa_basis_desc &bc,
                                const pa_restriction_desc &rf, const pa_basis_desc &bf, const double *Ic,

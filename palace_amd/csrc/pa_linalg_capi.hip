@@ -18,6 +18,9 @@ Operator *make_dense_interp_operator(const Context &ctx, const pa_restriction_de
 Operator *make_interp_operator(const Context &ctx, const pa_restriction_desc &rc, const pa_basis_desc &bc,
                                const pa_restriction_desc &rf, const pa_basis_desc &bf, const double *Ic,
                                const double *Io, const Halo *halo_c, int nt_c, int nt_f, int kind);
+Operator *make_conforming_interp_operator(const Context &ctx, const pa_restriction_desc &rc, const pa_basis_desc &bc,
+                                          const pa_restriction_desc &rf, const pa_basis_desc &bf, const double *Ic,
+                                          const double *Io, const Conforming *conf_c, int nt_c, int nt_f, int kind);
 }
 
 struct pa_context {
@@ -30,6 +33,9 @@ struct pa_context {
 };
 struct pa_halo {
   std::unique_ptr<Halo> halo;
+};
+struct pa_conform {
+  std::unique_ptr<Conforming> conf;
 };
 struct pa_par_op {
   pa_context *ctx;
@@ -1151,6 +1157,112 @@ int pa_gradient_create(pa_context *ctx, const pa_restriction_desc *rh, const pa_
     p->op.reset(make_interp_operator(ctx->ctx, *rh, *bh, *rn, *bn, I.data(), Dg,
                                      h1_halo ? h1_halo->halo.get() : nullptr, nt_h1, nt_nd, 1));
     *G = p;
+  });
+}
+/* ---- conforming prolongation with hanging-entity constraints (pa_conform.hip) ------------------------------------ */
+int pa_conform_create(pa_context *ctx, int n_true, int n_local, const int *row_ptr, const int32_t *col, const double *val,
+                      pa_conform **c) {
+  return guarded([&] {
+    PA_REQUIRE(ctx && c, "null argument");
+    auto *p = new pa_conform;
+    std::unique_ptr<pa_conform> hold(p);
+    p->conf = std::make_unique<Conforming>(ctx->ctx, n_true, n_local, row_ptr, col, val);
+    *c = hold.release();
+  });
+}
+void pa_conform_destroy(pa_conform *c) { delete c; }
+int pa_conform_prolongate(pa_context *ctx, pa_conform *c, const double *x, double *lx, const uint8_t *ess_mask) {
+  return guarded([&] {
+    PA_REQUIRE(ctx && c && x && lx, "null argument");
+    c->conf->Prolongate(x, lx, ess_mask, ctx->ctx.stream);
+  });
+}
+int pa_conform_restrict(pa_context *ctx, pa_conform *c, const double *ly, double *y, int flags, double a, const uint8_t *ess_mask,
+                        const double *x_ess) {
+  return guarded([&] {
+    PA_REQUIRE(ctx && c && ly && y, "null argument");
+    PA_REQUIRE((flags & ~(PA_CONFORM_ADD | PA_CONFORM_ABS | PA_CONFORM_FIX_ONE | PA_CONFORM_FIX_ZERO)) == 0, "unknown flag");
+    c->conf->Restrict(ly, y, flags, a, ess_mask, x_ess, ctx->ctx.stream);
+  });
+}
+int pa_conform_lanes(const pa_conform *c, int which) {
+  return c ? (which ? c->conf->TransposeLanes() : c->conf->ForwardLanes()) : 0;
+}
+int pa_par_op_create_conforming(pa_context *ctx, pa_op *local, int n_true, const int32_t *ess, int n_ess, int policy,
+                                pa_conform *conf, pa_par_op **A) {
+  return guarded([&] {
+    PA_REQUIRE(ctx && local && conf && A, "null argument");
+    auto p = std::make_unique<pa_par_op>();
+    p->ctx = ctx;
+    p->local = std::make_unique<ceed::Operator>(ctx->ctx, local, false);
+    p->op = std::make_unique<ParOperator>(ctx->ctx, *p->local, n_true, ess, n_ess,
+                                          policy == PA_DIAG_ONE ? ParOperator::DiagonalPolicy::DIAG_ONE
+                                                                : ParOperator::DiagonalPolicy::DIAG_ZERO,
+                                          nullptr, conf->conf.get());
+    *A = p.release();
+  });
+}
+int pa_par_sum_op_create_conforming(pa_context *ctx, int nterms, pa_op *const *locals, const double *coeffs, int n_true,
+                                    const int32_t *ess, int n_ess, int policy, pa_conform *conf, pa_par_op **A) {
+  return guarded([&] {
+    PA_REQUIRE(ctx && locals && coeffs && conf && A && nterms >= 1, "bad argument");
+    auto p = std::make_unique<pa_par_op>();
+    p->ctx = ctx;
+    const int n = pa_op_height(locals[0]);
+    p->sum = std::make_unique<SumOperator>(ctx->ctx, n, n);
+    for (int k = 0; k < nterms; k++) {
+      PA_REQUIRE(locals[k], "null local operator");
+      p->terms.push_back(std::make_unique<ceed::Operator>(ctx->ctx, locals[k], false));
+      p->sum->AddOperator(*p->terms.back(), coeffs[k]);
+    }
+    p->op = std::make_unique<ParOperator>(ctx->ctx, *p->sum, n_true, ess, n_ess,
+                                          policy == PA_DIAG_ONE ? ParOperator::DiagonalPolicy::DIAG_ONE
+                                                                : ParOperator::DiagonalPolicy::DIAG_ZERO,
+                                          nullptr, conf->conf.get());
+    *A = p.release();
+  });
+}
+int pa_par_op_fuses_essential(const pa_par_op *A) { return (A && A->op && A->op->FusesEssential()) ? 1 : 0; }
+int pa_par_op_prepare_cheby_step(pa_par_op *A) {
+  int out = 0;
+  if (A && A->op) (void)guarded([&] { out = A->op->PrepareChebyStep() ? 1 : 0; });
+  return out;
+}
+int pa_complex_par_op_create_conforming(pa_context *ctx, pa_op *Ar, pa_op *Ai, int n_true, pa_conform *conf,
+                                        pa_complex_par_op **A) {
+  return guarded([&] {
+    PA_REQUIRE(ctx && (Ar || Ai) && conf && A, "null argument");
+    auto p = std::make_unique<pa_complex_par_op>();
+    p->ctx = ctx;
+    if (Ar) p->local_r = std::make_unique<ceed::Operator>(ctx->ctx, Ar, false);
+    if (Ai) p->local_i = std::make_unique<ceed::Operator>(ctx->ctx, Ai, false);
+    p->op = std::make_unique<ComplexParOperator>(ctx->ctx, p->local_r.get(), p->local_i.get(), n_true, nullptr, conf->conf.get());
+    *A = p.release();
+  });
+}
+int pa_interp_create_conforming(pa_context *ctx, const pa_restriction_desc *rc, const pa_basis_desc *bc,
+                                const pa_restriction_desc *rf, const pa_basis_desc *bf, const double *Ic, const double *Io,
+                                pa_conform *coarse_conf, int nt_c, int nt_f, pa_interp **P) {
+  return guarded([&] {
+    PA_REQUIRE(ctx && rc && bc && rf && bf && coarse_conf && P, "null argument");
+    auto p = std::make_unique<pa_interp>();
+    p->ctx = ctx;
+    p->op.reset(make_conforming_interp_operator(ctx->ctx, *rc, *bc, *rf, *bf, Ic, Io, coarse_conf->conf.get(), nt_c, nt_f, 0));
+    *P = p.release();
+  });
+}
+int pa_gradient_create_conforming(pa_context *ctx, const pa_restriction_desc *rh, const pa_basis_desc *bh,
+                                  const pa_restriction_desc *rn, const pa_basis_desc *bn, const double *Dg, pa_conform *h1_conf,
+                                  int nt_h1, int nt_nd, pa_interp **G) {
+  return guarded([&] {
+    PA_REQUIRE(ctx && rh && bh && rn && bn && Dg && h1_conf && G, "null argument");
+    const int n = bn->order + 1;
+    std::vector<double> I((size_t)n * n, 0.0);
+    for (int i = 0; i < n; i++) I[(size_t)i * n + i] = 1.0;
+    auto p = std::make_unique<pa_interp>();
+    p->ctx = ctx;
+    p->op.reset(make_conforming_interp_operator(ctx->ctx, *rh, *bh, *rn, *bn, I.data(), Dg, h1_conf->conf.get(), nt_h1, nt_nd, 1));
+    *G = p.release();
   });
 }
 int pa_curl_create(pa_context *ctx, const pa_restriction_desc *rn, const pa_basis_desc *bn, const pa_restriction_desc *rr,

@@ -414,8 +414,78 @@ class Halo:
             pass
 
 
+class Conforming:
+    """Conforming prolongation P = [I; C] of a space with hanging-entity constraints on one rank (pa_conform_create): `C` a
+    scipy CSR matrix [n_local - n_true, n_true] whose columns are all true dofs (fem/nchex.py: NCSpace.C), or an NCSpace."""
+
+    def __init__(self, ctx: Context, C_or_space, n_true=None, n_local=None):
+        self.ctx = ctx
+        Cm = getattr(C_or_space, "C", C_or_space).tocsr()
+        self.n_true = Cm.shape[1] if n_true is None else n_true
+        self.n_local = self.n_true + Cm.shape[0] if n_local is None else n_local
+        rp = np.ascontiguousarray(Cm.indptr, dtype=np.int32)
+        col = np.ascontiguousarray(Cm.indices, dtype=np.int32)
+        val = np.ascontiguousarray(Cm.data, dtype=np.float64)
+        self.handle = C.c_void_p()
+        L = _L()
+        L.pa_conform_create.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.pa_conform_destroy.restype = None
+        L.pa_conform_destroy.argtypes = [C.c_void_p]
+        L.pa_conform_prolongate.argtypes = [C.c_void_p] * 5
+        L.pa_conform_restrict.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_void_p]
+        L.pa_conform_lanes.argtypes = [C.c_void_p, C.c_int]
+        _lib.check(L.pa_conform_create(ctx.handle, self.n_true, self.n_local, _ptr(rp), _ptr(col), _ptr(val), C.byref(self.handle)))
+
+    ADD, ABS, FIX_ONE, FIX_ZERO = 1, 2, 4, 8
+
+    def lanes(self, transpose=False):
+        return int(_L().pa_conform_lanes(self.handle, int(transpose)))
+
+    def prolongate(self, x, lx, ess_mask=None):
+        """lx = P x (entries flagged in the uint8 tensor ess_mask read as zero): one launch."""
+        assert x.numel() == self.n_true and lx.numel() == self.n_local and (ess_mask is None or ess_mask.numel() == self.n_true)
+        _lib.check(_L().pa_conform_prolongate(self.ctx.handle, self.handle, C.c_void_p(x.data_ptr()), C.c_void_p(lx.data_ptr()),
+                                              C.c_void_p(ess_mask.data_ptr()) if ess_mask is not None else None))
+        return lx
+
+    def restrict(self, ly, y, flags=0, a=1.0, ess_mask=None, x_ess=None):
+        """y = P^T ly (ABS: |P|^T; ADD: y += a P^T ly; FIX_ONE / FIX_ZERO: rows flagged in ess_mask take x_ess / 0): one launch."""
+        assert ly.numel() == self.n_local and y.numel() == self.n_true and (ess_mask is None or ess_mask.numel() == self.n_true)
+        assert x_ess is None or x_ess.numel() == self.n_true
+        _lib.check(_L().pa_conform_restrict(self.ctx.handle, self.handle, C.c_void_p(ly.data_ptr()), C.c_void_p(y.data_ptr()),
+                                            int(flags), float(a),
+                                            C.c_void_p(ess_mask.data_ptr()) if ess_mask is not None else None,
+                                            C.c_void_p(x_ess.data_ptr()) if x_ess is not None else None))
+        return y
+
+    def __del__(self):
+        try:
+            _L().pa_conform_destroy(self.handle)
+        except Exception:
+            pass
+
+
+def _default_true(space):
+    """True dofs of a space when the caller names none: all its dofs, or the unconstrained ones of an nchex.NCSpace."""
+    return space.n_true if hasattr(space, "C") and hasattr(space, "n_true") else space.ndofs
+
+
+def _one_of(halo, conforming):
+    if halo is not None and conforming is not None:
+        raise ValueError("a halo and a conforming prolongation together are not supported (hanging nodes: one rank)")
+
+
 class ParOperator:
     """palace::ParOperator (rap.cpp:154-234) on T-vectors."""
+
+    def fuses_essential(self):
+        """ParOperator::FusesEssential(): the essential dofs ride in the local apply (never with a conforming prolongation)."""
+        return bool(_L().pa_par_op_fuses_essential(self.handle))
+
+    def prepare_cheby_step(self):
+        """ParOperator::PrepareChebyStep(): the operator has the fused smoother step (never with a conforming prolongation).
+        A set-up call, not a pure query: where the form exists the local operator prepares it on the way."""
+        return bool(_L().pa_par_op_prepare_cheby_step(self.handle))
 
     def direct_form(self):
         """1: the multi-rank Mult runs without L-vector copies (peer transport + split-vector apply), 0: available, off, -1: n/a."""
@@ -424,12 +494,17 @@ class ParOperator:
     def set_direct(self, on=True):
         _lib.check(_L().pa_par_op_set_direct(self.handle, int(bool(on))))
 
-    def __init__(self, ctx: Context, local: Operator, ess_tdofs, diag_policy=DIAG_ONE, n_true=None, halo=None):
-        self.ctx, self.local, self.halo = ctx, local, halo
-        self.n = local.height if n_true is None else n_true
+    def __init__(self, ctx: Context, local: Operator, ess_tdofs, diag_policy=DIAG_ONE, n_true=None, halo=None, conforming=None):
+        _one_of(halo, conforming)
+        self.ctx, self.local, self.halo, self.conforming = ctx, local, halo, conforming
+        self.n = (conforming.n_true if conforming is not None else local.height) if n_true is None else n_true
         ess = np.ascontiguousarray(ess_tdofs, dtype=np.int32)
         self.ess = ess
         self.handle = C.c_void_p()
+        if conforming is not None:
+            _lib.check(_L().pa_par_op_create_conforming(ctx.handle, local.handle, self.n, _ptr(ess), ess.size, diag_policy,
+                                                        conforming.handle, C.byref(self.handle)))
+            return
         _lib.check(_L().pa_par_op_create(ctx.handle, local.handle, self.n, _ptr(ess), ess.size, diag_policy,
                                          halo.handle if halo else None, C.byref(self.handle)))
 
@@ -479,14 +554,19 @@ class AssembledParOperator(ParOperator):
 class ParSumOperator(ParOperator):
     """BuildParSumOperator (rap.cpp:843-919): ParOperator around sum_k coeffs[k] * locals[k]."""
 
-    def __init__(self, ctx: Context, locals_, coeffs, ess_tdofs, diag_policy=DIAG_ONE, n_true=None, halo=None):
-        self.ctx, self.local, self.halo = ctx, list(locals_), halo
-        self.n = self.local[0].height if n_true is None else n_true
+    def __init__(self, ctx: Context, locals_, coeffs, ess_tdofs, diag_policy=DIAG_ONE, n_true=None, halo=None, conforming=None):
+        _one_of(halo, conforming)
+        self.ctx, self.local, self.halo, self.conforming = ctx, list(locals_), halo, conforming
+        self.n = (conforming.n_true if conforming is not None else self.local[0].height) if n_true is None else n_true
         ess = np.ascontiguousarray(ess_tdofs, dtype=np.int32)
         self.ess = ess
         hs = (C.c_void_p * len(self.local))(*[o.handle for o in self.local])
         cs = np.ascontiguousarray(coeffs, dtype=np.float64)
         self.handle = C.c_void_p()
+        if conforming is not None:
+            _lib.check(_L().pa_par_sum_op_create_conforming(ctx.handle, len(self.local), hs, _ptr(cs), self.n, _ptr(ess), ess.size,
+                                                            diag_policy, conforming.handle, C.byref(self.handle)))
+            return
         _lib.check(_L().pa_par_sum_op_create(ctx.handle, len(self.local), hs, _ptr(cs), self.n, _ptr(ess), ess.size,
                                              diag_policy, halo.handle if halo else None, C.byref(self.handle)))
 
@@ -713,8 +793,11 @@ def gmres(ctx, A: ParOperator, precond=None, rel_tol=0.0, abs_tol=0.0, max_it=10
 class Interp:
     """p-prolongation between two spaces on the same mesh (bilinearform.cpp:203-282)."""
 
-    def __init__(self, ctx, space_c, space_f, coarse_halo=None, n_true_c=None, n_true_f=None):
-        self.ctx = ctx
+    def __init__(self, ctx, space_c, space_f, coarse_halo=None, n_true_c=None, n_true_f=None, conforming=None):
+        """conforming: the Conforming prolongation of the coarse space (hanging nodes: R_f I P_c on true-dof vectors; the
+        fine space's constraints enter through n_true_f alone)."""
+        _one_of(coarse_halo, conforming)
+        self.ctx, self.conforming = ctx, conforming
         pc, pf = space_c.p, space_f.p
         Ic, _ = lagrange_eval(gauss_lobatto(pc + 1), gauss_lobatto(pf + 1))
         Io, _ = lagrange_eval(gauss_legendre(pc)[0], gauss_legendre(pf)[0])
@@ -724,10 +807,15 @@ class Interp:
         bc, k3 = _basis_desc(space_c, pf + 1)
         bf, k4 = _basis_desc(space_f, pf + 1)
         self.handle = C.c_void_p()
+        n_true_c = _default_true(space_c) if n_true_c is None else n_true_c
+        n_true_f = _default_true(space_f) if n_true_f is None else n_true_f
+        if conforming is not None:
+            _lib.check(_L().pa_interp_create_conforming(ctx.handle, C.byref(rc), C.byref(bc), C.byref(rf), C.byref(bf), _ptr(Ic),
+                                                        _ptr(Io), conforming.handle, n_true_c, n_true_f, C.byref(self.handle)))
+            return
         _lib.check(_L().pa_interp_create(ctx.handle, C.byref(rc), C.byref(bc), C.byref(rf), C.byref(bf), _ptr(Ic),
-                                         _ptr(Io), coarse_halo.handle if coarse_halo else None,
-                                         space_c.ndofs if n_true_c is None else n_true_c,
-                                         space_f.ndofs if n_true_f is None else n_true_f, C.byref(self.handle)))
+                                         _ptr(Io), coarse_halo.handle if coarse_halo else None, n_true_c, n_true_f,
+                                         C.byref(self.handle)))
 
     def mult(self, x, y):
         _lib.check(_L().pa_interp_mult(self.handle, C.c_void_p(x.data_ptr()), C.c_void_p(y.data_ptr())))
@@ -805,8 +893,10 @@ class RefinementTransfer(Interp):
 class Gradient(Interp):
     """Discrete gradient G : H1(p) -> ND(p) (the auxiliary-space transfer of the Hiptmair smoother)."""
 
-    def __init__(self, ctx, h1_space, nd_space, h1_halo=None, n_true_h1=None, n_true_nd=None):
-        self.ctx = ctx
+    def __init__(self, ctx, h1_space, nd_space, h1_halo=None, n_true_h1=None, n_true_nd=None, conforming=None):
+        """conforming: the Conforming prolongation of the H1 space (hanging nodes: R_nd G P_h1 on true-dof vectors)."""
+        _one_of(h1_halo, conforming)
+        self.ctx, self.conforming = ctx, conforming
         p = nd_space.p
         assert h1_space.p == p
         _, Dg = lagrange_eval(gauss_lobatto(p + 1), gauss_legendre(p)[0])  # [p][p+1]
@@ -816,10 +906,14 @@ class Gradient(Interp):
         bh, k3 = _basis_desc(h1_space, p + 1)
         bn, k4 = _basis_desc(nd_space, p + 1)
         self.handle = C.c_void_p()
+        n_true_h1 = _default_true(h1_space) if n_true_h1 is None else n_true_h1
+        n_true_nd = _default_true(nd_space) if n_true_nd is None else n_true_nd
+        if conforming is not None:
+            _lib.check(_L().pa_gradient_create_conforming(ctx.handle, C.byref(rh), C.byref(bh), C.byref(rn), C.byref(bn), _ptr(Dg),
+                                                          conforming.handle, n_true_h1, n_true_nd, C.byref(self.handle)))
+            return
         _lib.check(_L().pa_gradient_create(ctx.handle, C.byref(rh), C.byref(bh), C.byref(rn), C.byref(bn), _ptr(Dg),
-                                           h1_halo.handle if h1_halo else None,
-                                           h1_space.ndofs if n_true_h1 is None else n_true_h1,
-                                           nd_space.ndofs if n_true_nd is None else n_true_nd, C.byref(self.handle)))
+                                           h1_halo.handle if h1_halo else None, n_true_h1, n_true_nd, C.byref(self.handle)))
 
 
 class Curl(Interp):
@@ -936,19 +1030,25 @@ class ComplexGmres:
 class ComplexParOperator:
     """palace::ComplexParOperator (linalg/rap.cpp:393-749) over two local ceed operators (either may be None)."""
 
-    def __init__(self, ctx, local_r, local_i, ess_tdofs=(), diag_policy=DIAG_ONE, n_true=None, halo=None):
+    def __init__(self, ctx, local_r, local_i, ess_tdofs=(), diag_policy=DIAG_ONE, n_true=None, halo=None, conforming=None):
+        _one_of(halo, conforming)
         L = _L()
         L.pa_complex_par_op_destroy.restype = None
         L.pa_complex_par_op_destroy.argtypes = [C.c_void_p]
         L.pa_complex_par_op_mult.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double] + [C.c_void_p] * 4
         L.pa_complex_par_op_local_mult.argtypes = L.pa_complex_par_op_mult.argtypes
-        self.ctx, self._keep = ctx, (local_r, local_i, halo)
+        self.ctx, self._keep = ctx, (local_r, local_i, halo, conforming)
         any_op = local_r if local_r is not None else local_i
-        self.n = any_op.height if n_true is None else n_true
+        self.n = (conforming.n_true if conforming is not None else any_op.height) if n_true is None else n_true
         self.handle = C.c_void_p()
-        _lib.check(L.pa_complex_par_op_create(ctx.handle, local_r.handle if local_r else None,
-                                              local_i.handle if local_i else None, self.n,
-                                              halo.handle if halo else None, C.byref(self.handle)))
+        if conforming is not None:
+            _lib.check(L.pa_complex_par_op_create_conforming(ctx.handle, local_r.handle if local_r else None,
+                                                             local_i.handle if local_i else None, self.n,
+                                                             conforming.handle, C.byref(self.handle)))
+        else:
+            _lib.check(L.pa_complex_par_op_create(ctx.handle, local_r.handle if local_r else None,
+                                                  local_i.handle if local_i else None, self.n,
+                                                  halo.handle if halo else None, C.byref(self.handle)))
         ess = np.ascontiguousarray(ess_tdofs, dtype=np.int32)
         if ess.size:
             _lib.check(L.pa_complex_par_op_set_essential(self.handle, _ptr(ess), ess.size, diag_policy))
