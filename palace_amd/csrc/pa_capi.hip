@@ -510,11 +510,12 @@ static void apply(pa_op *op, const double *x, double *y, bool overwrite, hipStre
   PA_REQUIRE(op->msubs.empty() || !TransposeScope::active() || (op->subs.empty() && op->dsubs.empty()),
              "transposed apply of an operator with two-space sub-operators: those only");
   bool first = true;
+  const StreamForm form = stream_form(masked);
   for (const SubOp *so : op->subs) {
     if (so->fe_type == PA_FE_HCURL) {
-      if (so->d_idxc && overwrite && first && (!masked || so->d_perm_s_bc)) {  // streaming kernel (y = A x) + E^T of the shared dofs by runs
-        if (g_debug_phase != 2) launch_nd_hex_stream(*so, x, y, masked, s);
-        if (g_debug_phase != 1) launch_et_run_gather(*so, y, false, s, x, masked, ess_policy);
+      if (so->d_idxc && overwrite && first && (!masked || so->stream[kStreamMasked].ready())) {  // streaming kernel (y = A x) + E^T of the shared dofs by runs
+        if (g_debug_phase != 2) launch_nd_hex_stream(*so, x, y, form, s);
+        if (g_debug_phase != 1) launch_et_run_gather(*so, y, false, s, x, form, ess_policy);
       } else if (so->d_ye) {
         launch_nd_hex_apply(*so, x, y, so->d_ye, masked, s, !(overwrite && first), ess_policy);
         launch_et_gather(*so, y, !(overwrite && first), s, x, ess_policy);
@@ -528,9 +529,9 @@ static void apply(pa_op *op, const double *x, double *y, bool overwrite, hipStre
         launch_et_gather_raw(so->lsize, so->d_tptr, so->d_tent, so->d_ye, y, !(overwrite && first), s, so->d_shared_bc, x, ess_policy);
       else
         launch_et_gather(*so, y, !(overwrite && first), s);
-    } else if (so->d_idxc && so->stream_default && overwrite && first && (!masked || so->d_perm_s_bc)) {  // streaming form, see above
-      launch_h1_hex_stream(*so, x, y, masked, s);
-      launch_et_run_gather(*so, y, false, s, x, masked, ess_policy);
+    } else if (so->d_idxc && so->stream_default && overwrite && first && (!masked || so->stream[kStreamMasked].ready())) {  // streaming form, see above
+      launch_nd_hex_stream(*so, x, y, form, s);
+      launch_et_run_gather(*so, y, false, s, x, form, ess_policy);
     } else {
       launch_h1_hex_apply(*so, x, masked, s);
       launch_et_gather(*so, y, !(overwrite && first), s);
@@ -566,7 +567,6 @@ void finalize_exclusive(pa_op *op) {
     for (const int32_t s : so->h_sidx) cnt[s >= 0 ? s : -1 - s]++;
     for (int d = 0; d < so->lsize; d++)
       if (cnt[d] != 1) so->h_shared.push_back(d);
-    so->n_shared = (int)so->h_shared.size();
     build_stream(*so);
     return;
   }
@@ -1206,12 +1206,12 @@ int pa_op_mult_complex(pa_op *op_r, pa_op *op_i, const double *xr, const double 
       launch_dense_gather(*dr, yi, false, s, dr->d_ye2, nullptr, masked ? xi : nullptr, ess_policy);
     } else {
       SubOp *sr = op_r->subs[0];
-      PA_REQUIRE(!masked || (op_r->has_essential && sr->d_perm_s_bc), "pa_op_set_essential has not been called on the real operator");
+      PA_REQUIRE(!masked || (op_r->has_essential && sr->stream[kStreamMasked].ready()), "pa_op_set_essential has not been called on the real operator");
       if (!sr->d_ye2) sr->d_ye2 = dev_alloc<double>((size_t)((sr->ne + 3) & ~3) * sr->P);
       if (sr->qd->metric) stream_element_coefficients(*op_i->subs[0]);
       launch_nd_hex_stream_complex(*sr, *op_i->subs[0], xr, xi, yr, yi, sr->d_ye2, masked, s);
       // both parts in one launch: headers and copy positions read once (round 6)
-      launch_et_run_gather2(*sr, yr, yi, s, xr, xi, masked, ess_policy, sr->d_ye2);
+      launch_et_run_gather2(*sr, yr, yi, s, xr, xi, stream_form(masked), ess_policy, sr->d_ye2);
     }
     // the remaining sub-operators (operator.cpp:98-134 term by term): B of the real part, yr += B xr, yi += B xi; B of the
     // imaginary part, yi += B xr, yr -= B xi; essential entries of x read as zero through B's own flagged index copy, essential
@@ -1320,7 +1320,7 @@ int pa_op_mult_essential_diag(pa_op *op, const double *x, double *y, int diag_po
     const bool fuse = s0 && op->dsubs.empty() && op->msubs.empty() &&
                       (s0->fe_type == PA_FE_HCURL  ? nd_hex_fuses_essential(*s0)
                        : s0->fe_type == PA_FE_HDIV ? s0->d_shared_bc != nullptr  // (the plain gather over the flagged dof list)
-                                                   : (s0->d_idxc && s0->stream_default && s0->d_perm_s_bc));
+                                                   : (s0->d_idxc && s0->stream_default && s0->stream[kStreamMasked].ready()));
     apply(op, x, y, true, (hipStream_t)stream, true, fuse ? (diag_policy ? 1 : 0) : -1);
     *handled = fuse ? 1 : 0;
   });
@@ -1386,8 +1386,9 @@ int pa_op_prepare_fused_step(pa_op *op, int *available) {
     // tables: pa_nd_hex_stream3.hip -- nd_hex_stream_ok covers them all; H1 blocks whose y = A x runs on the streaming kernel:
     // pa_h1_hex_stream.hip)
     if (so->fe_type == PA_FE_H1) {
-      if (!so->d_idxc || !so->stream_default || !so->d_perm_s_bc || !h1_hex_stream_ok(*so)) return;
-    } else if (so->fe_type != PA_FE_HCURL || (so->q1d != 3 && so->q1d != 4 && so->q1d != 5) || !so->d_idxc || !so->d_perm_s_bc || !nd_hex_stream_ok(*so)) {
+      if (!so->d_idxc || !so->stream_default || !so->stream[kStreamMasked].ready() || !h1_hex_stream_ok(*so)) return;
+    } else if (so->fe_type != PA_FE_HCURL || (so->q1d != 3 && so->q1d != 4 && so->q1d != 5) || !so->d_idxc || !so->stream[kStreamMasked].ready() ||
+               !nd_hex_stream_ok(*so)) {
       return;
     }
     *available = stream_build_all(*so) ? 1 : 0;
@@ -1429,10 +1430,10 @@ int pa_op_mult_cheb_step(pa_op *op, const double *x, const pa_cheb_step *step, i
                                diag_policy ? 1 : 0, (hipStream_t)stream);
       return;
     }
-    PA_REQUIRE(op->subs.size() == 1 && op->subs[0]->n_all > 0, "pa_op_prepare_fused_step has not been called (or found no fused form)");
+    PA_REQUIRE(op->subs.size() == 1 && op->subs[0]->stream[kStreamAll].ready(), "pa_op_prepare_fused_step has not been called (or found no fused form)");
     const SubOp &so = *op->subs[0];
     launch_nd_hex_stream_all(so, x, (hipStream_t)stream);
-    launch_et_run_gather_step(so, x, GatherStep{step->sd, step->sr, step->dinv, step->r0, step->e_prev, step->out, step->add, nullptr, 1},
+    launch_et_run_gather_step(so, kStreamAll, x, GatherStep{step->sd, step->sr, step->dinv, step->r0, step->e_prev, step->out, step->add, nullptr, 1},
                               diag_policy ? 1 : 0, (hipStream_t)stream);
   });
 }
@@ -1451,10 +1452,10 @@ int pa_op_mult_residual(pa_op *op, const double *y, const double *b, double *res
                                (hipStream_t)stream);
       return;
     }
-    PA_REQUIRE(op->subs.size() == 1 && op->subs[0]->n_all > 0, "pa_op_prepare_fused_step has not been called (or found no fused form)");
+    PA_REQUIRE(op->subs.size() == 1 && op->subs[0]->stream[kStreamAll].ready(), "pa_op_prepare_fused_step has not been called (or found no fused form)");
     const SubOp &so = *op->subs[0];
     launch_nd_hex_stream_all(so, y, (hipStream_t)stream);
-    launch_et_run_gather_step(so, y, GatherStep{0.0, c0, dinv, b, nullptr, d0, 0, res, 2}, diag_policy ? 1 : 0, (hipStream_t)stream);
+    launch_et_run_gather_step(so, kStreamAll, y, GatherStep{0.0, c0, dinv, b, nullptr, d0, 0, res, 2}, diag_policy ? 1 : 0, (hipStream_t)stream);
   });
 }
 
@@ -1488,12 +1489,9 @@ int pa_op_mult_split(pa_op *op, const double *x, const double *xg0, const double
       return;
     }
     SubOp *so = op->subs[0];
-    PA_REQUIRE(!masked || (op->has_essential && so->d_perm_s_bc), "pa_op_set_essential has not been called");
-    if (so->fe_type == PA_FE_H1)
-      launch_h1_hex_stream(*so, x, y, masked, s, &io);
-    else
-      launch_nd_hex_stream(*so, x, y, masked, s, &io);
-    launch_et_run_gather(*so, y, false, s, x, masked, ess_policy, nullptr, &io);
+    PA_REQUIRE(!masked || (op->has_essential && so->stream[kStreamMasked].ready()), "pa_op_set_essential has not been called");
+    launch_nd_hex_stream(*so, x, y, stream_form(masked), s, &io);
+    launch_et_run_gather(*so, y, false, s, x, stream_form(masked), ess_policy, nullptr, &io);
   });
 }
 
@@ -1514,11 +1512,11 @@ int pa_op_mult_split_step(pa_op *op, const double *x, const double *xg0, const d
                                                  st->iface_mask, st->t_iface}, ess_policy, s, &io);
       return;
     }
-    PA_REQUIRE(op->subs.size() == 1 && op->dsubs.empty() && op->subs[0]->n_all > 0,
+    PA_REQUIRE(op->subs.size() == 1 && op->dsubs.empty() && op->subs[0]->stream[kStreamAll].ready(),
                "pa_op_prepare_fused_step has not been called (or found no fused form)");
     const SubOp &so = *op->subs[0];
     launch_nd_hex_stream_all(so, x, s, &io);
-    launch_et_run_gather_step(so, x, GatherStep{st->sd, st->sr, st->dinv, st->r0, st->e_prev, st->out, st->add, st->res, st->mode,
+    launch_et_run_gather_step(so, kStreamAll, x, GatherStep{st->sd, st->sr, st->dinv, st->r0, st->e_prev, st->out, st->add, st->res, st->mode,
                                                 st->iface_mask, st->t_iface}, ess_policy, s, &io);
   });
 }

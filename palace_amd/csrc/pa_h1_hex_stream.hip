@@ -8,6 +8,7 @@
 #include <string>
 
 #include "pa_hex_core.hpp"
+#include "pa_stream_launch.hpp"
 
 namespace pa {
 
@@ -325,16 +326,6 @@ __global__ __launch_bounds__(64 * kH1StreamWaves, MINW) void h1_hex_stream_kerne
   }
 }
 
-int device_cus_h1() {
-  static int cus = [] {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
-      n = 256;
-    return n;
-  }();
-  return cus;
-}
-
 template <int P1, bool V, bool G, bool SPLIT = false>
 void launch_vg(const SubOp &so, H1StreamArgs<P1> &a, hipStream_t s) {
   using L = H1Layout<P1, 4>;
@@ -342,16 +333,11 @@ void launch_vg(const SubOp &so, H1StreamArgs<P1> &a, hipStream_t s) {
   constexpr int NC = P1 + 1, PP = NC * NC * NC, NPL = (PP + 15) / 16, NPK = (NPL + 3) / 4;
   for (int i = 0; i < 2 * NC; i++) a.tab.Bc[i] = so.Bc[i], a.tab.Gc[i] = so.Gc[i];
   const size_t lds = sizeof(double) * (size_t)(kH1StreamWaves * 4) * ((L::ELEM_PAD + (PP + 1) / 2 + (NPK + 1) * 8 + 14 + 15) / 32 * 32 + 16);
-  static const int per_cu = [&] {
-    int nb = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, h1_hex_stream_kernel<P1, V, G, MINW, SPLIT>, 64 * kH1StreamWaves, lds) != hipSuccess ||
-        nb <= 0)
-      nb = 2;
-    return std::max(1, std::min(std::min(nb, MINW * 2), 8));
-  }();
+  static const int per_cu =
+      std::max(1, std::min({stream_occupancy(h1_hex_stream_kernel<P1, V, G, MINW, SPLIT>, 64 * kH1StreamWaves, lds, 2), MINW * 2, 8}));
   a.nbatch = (so.ne + 3) / 4;
   a.chunk = (a.nbatch + 7) / 8;
-  const int cus = device_cus_h1();
+  const int cus = stream_device_cus();
   // (workgroups are dealt to the XCDs round-robin: the grid is a multiple of 8)
   int grid = std::max(8, std::min(per_cu * cus, ((a.nbatch + kH1StreamWaves - 1) / kH1StreamWaves + 7) / 8 * 8));
   grid = (grid + 7) / 8 * 8;
@@ -360,19 +346,15 @@ void launch_vg(const SubOp &so, H1StreamArgs<P1> &a, hipStream_t s) {
 }
 
 template <int P1>
-void launch_p(const SubOp &so, const double *x, double *y, bool masked, hipStream_t s, const SplitIO *split, bool all) {
+void launch_p(const SubOp &so, const double *x, double *y, StreamForm form, hipStream_t s, const SplitIO *split) {
   H1StreamArgs<P1> a;
   a.ne = so.ne;
   a.idxc = so.d_idxc;
-  a.perm = all ? so.d_perm_s_all : (masked ? so.d_perm_s_bc : so.d_perm_s);  // (all: no entry exclusive -- the fused smoother step)
+  a.perm = so.stream[form].d_flags;
   a.qdata = so.qd->d;
   a.x = x, a.y = y, a.ye = so.d_ye;
-  a.nsplit = -1, a.xg0 = a.xg1 = nullptr, a.xg_sel = nullptr, a.yg = nullptr;
+  stream_set_split(a, split, so.lsize);
   if (split) {
-    PA_REQUIRE(split->n_true >= 0 && split->n_true <= so.lsize, "split point outside the local vector");
-    a.nsplit = split->n_true;
-    a.xg0 = split->xg0 - split->n_true, a.xg1 = (split->xg1 ? split->xg1 : split->xg0) - split->n_true;
-    a.xg_sel = split->sel, a.yg = split->yg - split->n_true;
     switch (so.qf) {
       case PA_QF_HCURL_33: launch_vg<P1, false, true, true>(so, a, s); break;
       case PA_QF_H1_1: launch_vg<P1, true, false, true>(so, a, s); break;
@@ -418,11 +400,11 @@ bool h1_hex_stream_ok(const SubOp &so) {
   return so.fe_type == PA_FE_H1 && so.q1d == 4 && so.p >= (all ? 1 : 3) && so.p <= 3 && so.qd && so.qd->d && so.d_ye && so.d_tptr;
 }
 
-void launch_h1_hex_stream(const SubOp &so, const double *x, double *y, bool masked, hipStream_t s, const SplitIO *split, bool all) {
+void launch_h1_hex_stream(const SubOp &so, const double *x, double *y, StreamForm form, hipStream_t s, const SplitIO *split) {
   switch (so.p) {
-    case 1: launch_p<1>(so, x, y, masked, s, split, all); break;
-    case 2: launch_p<2>(so, x, y, masked, s, split, all); break;
-    case 3: launch_p<3>(so, x, y, masked, s, split, all); break;
+    case 1: launch_p<1>(so, x, y, form, s, split); break;
+    case 2: launch_p<2>(so, x, y, form, s, split); break;
+    case 3: launch_p<3>(so, x, y, form, s, split); break;
     default: throw Error("no streaming H1 kernel for this order");
   }
 }

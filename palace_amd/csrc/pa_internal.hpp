@@ -189,6 +189,32 @@ __host__ __device__ inline int nd_qd_offset(int q1d, int c, int q) {
   return c * q1d * q1d * q1d + q;
 }
 
+// The three forms of a block's streaming tables.  They differ in which entries an element kernel stores straight to y and which
+// rows the run gather owns:
+//   plain   entries that are the only copy of their dof go straight to y, the gather sums the other dofs
+//   masked  the same with the essential dofs read as zero and taken off the direct path: the gather owns their rows too and
+//           writes x or 0 there when ParOperator's fix-up is fused (pa_op_set_essential)
+//   all     no entry goes straight to y: EVERY dof goes through the E-vector and is owned by the gather, whose epilogue can then
+//           consume the sum instead of storing it (the fused smoother step, launch_et_run_gather_step); essential dofs as in masked
+enum StreamForm { kStreamPlain = 0, kStreamMasked = 1, kStreamAll = 2 };
+inline StreamForm stream_form(bool masked) { return masked ? kStreamMasked : kStreamPlain; }
+
+// What one form owns on the device
+struct StreamTables {
+  // the words that carry the form's flags, as the block's element kernel reads them: three- and four-point H(curl) the flag
+  // words on their own, [ne][16]; five-point H(curl) [ne][ceil(P/64)][32] and H1 [ne][ceil(P/64) + 1][16] the slot words with them
+  uint32_t *d_flags = nullptr;
+  uint32_t *d_rchunk = nullptr;  // [ceil(n_rows / 64)] RunChunk: run-start mask of 64 gathered dofs + run / offset of the first
+  int32_t *d_rhdr = nullptr;     // [n_runs + 1] run headers {first dof | length - 1 | essential, first copy entry}
+  int32_t *d_rpos = nullptr;     // copy positions in d_ye
+  int n_rows = 0, n_runs = 0;    // dofs the run gather owns, runs they fall into
+  bool ready() const { return d_rhdr != nullptr; }  // the form has been built
+  void release() {
+    (void)hipFree(d_flags), (void)hipFree(d_rchunk), (void)hipFree(d_rhdr), (void)hipFree(d_rpos);
+    *this = StreamTables{};
+  }
+};
+
 struct SubOp {
   Geom *geom = nullptr;
   QData *qd = nullptr;  // nullptr: matrix-free D from the geometry data (the reference default)
@@ -215,31 +241,19 @@ struct SubOp {
   double *d_ye2 = nullptr;     // second E-vector (two right-hand sides), allocated on first use
   int32_t *d_tptr = nullptr;   // [lsize + 1]
   int32_t *d_tent = nullptr;   // [ne * P] signed positions into d_ye
-  // streaming form (pa_nd_hex_stream.hip): index words with the exclusive flag, byte slots, E^T of the shared dofs by runs
+  // streaming form (pa_nd_hex_stream.hip): run-compressed index words, byte slots, E^T by runs.  Shared by every form:
   uint32_t *d_idxc = nullptr;  // [ne][kIdxWords] run-compressed sorted element -> dof index (pa_stream_host.hpp)
   bool stream_default = true;  // false: the tables exist for the split-vector apply only, y = A x keeps the one-shot kernel (H1, p < 3)
-  uint32_t *d_perm_s_bc = nullptr;                      // flag words with the essential dofs taken off the direct path
-  std::vector<uint32_t> h_perm_s;
-  int32_t *d_rhdr_bc = nullptr, *d_rpos_bc = nullptr;   // run list that also owns the essential rows
-  int n_shared_bc = 0;
-  uint32_t *d_perm_s = nullptr;                         // [ne][ceil(P/64)][16], four 8-bit tensor-order slots per word
-  // four-point H(curl) kernel: the flag words on their own ([ne][16]; _bc: the copy with the essential dofs) and the slot words
-  // through a dictionary -- elements whose sorted -> tensor-order permutation agrees share one entry (a structured mesh has a
-  // handful: 10 on the 125 440-element bench cylinder), the element's entry number rides in a spare word of its index block
-  uint32_t *d_flagw = nullptr, *d_flagw_bc = nullptr, *d_slots = nullptr;
+  std::vector<uint32_t> h_perm_s;  // slot + flag words as pack_index / pack_index_wide lay them out (host; the forms are edited copies)
+  // three- and four-point H(curl) kernels: the slot words through a dictionary -- elements whose sorted -> tensor-order permutation
+  // agrees share one entry (a structured mesh has a handful: 10 on the 125 440-element bench cylinder), the element's entry
+  // number rides in a spare word of its index block
+  uint32_t *d_slots = nullptr;
   int n_slot_patterns = 0;
-  double *d_coef_s = nullptr;                           // metric form: [ne][2] scalar mass / curl-curl coefficient per element
-  int32_t *d_rhdr = nullptr, *d_rpos = nullptr;         // run headers {first dof | length - 1 | essential, first copy entry}; copy positions in d_ye
-  int n_runs = 0, n_runs_bc = 0;
-  uint32_t *d_rchunk = nullptr, *d_rchunk_bc = nullptr;  // [ceil(n_shared / 64)] RunChunk: run-start mask of 64 shared dofs + run / offset of the first
-  // third form (round 6, stream_build_all): EVERY dof goes through the E-vector and is owned by the run gather -- no entry is
-  // exclusive in this copy of the flag words -- so that the gather's epilogue can consume the result instead of storing it (the
-  // fused Chebyshev step, launch_et_run_gather_step); essential dofs flagged as in the _bc copy
-  uint32_t *d_flagw_all = nullptr, *d_rchunk_all = nullptr;
-  uint32_t *d_perm_s_all = nullptr;  // the same for the five-point kernel, whose flags ride in the slot half-words
-  int32_t *d_rhdr_all = nullptr, *d_rpos_all = nullptr;
-  int n_all = 0, n_runs_all = 0;
+  double *d_coef_s = nullptr;    // metric form: [ne][2] scalar mass / curl-curl coefficient per element
   std::vector<char> h_ess_flag;  // the essential flags last fused (stream_set_essential), for stream_build_all
+  // ... and per form (StreamForm): plain from build_stream, masked from stream_set_essential, all from stream_build_all
+  StreamTables stream[3];
   std::vector<double> Bc, Gc, Bo;  // full 1-D tables [q1d][n] (host)
   double *d_tab = nullptr;        // the same on the device: [Bo | Bc | Gc]
   bool iso = false;               // every material coefficient is a multiple of the identity
@@ -337,8 +351,7 @@ void launch_h1_hex_q6(const SubOp &so, const double *x, bool masked, hipStream_t
 struct SplitIO;
 bool h1_hex_stream_ok(const SubOp &so);       // the streaming form is the default for y = A x
 bool h1_hex_stream_capable(const SubOp &so);  // ... its tables can be built (split-vector applies use it at every order)
-void launch_h1_hex_stream(const SubOp &so, const double *x, double *y, bool masked, hipStream_t s, const SplitIO *split = nullptr,
-                          bool all = false);
+void launch_h1_hex_stream(const SubOp &so, const double *x, double *y, StreamForm form, hipStream_t s, const SplitIO *split = nullptr);
 bool nd_hex_stream_ok(const SubOp &so);
 void build_stream(SubOp &so);
 void stream_set_essential(SubOp &so, const std::vector<char> &flag);
@@ -353,7 +366,9 @@ struct SplitIO {
   double *yg;
 };
 bool nd_hex_stream_split_ok(const SubOp &so);
-void launch_nd_hex_stream(const SubOp &so, const double *x, double *y, bool masked, hipStream_t s, const SplitIO *split = nullptr);
+// the element kernel of any streaming block on the tables of `form` (H(curl) at three, four or five points; H1 blocks are passed
+// on to launch_h1_hex_stream)
+void launch_nd_hex_stream(const SubOp &so, const double *x, double *y, StreamForm form, hipStream_t s, const SplitIO *split = nullptr);
 // One step of a smoother recurrence consumed inside E^T (round 6): with t = (A x)[d] (the essential rows fixed as in the masked
 // apply) the run gather writes  out[d] (+)= x[d] + sd (x[d] - ep[d]) + sr dinv[d] (r0[d] - t)  for every dof and never stores t:
 // the Chebyshev step of chebyshev.cpp:204-218 in its accumulated form (linalg.hip: OpChebStep3) without the round trip of A x.
@@ -375,22 +390,20 @@ struct GatherStep {
   // are added to the sum of every row that is not an essential one (nullptr: none).  Dense path only.
   const double *t_add;
 };
-void launch_et_run_gather2(const SubOp &so, double *y, double *y1, hipStream_t s, const double *x, const double *x1, bool masked,
+void launch_et_run_gather2(const SubOp &so, double *y, double *y1, hipStream_t s, const double *x, const double *x1, StreamForm form,
                            int ess_policy, const double *ye1);
 bool stream_build_all(SubOp &so);  // the index copies the fused step needs (idempotent; false: this block has no such form)
 void launch_nd_hex_stream_all(const SubOp &so, const double *x, hipStream_t s, const SplitIO *split = nullptr);
-void launch_et_run_gather_step(const SubOp &so, const double *x, const GatherStep &step, int ess_policy, hipStream_t s,
+void launch_et_run_gather_step(const SubOp &so, StreamForm form, const double *x, const GatherStep &step, int ess_policy, hipStream_t s,
                                const SplitIO *split = nullptr);
 bool nd_hex_stream5_ok(const SubOp &so);
 // pa_nd_hex_stream3.hip: three points per direction (orders 1 and 2), opt-in with PALACE_AMD_STREAM3=1 at operator creation
 bool nd_hex_stream3_ok(const SubOp &so);
-void launch_nd_hex_stream3(const SubOp &so, const double *x, double *y, bool masked, hipStream_t s, const SplitIO *split = nullptr,
-                           bool all = false);
-void launch_nd_hex_stream5(const SubOp &so, const double *x, double *y, bool masked, hipStream_t s, const SplitIO *split = nullptr,
-                           bool all = false);
+void launch_nd_hex_stream3(const SubOp &so, const double *x, double *y, StreamForm form, hipStream_t s, const SplitIO *split = nullptr);
+void launch_nd_hex_stream5(const SubOp &so, const double *x, double *y, StreamForm form, hipStream_t s, const SplitIO *split = nullptr);
 void launch_nd_hex_stream5_complex(const SubOp &sr, const SubOp &si, const double *xr, const double *xi, double *yr, double *yi,
                                    double *ye_i, bool masked, hipStream_t s);
-void launch_et_run_gather(const SubOp &so, double *y, bool accumulate, hipStream_t s, const double *x, bool masked,
+void launch_et_run_gather(const SubOp &so, double *y, bool accumulate, hipStream_t s, const double *x, StreamForm form,
                           int ess_policy, const double *ye = nullptr, const SplitIO *split = nullptr);
 void stream_element_coefficients(SubOp &so);
 bool nd_hex_stream_complex_ok(const SubOp &sr, const SubOp &si);

@@ -531,7 +531,7 @@ void launch_et_gather_raw(int n, const int32_t *tptr, const int32_t *tent, const
 
 bool nd_hex_fuses_essential(const SubOp &so) {
   // (five points per direction: only the streaming kernel's run gather owns the essential rows, pa_nd_hex_stream5.hip)
-  return (use_direct(so) && so.d_shared_bc != nullptr) || (so.q1d == 5 && so.d_idxc && so.d_perm_s_bc);
+  return (use_direct(so) && so.d_shared_bc != nullptr) || (so.q1d == 5 && so.d_idxc && so.stream[kStreamMasked].ready());
 }
 
 void launch_et_gather(const SubOp &so, double *y, bool accumulate, hipStream_t s, const double *x, int ess_policy) {

@@ -22,6 +22,7 @@
 #include <map>
 
 #include "pa_nd_hex_core.hpp"
+#include "pa_stream_launch.hpp"
 
 #ifndef PA_CPLX_QAHEAD
 #define PA_CPLX_QAHEAD 0  // (with PA_STREAM_QAHEAD: also the packed complex form)
@@ -777,7 +778,7 @@ bool nd_hex_stream_ok(const SubOp &so) {
   if (so.q1d == 5) return nd_hex_stream5_ok(so);  // five points per direction: pa_nd_hex_stream5.hip
   if (so.q1d == 3) return nd_hex_stream3_ok(so);  // three (opt-in, PALACE_AMD_STREAM3=1): pa_nd_hex_stream3.hip
   if (so.fe_type != PA_FE_HCURL || so.q1d != 4 || so.p > 3 || !so.qd || !so.d_ye || !so.d_perm_x) return false;
-  return so.qd->metric || so.qd->ncomp == 6 || (so.qd->ncomp == 12 && so.qf == PA_QF_HDIVMASS_33);
+  return stream_qdata_ok(so);
 }
 
 static bool wide_form(const SubOp &so) { return so.fe_type == PA_FE_HCURL && so.q1d == 5; }
@@ -931,12 +932,42 @@ static void stream_affine_setup(SubOp &so) {
   qd.d_aff = d_aff;
 }
 
+// the layout the slot + flag words of this block are packed and edited in (so.h_perm_s)
+static streamhost::FlagLayout flag_layout(const SubOp &so) {
+  return streamhost::FlagLayout{wide_form(so) ? streamhost::FlagLayout::kFlagWide : streamhost::FlagLayout::kFlagRow, so.P};
+}
+
+// the flag-carrying words of a form as the block's element kernel reads them (StreamTables::d_flags)
+static uint32_t *upload_flags(const SubOp &so, const std::vector<uint32_t> &pp) {
+  if (so.fe_type != PA_FE_HCURL || wide_form(so)) return dev_upload(pp.data(), pp.size());
+  const std::vector<uint32_t> fw = streamhost::split_flag_rows(flag_layout(so), pp);  // (the slot words: so.d_slots)
+  return dev_upload(fw.data(), fw.size());
+}
+
+// the run form of E^T over `rows` (increasing), essential rows flagged in their headers
+static void upload_runs(StreamTables &t, const SubOp &so, const std::vector<int32_t> &rows, const char *ess, const char *skip) {
+  std::vector<uint32_t> code;
+  std::vector<RunHdr> hdr;
+  std::vector<int32_t> rpos;
+  streamhost::build_runs(so.ne, so.P, so.lsize, so.h_sidx.data(), rows, code, hdr, rpos, ess, skip);  // (runs: all essential or none)
+  const std::vector<RunChunk> ch = streamhost::run_chunks(code);
+  t.d_rchunk = dev_upload(reinterpret_cast<const uint32_t *>(ch.data()), 4 * ch.size());
+  t.d_rhdr = dev_upload(reinterpret_cast<const int32_t *>(hdr.data()), 2 * hdr.size());
+  t.d_rpos = dev_upload(rpos.data(), rpos.size());
+  t.n_rows = (int)rows.size(), t.n_runs = (int)hdr.size() - 1;
+}
+
+// (pricing experiment: copies taken off the E-vector are not copies)
+static const char *price_skip(const SubOp &so) { return so.h_price_skip.empty() ? nullptr : so.h_price_skip.data(); }
+
 // Index arrays of the streaming kernel and the run form of the transpose map (after finalize_exclusive: needs the
 // exclusive flags).  Host work proportional to the index array, once per operator.  Every per-element array is padded
 // to a multiple of four elements (one batch); the pad entries are flagged essential (read as zero).
 void build_stream(SubOp &so) {
   if (so.d_idxc || !(nd_hex_stream_ok(so) || h1_hex_stream_capable(so))) return;
   const int P = so.P, ne = so.ne;
+  const bool lane16_curl = so.fe_type == PA_FE_HCURL && !wide_form(so);  // three and four points per direction
+  const streamhost::FlagLayout fl = flag_layout(so);
   std::vector<uint32_t> ic, pp;
   // (a numbering that breaks an element's dofs into more than kIdxMaxRuns runs keeps the one-shot kernel)
   if (wide_form(so)) {
@@ -950,13 +981,12 @@ void build_stream(SubOp &so) {
   // straight to y instead, like an exclusive dof's) and out of the run lists; a dof whose copies all sit in one group leaves
   // the gather altogether.  What is NOT priced: the LDS traffic and barrier of the on-chip assembly itself.
 #ifdef PA_ABLATION  // (the ablation library only, `make ablate`: the product library has no such switch)
-  const int price_group = (so.fe_type == PA_FE_HCURL && !wide_form(so) && getenv("PALACE_AMD_PRICE_BLOCK")) ? atoi(getenv("PALACE_AMD_PRICE_BLOCK")) : 0;
+  const int price_group = (lane16_curl && getenv("PALACE_AMD_PRICE_BLOCK")) ? atoi(getenv("PALACE_AMD_PRICE_BLOCK")) : 0;
 #else
   constexpr int price_group = 0;
 #endif
   if (price_group > 1) {
     const size_t nnz = (size_t)ne * P;
-    const int npl = (P + 15) / 16, npk = (npl + 3) / 4;
     so.h_price_skip.assign(nnz, 0);
     std::vector<int32_t> seen((size_t)so.lsize, -1), cnt((size_t)so.lsize, 0), cnt2((size_t)so.lsize, 0);
     for (size_t k = 0; k < nnz; k++) {
@@ -969,9 +999,8 @@ void build_stream(SubOp &so) {
       const int d = streamhost::dof_of(so.h_sidx[k]);
       const bool direct = so.h_price_skip[k] || (cnt2[d] == 1 && cnt[d] > 1);
       if (!direct) continue;
-      const size_t e = k / P;
-      const int m = (int)(k - e * P), t = m & 15, r = m >> 4;
-      pp[(e * (npk + 1) + npk) * 16 + t] |= 2u << (2 * r);
+      const int m = (int)(k % P);
+      pp[fl.word(k / P, m)] |= fl.only_copy(m);
       dropped += so.h_price_skip[k] ? 1 : 0, freed += so.h_price_skip[k] ? 0 : 1;
     }
     std::vector<int32_t> shared2;
@@ -982,30 +1011,23 @@ void build_stream(SubOp &so) {
     so.h_shared = shared2;
     so.n_shared = (int)shared2.size();
   }
-  if (so.fe_type == PA_FE_HCURL && !wide_form(so)) {
+  if (lane16_curl) {
     // batches of four affine elements: kAffBit in the flag words of their 4 x 16 (element, lane) pairs -- the flag arrives with the
     // index words, one batch ahead of the q-data request it steers
     stream_affine_setup(so);
-    const int npl = (P + 15) / 16, npk = (npl + 3) / 4;
     for (size_t b = 0; b < so.qd->batch_aff.size(); b++)
       if (so.qd->batch_aff[b])
-        for (size_t e = 4 * b; e < 4 * b + 4; e++)
-          for (int t = 0; t < 16; t++) pp[(e * (npk + 1) + npk) * 16 + t] |= streamhost::kAffBit;
+        for (size_t e = 4 * b; e < 4 * b + 4; e++) streamhost::set_element_bit(fl, pp, e, streamhost::kAffBit);
     for (size_t b = 0; b < so.qd->batch_col.size(); b++)  // (column-separable and not all-affine: QData::d_col)
       if (so.qd->batch_col[b])
-        for (size_t e = 4 * b; e < 4 * b + 4; e++)
-          for (int t = 0; t < 16; t++) pp[(e * (npk + 1) + npk) * 16 + t] |= streamhost::kColBit;
-  }
-  so.h_perm_s = pp;
-  if (so.fe_type == PA_FE_HCURL && !wide_form(so)) {
-    // four-point H(curl) kernel: flag words on their own, slot words through the pattern dictionary (pa_internal.hpp)
-    const int npl = (P + 15) / 16, npk = (npl + 3) / 4, nep = (ne + 3) & ~3, sw = npk * 16;
-    std::vector<uint32_t> flagw((size_t)nep * 16), slots;
+        for (size_t e = 4 * b; e < 4 * b + 4; e++) streamhost::set_element_bit(fl, pp, e, streamhost::kColBit);
+    // slot words through the pattern dictionary (pa_internal.hpp)
+    const int nep = fl.padded(ne), sw = fl.elem_words() - 16;
+    std::vector<uint32_t> slots;
     std::map<std::vector<uint32_t>, uint32_t> dict;
     std::vector<uint32_t> key((size_t)sw);
     for (int e = 0; e < nep; e++) {
-      const uint32_t *row = &pp[(size_t)e * (npk + 1) * 16];
-      std::copy(row + sw, row + sw + 16, flagw.begin() + (size_t)e * 16);
+      const uint32_t *row = &pp[(size_t)e * fl.elem_words()];
       key.assign(row, row + sw);
       auto it = dict.find(key);
       if (it == dict.end()) {
@@ -1015,111 +1037,36 @@ void build_stream(SubOp &so) {
       ic[(size_t)e * streamhost::kIdxWords + streamhost::kIdxPattern] = it->second;
     }
     so.n_slot_patterns = (int)dict.size();
-    so.d_flagw = dev_upload(flagw.data(), flagw.size());
     so.d_slots = dev_upload(slots.data(), slots.size());
   }
+  so.h_perm_s = pp;
   so.d_idxc = dev_upload(ic.data(), ic.size());
-  so.d_perm_s = dev_upload(pp.data(), pp.size());
   if (so.qd->metric || (so.iso && so.qf == PA_QF_HDIV_33 && so.geom->d_xnodes)) stream_element_coefficients(so);
-
-  std::vector<uint32_t> code;
-  std::vector<RunHdr> hdr;
-  std::vector<int32_t> rpos;
-  streamhost::build_runs(ne, P, so.lsize, so.h_sidx.data(), so.h_shared, code, hdr, rpos, nullptr,
-                         so.h_price_skip.empty() ? nullptr : so.h_price_skip.data());
-  {
-    const std::vector<RunChunk> ch = streamhost::run_chunks(code);
-    so.d_rchunk = dev_upload(reinterpret_cast<const uint32_t *>(ch.data()), 4 * ch.size());
-  }
-  so.d_rhdr = dev_upload(reinterpret_cast<const int32_t *>(hdr.data()), 2 * hdr.size());
-  so.d_rpos = dev_upload(rpos.data(), rpos.size());
-  so.n_runs = (int)hdr.size() - 1;
+  StreamTables &t = so.stream[kStreamPlain];
+  t.d_flags = upload_flags(so, pp);
+  upload_runs(t, so, so.h_shared, nullptr, price_skip(so));
 }
 
-// Essential dofs (pa_op_set_essential): flagged (read as zero) and never exclusive in a copy of
-// the flag words (their element-local result goes to the E-vector like a shared dof's), and present in a second run list,
+// Essential dofs (pa_op_set_essential): flagged (read as zero) and never exclusive in the masked form's copy of
+// the flag words (their element-local result goes to the E-vector like a shared dof's), and present in its run list,
 // so that the run gather owns every essential row: it writes x or 0 there when ParOperator's fix-up is fused
 // (rap.cpp:223-233) and the plain sum otherwise.
 void stream_set_essential(SubOp &so, const std::vector<char> &flag) {
   if (!so.d_idxc) return;
   so.h_ess_flag = flag;
-  if (so.n_all > 0) {  // (built for another list: again on the next pa_op_prepare_fused_step)
-    hipFree(so.d_flagw_all), hipFree(so.d_perm_s_all), hipFree(so.d_rchunk_all), hipFree(so.d_rhdr_all), hipFree(so.d_rpos_all);
-    so.d_flagw_all = so.d_perm_s_all = nullptr, so.d_rchunk_all = nullptr, so.d_rhdr_all = so.d_rpos_all = nullptr, so.n_all = 0;
-  }
-  const int P = so.P, npl = (P + 15) / 16, npk = (npl + 3) / 4;
+  so.stream[kStreamAll].release();  // (built for another list: again on the next pa_op_prepare_fused_step)
   std::vector<uint32_t> pb(so.h_perm_s);
-  const size_t nnz = (size_t)so.ne * so.P;
-  const bool wide = wide_form(so);
-  const int npkw = ((P + 31) / 32 + 1) / 2;
-  for (size_t k = 0; k < nnz; k++) {
-    if (flag[streamhost::dof_of(so.h_sidx[k])]) {
-      const size_t e = k / P;
-      if (wide) {  // flags ride in the slot half-words (pack_index_wide)
-        const int m = (int)(k - e * P), t = m & 31, r = m >> 5;
-        uint32_t &w = pb[(e * npkw + (r >> 1)) * 32 + t];
-        w &= ~(streamhost::kWideExcl << (16 * (r & 1)));
-        w |= streamhost::kWideEss << (16 * (r & 1));
-        continue;
-      }
-      const int m = (int)(k - e * P), t = m & 15, r = m >> 4;
-      uint32_t &fw = pb[(e * (npk + 1) + npk) * 16 + t];
-      fw &= ~(2u << (2 * r));  // off the direct path
-      fw |= 1u << (18 + r);    // read as zero
-    }
-  }
-  hipFree(so.d_perm_s_bc);
-  so.d_perm_s_bc = dev_upload(pb.data(), pb.size());
-  if (so.d_flagw) {  // (the flag words of the masked copy; the slot words are the same)
-    const int nep = (so.ne + 3) & ~3;
-    std::vector<uint32_t> fb((size_t)nep * 16);
-    for (int e = 0; e < nep; e++) std::copy(&pb[((size_t)e * (npk + 1) + npk) * 16], &pb[((size_t)e * (npk + 1) + npk) * 16] + 16, fb.begin() + (size_t)e * 16);
-    hipFree(so.d_flagw_bc);
-    so.d_flagw_bc = dev_upload(fb.data(), fb.size());
-  }
-  std::vector<int32_t> count((size_t)so.lsize, 0);
-  for (size_t k = 0; k < nnz; k++) count[streamhost::dof_of(so.h_sidx[k])]++;
-  std::vector<int32_t> shared;
-  shared.reserve(so.h_shared.size());
-  if (!so.h_price_skip.empty()) {  // (pricing experiment: copies taken off the E-vector are not copies)
-    std::fill(count.begin(), count.end(), 0);
-    for (size_t k = 0; k < nnz; k++)
-      if (!so.h_price_skip[k]) count[streamhost::dof_of(so.h_sidx[k])]++;
-  }
-  for (int d = 0; d < so.lsize; d++)
-    if (count[d] != 1 || flag[d]) shared.push_back(d);
-  std::vector<uint32_t> code;
-  std::vector<RunHdr> hdr;
-  std::vector<int32_t> rpos;
-  streamhost::build_runs(so.ne, P, so.lsize, so.h_sidx.data(), shared, code, hdr, rpos, flag.data(),  // (runs: all essential or none)
-                         so.h_price_skip.empty() ? nullptr : so.h_price_skip.data());
-  hipFree(so.d_rhdr_bc), hipFree(so.d_rpos_bc), hipFree(so.d_rchunk_bc);
-  {
-    const std::vector<RunChunk> ch = streamhost::run_chunks(code);
-    so.d_rchunk_bc = dev_upload(reinterpret_cast<const uint32_t *>(ch.data()), 4 * ch.size());
-  }
-  so.d_rhdr_bc = dev_upload(reinterpret_cast<const int32_t *>(hdr.data()), 2 * hdr.size());
-  so.d_rpos_bc = dev_upload(rpos.data(), rpos.size());
-  so.n_shared_bc = (int)shared.size();
-  so.n_runs_bc = (int)hdr.size() - 1;
+  streamhost::mark_essential(flag_layout(so), pb, so.ne, so.h_sidx.data(), flag.data(), true);
+  StreamTables &t = so.stream[kStreamMasked];
+  t.release();
+  t.d_flags = upload_flags(so, pb);
+  upload_runs(t, so, streamhost::gather_rows(so.ne, so.P, so.lsize, so.h_sidx.data(), flag.data(), price_skip(so), false), flag.data(),
+              price_skip(so));
 }
 
 void free_stream(SubOp &so) {
-  hipFree(so.d_idxc), hipFree(so.d_perm_s), hipFree(so.d_perm_s_bc), hipFree(so.d_coef_s);
-  hipFree(so.d_flagw), hipFree(so.d_flagw_bc), hipFree(so.d_slots);
-  hipFree(so.d_flagw_all), hipFree(so.d_perm_s_all), hipFree(so.d_rchunk_all), hipFree(so.d_rhdr_all), hipFree(so.d_rpos_all);
-  so.d_flagw_all = so.d_perm_s_all = nullptr, so.d_rchunk_all = nullptr, so.d_rhdr_all = so.d_rpos_all = nullptr, so.n_all = 0;
-  hipFree(so.d_rhdr), hipFree(so.d_rpos), hipFree(so.d_rhdr_bc), hipFree(so.d_rpos_bc), hipFree(so.d_rchunk), hipFree(so.d_rchunk_bc);
-}
-
-static int device_cus() {
-  static int cus = [] {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
-      n = 256;
-    return n;
-  }();
-  return cus;
+  hipFree(so.d_idxc), hipFree(so.d_slots), hipFree(so.d_coef_s);
+  for (StreamTables &t : so.stream) t.release();
 }
 
 template <int P1, bool U, bool C, bool METRIC, int MINW, int GPOS, bool CPLX = false, bool SPLIT = false, int GEOMN = 0>
@@ -1134,22 +1081,15 @@ static void launch_gpos(const SubOp &so, NDStreamArgs<P1> &a, hipStream_t s) {
   // resident workgroups per CU: registers (MINW waves per SIMD), LDS (160 KB), at most 8
   // workgroups per CU: what the registers (MINW waves per SIMD) and the LDS admit, and not more than the occupancy query
   // says -- with a fixed stride a workgroup that had to queue would run after the others and double the time
-  static const int wg_env = getenv("PALACE_AMD_STREAM_WG") ? atoi(getenv("PALACE_AMD_STREAM_WG")) : 0;
-  static const int per_cu_query = [&] {
-    int nb = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, nd_hex_stream_kernel<P1, U, C, METRIC, MINW, GPOS, CPLX, SPLIT, GEOMN>,
-                                                     64 * kWavesPerBlock, lds) != hipSuccess || nb <= 0)
-      nb = 8;
-    return std::min({nb, MINW * 4 / kWavesPerBlock, (int)(160 * 1024 / lds), 8});
-  }();
-  const int per_cu = wg_env > 0 ? wg_env : per_cu_query;
-  const int per_xcd = std::max(1, device_cus() / 8) * per_cu;
+  static const int wg_env = stream_env_int("PALACE_AMD_STREAM_WG");
+  static const int per_cu_query =
+      std::min({stream_occupancy(nd_hex_stream_kernel<P1, U, C, METRIC, MINW, GPOS, CPLX, SPLIT, GEOMN>, 64 * kWavesPerBlock, lds, 8),
+                MINW * 4 / kWavesPerBlock, (int)(160 * 1024 / lds), 8});
   if (CPLX) a.nbatch = (so.ne + 1) / 2;  // two elements times two parts per batch
   else a.nbatch = (so.ne + 3) / 4;
   if (a.nbatch == 0) return;
   a.chunk = (a.nbatch + 7) / 8;
-  const int waves = std::min(per_xcd * kWavesPerBlock, a.chunk);
-  const int wgx = std::max(1, (waves + kWavesPerBlock - 1) / kWavesPerBlock);
+  const int wgx = stream_wgx(wg_env > 0 ? wg_env : per_cu_query, a.chunk, kWavesPerBlock, false);
   hipLaunchKernelGGL((nd_hex_stream_kernel<P1, U, C, METRIC, MINW, GPOS, CPLX, SPLIT, GEOMN>), dim3(8 * wgx), dim3(64 * kWavesPerBlock),
                      lds, s, a);
   PA_HIP(hipGetLastError());
@@ -1173,19 +1113,12 @@ static void launch_variant(const SubOp &so, NDStreamArgs<P1> &a, hipStream_t s) 
 }
 
 template <int P1>
-static void launch_p(const SubOp &so, const double *x, double *y, bool masked, hipStream_t s, const SplitIO *split,
-                     bool all = false) {
+static void launch_p(const SubOp &so, const double *x, double *y, StreamForm form, hipStream_t s, const SplitIO *split) {
   NDStreamArgs<P1> a{};  // (every field the chosen form does not use: zero)
-  a.nsplit = -1, a.xg0 = a.xg1 = nullptr, a.xg_sel = nullptr, a.yg = nullptr;
-  if (split) {
-    PA_REQUIRE(split->n_true >= 0 && split->n_true <= so.lsize, "split point outside the local vector");
-    a.nsplit = split->n_true;
-    a.xg0 = split->xg0 - split->n_true, a.xg1 = (split->xg1 ? split->xg1 : split->xg0) - split->n_true;
-    a.xg_sel = split->sel, a.yg = split->yg - split->n_true;
-  }
+  stream_set_split(a, split, so.lsize);
   a.ne = so.ne, a.nbatch = 0;
   a.idxc = so.d_idxc;
-  a.flagw = all ? so.d_flagw_all : (masked ? so.d_flagw_bc : so.d_flagw);
+  a.flagw = so.stream[form].d_flags;
   a.slots = so.d_slots;
   a.qdata = so.qd->d;
   a.qaff = so.qd->d_aff, a.qcol = so.qd->d_col, a.wq2[0] = so.qd->wq2[0], a.wq2[1] = so.qd->wq2[1];
@@ -1230,17 +1163,8 @@ static void launch_p(const SubOp &so, const double *x, double *y, bool masked, h
 }
 
 void launch_nd_hex_stream_all(const SubOp &so, const double *x, hipStream_t s, const SplitIO *split) {
-  PA_REQUIRE(so.n_all > 0, "stream_build_all has not been called");
-  double *unused = so.d_ye;  // (no entry is exclusive in this form: y is never written)
-  if (so.fe_type == PA_FE_H1) return launch_h1_hex_stream(so, x, unused, true, s, split, true);
-  if (wide_form(so)) return launch_nd_hex_stream5(so, x, unused, true, s, split, true);
-  if (three_point_form(so)) return launch_nd_hex_stream3(so, x, unused, true, s, split, true);
-  switch (so.p) {
-    case 1: launch_p<1>(so, x, unused, true, s, split, true); break;
-    case 2: launch_p<2>(so, x, unused, true, s, split, true); break;
-    case 3: launch_p<3>(so, x, unused, true, s, split, true); break;
-    default: throw Error("no streaming H(curl) hex kernel for this order");
-  }
+  PA_REQUIRE(so.stream[kStreamAll].ready(), "stream_build_all has not been called");
+  launch_nd_hex_stream(so, x, so.d_ye, kStreamAll, s, split);  // (no entry is exclusive in this form: y is never written)
 }
 
 bool nd_hex_stream_split_ok(const SubOp &so) {
@@ -1248,13 +1172,16 @@ bool nd_hex_stream_split_ok(const SubOp &so) {
          (so.q1d == 4 || (wide_form(so) && nd_hex_stream5_ok(so)) || (three_point_form(so) && nd_hex_stream3_ok(so)));
 }
 
-void launch_nd_hex_stream(const SubOp &so, const double *x, double *y, bool masked, hipStream_t s, const SplitIO *split) {
-  if (wide_form(so)) return launch_nd_hex_stream5(so, x, y, masked, s, split);
-  if (three_point_form(so)) return launch_nd_hex_stream3(so, x, y, masked, s, split);
+// the element kernel of a streaming block on the tables of `form`: H(curl) at three, four or five points, and H1
+// (pa_h1_hex_stream.hip).  The callers have checked that the form is built.
+void launch_nd_hex_stream(const SubOp &so, const double *x, double *y, StreamForm form, hipStream_t s, const SplitIO *split) {
+  if (so.fe_type == PA_FE_H1) return launch_h1_hex_stream(so, x, y, form, s, split);
+  if (wide_form(so)) return launch_nd_hex_stream5(so, x, y, form, s, split);
+  if (three_point_form(so)) return launch_nd_hex_stream3(so, x, y, form, s, split);
   switch (so.p) {
-    case 1: launch_p<1>(so, x, y, masked, s, split); break;
-    case 2: launch_p<2>(so, x, y, masked, s, split); break;
-    case 3: launch_p<3>(so, x, y, masked, s, split); break;
+    case 1: launch_p<1>(so, x, y, form, s, split); break;
+    case 2: launch_p<2>(so, x, y, form, s, split); break;
+    case 3: launch_p<3>(so, x, y, form, s, split); break;
     default: throw Error("no streaming H(curl) hex kernel for this order");
   }
 }
@@ -1292,7 +1219,7 @@ static void launch_complex_p(const SubOp &sr, const SubOp &si, const double *xr,
   NDStreamArgs<P1> a{};  // (every field the chosen form does not use: zero)
   a.ne = sr.ne, a.nbatch = 0;
   a.idxc = sr.d_idxc;
-  a.flagw = masked ? sr.d_flagw_bc : sr.d_flagw;
+  a.flagw = sr.stream[stream_form(masked)].d_flags;
   a.slots = sr.d_slots;
   a.qdata = sr.qd->d;
   if (sr.qd->metric)  // (affine and column batches: the metric form)
@@ -1301,7 +1228,7 @@ static void launch_complex_p(const SubOp &sr, const SubOp &si, const double *xr,
   a.coef = sr.d_coef_s, a.coef1 = si.d_coef_s;
   a.xn = nullptr, a.gtab = nullptr;
   a.x = xr, a.x1 = xi, a.y = yr, a.y1 = yi, a.ye = sr.d_ye, a.ye1 = ye_i;
-  a.nsplit = -1, a.xg0 = a.xg1 = nullptr, a.xg_sel = nullptr, a.yg = nullptr;
+  stream_set_split(a, nullptr, sr.lsize);
   a.qdata1 = nullptr;
   if (sr.qd->metric) return launch_gpos<P1, true, true, true, 2, 2, true>(sr, a, s);
   const SubOp *ops[2] = {&sr, &si};
@@ -1327,112 +1254,58 @@ void launch_nd_hex_stream_complex(const SubOp &sr, const SubOp &si, const double
   }
 }
 
-// masked: the run list that owns the essential rows (the element kernel then ran on the _bc index arrays); ess_policy >= 0
-// additionally fuses ParOperator's fix-up y[ess] = x[ess] | 0 into it
-void launch_et_run_gather(const SubOp &so, double *y, bool accumulate, hipStream_t s, const double *x, bool masked,
-                          int ess_policy, const double *ye, const SplitIO *split) {
-  const int n = masked ? so.n_shared_bc : so.n_shared;
+// One launch of the run gather on the tables of `form`.  Forms other than plain own the essential rows (the element kernel then
+// ran on the same form's flag words); ess_policy >= 0 additionally fuses ParOperator's fix-up y[ess] = x[ess] | 0 into them
+template <bool STEP, bool DUAL = false>
+static void launch_run_gather(const SubOp &so, StreamForm form, const double *ye, double *y, bool accumulate, const double *x,
+                              int ess_policy, const SplitIO *split, const GatherStep &step, const GatherPart2 &p2, hipStream_t s) {
+  const StreamTables &t = so.stream[form];
+  const int n = t.n_rows;
   if (n == 0) return;
-  PA_REQUIRE(!split || !accumulate, "split vectors: y = A x only");
-  hipLaunchKernelGGL(et_run_gather_kernel_t<false>, dim3((n + 256 * kGatherILP - 1) / (256 * kGatherILP)), dim3(256), 0, s, n,
-                     reinterpret_cast<const RunChunk *>(masked ? so.d_rchunk_bc : so.d_rchunk),
-                     reinterpret_cast<const RunHdr *>(masked ? so.d_rhdr_bc : so.d_rhdr),
-                     masked ? so.d_rpos_bc : so.d_rpos, ye ? ye : so.d_ye, y, accumulate ? 1 : 0, x, masked ? ess_policy : -1,
-                     split ? split->n_true : 0x7fffffff, split ? split->yg - split->n_true : nullptr, GatherStep{}, GatherPart2{});
+  hipLaunchKernelGGL((et_run_gather_kernel_t<STEP, DUAL>), dim3((n + 256 * kGatherILP - 1) / (256 * kGatherILP)), dim3(256), 0, s, n,
+                     reinterpret_cast<const RunChunk *>(t.d_rchunk), reinterpret_cast<const RunHdr *>(t.d_rhdr), t.d_rpos, ye, y,
+                     accumulate ? 1 : 0, x, form != kStreamPlain ? ess_policy : -1, split ? split->n_true : 0x7fffffff,
+                     split ? split->yg - split->n_true : nullptr, step, p2);
   PA_HIP(hipGetLastError());
 }
 
+void launch_et_run_gather(const SubOp &so, double *y, bool accumulate, hipStream_t s, const double *x, StreamForm form,
+                          int ess_policy, const double *ye, const SplitIO *split) {
+  PA_REQUIRE(!split || !accumulate, "split vectors: y = A x only");
+  launch_run_gather<false>(so, form, ye ? ye : so.d_ye, y, accumulate, x, ess_policy, split, GatherStep{}, GatherPart2{}, s);
+}
+
 // the two parts of a one-pass complex apply in one launch: y = sum of `so.d_ye`, y1 = sum of ye1 (same runs, same order)
-void launch_et_run_gather2(const SubOp &so, double *y, double *y1, hipStream_t s, const double *x, const double *x1, bool masked,
+void launch_et_run_gather2(const SubOp &so, double *y, double *y1, hipStream_t s, const double *x, const double *x1, StreamForm form,
                            int ess_policy, const double *ye1) {
-  const int n = masked ? so.n_shared_bc : so.n_shared;
-  if (n == 0) return;
-  hipLaunchKernelGGL((et_run_gather_kernel_t<false, true>), dim3((n + 256 * kGatherILP - 1) / (256 * kGatherILP)), dim3(256), 0, s, n,
-                     reinterpret_cast<const RunChunk *>(masked ? so.d_rchunk_bc : so.d_rchunk),
-                     reinterpret_cast<const RunHdr *>(masked ? so.d_rhdr_bc : so.d_rhdr),
-                     masked ? so.d_rpos_bc : so.d_rpos, so.d_ye, y, 0, x, masked ? ess_policy : -1, 0x7fffffff, nullptr, GatherStep{},
-                     GatherPart2{ye1, x1, y1});
-  PA_HIP(hipGetLastError());
+  launch_run_gather<false, true>(so, form, so.d_ye, y, false, x, ess_policy, nullptr, GatherStep{}, GatherPart2{ye1, x1, y1}, s);
 }
 
 // ---- the fused smoother step: every dof through the E-vector, consumed by the gather's epilogue -------------------------------
 bool stream_build_all(SubOp &so) {
-  if (so.n_all > 0) return true;
-  const bool wide = wide_form(so), h1 = so.fe_type == PA_FE_H1;
-  // (H1 blocks on the streaming kernel: the flag word is the last row of the element's block of slot words, pa_h1_hex_stream.hip)
-  if (!so.d_idxc || (!h1 && so.fe_type != PA_FE_HCURL) || (!wide && !h1 && !so.d_flagw) || so.h_perm_s.empty()) return false;
-  const int P = so.P, npl = (P + 15) / 16, npk = (npl + 3) / 4, nep = (so.ne + 3) & ~3;
-  const size_t nnz = (size_t)so.ne * P;
+  StreamTables &t = so.stream[kStreamAll];
+  if (t.ready()) return true;
+  if (!so.stream[kStreamPlain].ready() || (so.fe_type != PA_FE_H1 && so.fe_type != PA_FE_HCURL) || so.h_perm_s.empty()) return false;
   std::vector<char> flag(so.h_ess_flag);
   flag.resize((size_t)so.lsize, 0);
-  std::vector<uint32_t> fw;  // four-point kernel: the flag words; five-point kernel: the slot half-words with their flags
-  const int npkw = ((P + 31) / 32 + 1) / 2;
-  if (wide) {
-    fw = so.h_perm_s;
-    for (uint32_t &w : fw) w &= ~(streamhost::kWideExcl | (streamhost::kWideExcl << 16));  // nothing takes the direct path
-  } else if (h1) {
-    fw = so.h_perm_s;  // [nep][npk + 1][16]: the flag words are row npk
-    for (int e = 0; e < nep; e++)
-      for (int t = 0; t < 16; t++)
-        for (int r = 0; r < npl; r++) fw[((size_t)e * (npk + 1) + npk) * 16 + t] &= ~(2u << (2 * r));
-  } else {
-    fw.resize((size_t)nep * 16);
-    for (int e = 0; e < nep; e++)
-      for (int t = 0; t < 16; t++) {
-        uint32_t w = so.h_perm_s[((size_t)e * (npk + 1) + npk) * 16 + t];
-        for (int r = 0; r < npl; r++) w &= ~(2u << (2 * r));  // nothing takes the direct path
-        fw[(size_t)e * 16 + t] = w;
-      }
-  }
-  std::vector<char> present((size_t)so.lsize, 0);
-  for (size_t k = 0; k < nnz; k++) {
-    const int d = streamhost::dof_of(so.h_sidx[k]);
-    present[d] = 1;
-    if (flag[d]) {
-      const size_t e = k / P;
-      if (wide) {
-        const int m = (int)(k - e * P), t = m & 31, r = m >> 5;
-        fw[(e * npkw + (r >> 1)) * 32 + t] |= streamhost::kWideEss << (16 * (r & 1));  // read as zero
-      } else if (h1) {
-        const int m = (int)(k - e * P), t = m & 15, r = m >> 4;
-        fw[(e * (npk + 1) + npk) * 16 + t] |= 1u << (18 + r);
-      } else {
-        const int m = (int)(k - e * P), t = m & 15, r = m >> 4;
-        fw[e * 16 + t] |= 1u << (18 + r);  // read as zero
-      }
-    }
-  }
-  std::vector<int32_t> all;
-  all.reserve((size_t)so.lsize);
-  for (int d = 0; d < so.lsize; d++)
-    if (present[d] || flag[d]) all.push_back(d);
+  const std::vector<int32_t> all = streamhost::gather_rows(so.ne, so.P, so.lsize, so.h_sidx.data(), flag.data(), nullptr, true);
   if ((int)all.size() != so.lsize) return false;  // (a dof no element holds: the plain forms leave it alone, the step must not)
-  std::vector<uint32_t> code;
-  std::vector<RunHdr> hdr;
-  std::vector<int32_t> rpos;
-  streamhost::build_runs(so.ne, P, so.lsize, so.h_sidx.data(), all, code, hdr, rpos, flag.data(), nullptr);
-  const std::vector<RunChunk> ch = streamhost::run_chunks(code);
-  so.d_rchunk_all = dev_upload(reinterpret_cast<const uint32_t *>(ch.data()), 4 * ch.size());
-  so.d_rhdr_all = dev_upload(reinterpret_cast<const int32_t *>(hdr.data()), 2 * hdr.size());
-  so.d_rpos_all = dev_upload(rpos.data(), rpos.size());
-  so.n_all = (int)all.size(), so.n_runs_all = (int)hdr.size() - 1;
-  if (wide || h1)
-    so.d_perm_s_all = dev_upload(fw.data(), fw.size());
-  else
-    so.d_flagw_all = dev_upload(fw.data(), fw.size());
+  const streamhost::FlagLayout fl = flag_layout(so);
+  std::vector<uint32_t> fw(so.h_perm_s);
+  streamhost::clear_only_copy(fl, fw);
+  streamhost::mark_essential(fl, fw, so.ne, so.h_sidx.data(), flag.data(), false);
+  t.d_flags = upload_flags(so, fw);
+  upload_runs(t, so, all, flag.data(), nullptr);
   return true;
 }
 
-void launch_et_run_gather_step(const SubOp &so, const double *x, const GatherStep &step, int ess_policy, hipStream_t s,
+void launch_et_run_gather_step(const SubOp &so, StreamForm form, const double *x, const GatherStep &step, int ess_policy, hipStream_t s,
                                const SplitIO *split) {
-  PA_REQUIRE(so.n_all > 0, "stream_build_all has not been called");
+  // (the epilogue consumes the sum of EVERY row, so only the form whose gather owns them all can run it; the parameter is
+  // there so that the three gathers read alike at their call sites)
+  PA_REQUIRE(form == kStreamAll && so.stream[form].ready(), "stream_build_all has not been called");
   PA_REQUIRE(!split || (step.iface_mask && step.t_iface), "split form of the fused step: interface mask and buffer missing");
-  const int n = so.n_all;
-  hipLaunchKernelGGL(et_run_gather_kernel_t<true>, dim3((n + 256 * kGatherILP - 1) / (256 * kGatherILP)), dim3(256), 0, s, n,
-                     reinterpret_cast<const RunChunk *>(so.d_rchunk_all), reinterpret_cast<const RunHdr *>(so.d_rhdr_all), so.d_rpos_all,
-                     so.d_ye, nullptr, 0, x, ess_policy, split ? split->n_true : 0x7fffffff, split ? split->yg - split->n_true : nullptr,
-                     step, GatherPart2{});
-  PA_HIP(hipGetLastError());
+  launch_run_gather<true>(so, form, so.d_ye, nullptr, false, x, ess_policy, split, step, GatherPart2{}, s);
 }
 
 #ifdef PA_STREAM_TRACE

@@ -29,6 +29,7 @@
 #include <algorithm>
 
 #include "pa_nd_hex_core.hpp"
+#include "pa_stream_launch.hpp"
 
 namespace pa {
 
@@ -285,17 +286,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, MINW) void nd_hex_stream3_kern
 bool nd_hex_stream3_ok(const SubOp &so) {
   if (so.fe_type != PA_FE_HCURL || so.q1d != 3 || so.p > 2 || !so.qd || !so.d_ye || !so.d_perm_x) return false;
   if (!so.d_idxc && !(getenv("PALACE_AMD_STREAM3") && atoi(getenv("PALACE_AMD_STREAM3")) == 1)) return false;
-  return so.qd->metric || so.qd->ncomp == 6 || (so.qd->ncomp == 12 && so.qf == PA_QF_HDIVMASS_33);
-}
-
-static int device_cus3() {
-  static int cus = [] {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
-      n = 256;
-    return n;
-  }();
-  return cus;
+  return stream_qdata_ok(so);
 }
 
 template <int P1, bool U, bool C, bool METRIC, int MINW, bool SPLIT>
@@ -305,24 +296,15 @@ static void launch3_kernel(const SubOp &so, NDStream3Args<P1> &a, hipStream_t s)
   for (int i = 0; i < HalfTab<P1 + 1, 3>::LEN; i++) a.tab.Bc[i] = so.Bc[i], a.tab.Gc[i] = so.Gc[i];
   constexpr int PP = 3 * P1 * (P1 + 1) * (P1 + 1), NPK = ((PP + 15) / 16 + 3) / 4;
   const size_t lds = sizeof(double) * (size_t)(kWavesPerBlock * 4) * stream3_lds_elem(L::ELEM_PAD + (PP + 1) / 2 + (NPK + 1) * 8 + 12);
-  const int wg_env = getenv("PALACE_AMD_STREAM_WG") ? atoi(getenv("PALACE_AMD_STREAM_WG")) : 0;
-  // workgroups per CU: what the registers and the LDS admit, and not more than the occupancy query says (with a fixed stride
-  // a workgroup that had to queue would run after the others and double the time)
-  static const int per_cu_query = [&] {
-    int nb = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, nd_hex_stream3_kernel<P1, U, C, METRIC, MINW, SPLIT>, 64 * kWavesPerBlock, lds) !=
-            hipSuccess || nb <= 0)
-      nb = MINW * 4 / kWavesPerBlock;
-    return std::min({nb, (int)(160 * 1024 / lds), 8});
-  }();
-  const int per_cu = wg_env > 0 ? wg_env : per_cu_query;
-  const int per_xcd = std::max(1, device_cus3() / 8) * per_cu;
+  const int wg_env = stream_env_int("PALACE_AMD_STREAM_WG");
+  // workgroups per CU: what the registers and the LDS admit, and not more than the occupancy query says
+  static const int per_cu_query =
+      std::min({stream_occupancy(nd_hex_stream3_kernel<P1, U, C, METRIC, MINW, SPLIT>, 64 * kWavesPerBlock, lds, MINW * 4 / kWavesPerBlock),
+                (int)(160 * 1024 / lds), 8});
   a.nbatch = (so.ne + 3) / 4;
   if (a.nbatch == 0) return;
   a.chunk = (a.nbatch + 7) / 8;
-  int wgx = std::max(1, std::min(per_xcd, (a.chunk + kWavesPerBlock - 1) / kWavesPerBlock));
-  // PALACE_AMD_STREAM_WGX caps the workgroups per XCD (tests: many batches per wave on a small mesh)
-  if (const char *cap = getenv("PALACE_AMD_STREAM_WGX")) wgx = std::max(1, std::min(wgx, atoi(cap)));
+  const int wgx = stream_wgx(wg_env > 0 ? wg_env : per_cu_query, a.chunk, kWavesPerBlock, true);
   hipLaunchKernelGGL((nd_hex_stream3_kernel<P1, U, C, METRIC, MINW, SPLIT>), dim3(8 * wgx), dim3(64 * kWavesPerBlock), lds, s, a);
   PA_HIP(hipGetLastError());
 }
@@ -335,18 +317,12 @@ static void launch3_variant(const SubOp &so, NDStream3Args<P1> &a, hipStream_t s
 }
 
 template <int P1>
-static void launch3_p(const SubOp &so, const double *x, double *y, bool masked, hipStream_t s, const SplitIO *split, bool all) {
+static void launch3_p(const SubOp &so, const double *x, double *y, StreamForm form, hipStream_t s, const SplitIO *split) {
   NDStream3Args<P1> a{};
-  a.nsplit = -1, a.xg0 = a.xg1 = nullptr, a.xg_sel = nullptr, a.yg = nullptr;
-  if (split) {
-    PA_REQUIRE(split->n_true >= 0 && split->n_true <= so.lsize, "split point outside the local vector");
-    a.nsplit = split->n_true;
-    a.xg0 = split->xg0 - split->n_true, a.xg1 = (split->xg1 ? split->xg1 : split->xg0) - split->n_true;
-    a.xg_sel = split->sel, a.yg = split->yg - split->n_true;
-  }
+  stream_set_split(a, split, so.lsize);
   a.ne = so.ne, a.nbatch = 0;
   a.idxc = so.d_idxc;
-  a.flagw = all ? so.d_flagw_all : (masked ? so.d_flagw_bc : so.d_flagw);  // (all: no entry exclusive -- the fused smoother step)
+  a.flagw = so.stream[form].d_flags;
   a.slots = so.d_slots;
   PA_REQUIRE(a.idxc && a.flagw && a.slots, "the streaming tables of this block have not been built");
   a.qdata = so.qd->d;
@@ -371,10 +347,10 @@ static void launch3_p(const SubOp &so, const double *x, double *y, bool masked, 
   }
 }
 
-void launch_nd_hex_stream3(const SubOp &so, const double *x, double *y, bool masked, hipStream_t s, const SplitIO *split, bool all) {
+void launch_nd_hex_stream3(const SubOp &so, const double *x, double *y, StreamForm form, hipStream_t s, const SplitIO *split) {
   switch (so.p) {
-    case 1: launch3_p<1>(so, x, y, masked, s, split, all); break;
-    case 2: launch3_p<2>(so, x, y, masked, s, split, all); break;
+    case 1: launch3_p<1>(so, x, y, form, s, split); break;
+    case 2: launch3_p<2>(so, x, y, form, s, split); break;
     default: throw Error("no three-point streaming H(curl) hex kernel for this order");
   }
 }

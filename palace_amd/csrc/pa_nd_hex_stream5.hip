@@ -16,6 +16,7 @@
 #include <type_traits>
 
 #include "pa_nd_hex_core.hpp"
+#include "pa_stream_launch.hpp"
 
 namespace pa {
 
@@ -391,17 +392,7 @@ bool nd_hex_stream5_ok(const SubOp &so) {
   if (getenv("PALACE_AMD_STREAM5") && atoi(getenv("PALACE_AMD_STREAM5")) == 0) return false;
   if (so.fe_type != PA_FE_HCURL || so.q1d != 5 || so.p > 4 || !so.qd || !so.d_ye || !so.d_perm_x) return false;
   // (packed D of both terms -- anisotropic materials, twelve rows per point -- for the curl-curl + mass QFunction only)
-  return so.qd->metric || so.qd->ncomp == 6 || (so.qd->ncomp == 12 && so.qf == PA_QF_HDIVMASS_33);
-}
-
-static int device_cus5() {
-  static int cus = [] {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
-      n = 256;
-    return n;
-  }();
-  return cus;
+  return stream_qdata_ok(so);
 }
 
 template <int P1, bool U, bool C, bool METRIC, int GPOS, int QPOS, bool CPLX = false, bool SPLIT = false>
@@ -411,24 +402,15 @@ static void launch5_gpos(const SubOp &so, NDStream5Args<P1> &a, hipStream_t s) {
   for (int i = 0; i < HalfTab<P1 + 1, 5>::LEN; i++) a.tab.Bc[i] = so.Bc[i], a.tab.Gc[i] = so.Gc[i];
   constexpr int PP = 3 * P1 * (P1 + 1) * (P1 + 1), NPL = (PP + 31) / 32, NPK = (NPL + 1) / 2;
   const size_t lds = sizeof(double) * (size_t)(kWavesPerBlock * 2) * (((L::ELEM + 1) & ~1) + ((PP + 1) & ~1) + NPK * 16 + streamhost::kWideWords);
-  const int wg_env = getenv("PALACE_AMD_STREAM_WG") ? atoi(getenv("PALACE_AMD_STREAM_WG")) : 0;
+  const int wg_env = stream_env_int("PALACE_AMD_STREAM_WG");
   // workgroups per CU: what the registers (two waves per SIMD) and the LDS admit, and not more than the occupancy query says
-  // (with a fixed stride a workgroup that had to queue would run after the others and double the time)
-  static const int per_cu_query = [&] {
-    int nb = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, nd_hex_stream5_kernel<P1, U, C, METRIC, GPOS, QPOS, CPLX, SPLIT>, 64 * kWavesPerBlock, lds) !=
-            hipSuccess || nb <= 0)
-      nb = 4;
-    return std::min({nb, (int)(160 * 1024 / lds), 8});
-  }();
-  const int per_cu = wg_env > 0 ? wg_env : per_cu_query;
-  const int per_xcd = std::max(1, device_cus5() / 8) * per_cu;
+  static const int per_cu_query =
+      std::min({stream_occupancy(nd_hex_stream5_kernel<P1, U, C, METRIC, GPOS, QPOS, CPLX, SPLIT>, 64 * kWavesPerBlock, lds, 4),
+                (int)(160 * 1024 / lds), 8});
   a.nbatch = CPLX ? so.ne : (so.ne + 1) / 2;  // (complex form: one element per wave)
   if (a.nbatch == 0) return;
   a.chunk = (a.nbatch + 7) / 8;
-  int wgx = std::max(1, std::min(per_xcd, (a.chunk + kWavesPerBlock - 1) / kWavesPerBlock));
-  // PALACE_AMD_STREAM_WGX caps the workgroups per XCD (tests: many batches per wave on a small mesh)
-  if (const char *cap = getenv("PALACE_AMD_STREAM_WGX")) wgx = std::max(1, std::min(wgx, atoi(cap)));
+  const int wgx = stream_wgx(wg_env > 0 ? wg_env : per_cu_query, a.chunk, kWavesPerBlock, true);
   hipLaunchKernelGGL((nd_hex_stream5_kernel<P1, U, C, METRIC, GPOS, QPOS, CPLX, SPLIT>), dim3(8 * wgx), dim3(64 * kWavesPerBlock), lds, s, a);
   PA_HIP(hipGetLastError());
 }
@@ -442,19 +424,12 @@ static void launch5_variant(const SubOp &so, NDStream5Args<P1> &a, hipStream_t s
 }
 
 template <int P1>
-static void launch5_p(const SubOp &so, const double *x, double *y, bool masked, hipStream_t s, const SplitIO *split,
-                      bool all = false) {
+static void launch5_p(const SubOp &so, const double *x, double *y, StreamForm form, hipStream_t s, const SplitIO *split) {
   NDStream5Args<P1> a;
-  a.nsplit = -1, a.xg0 = a.xg1 = nullptr, a.xg_sel = nullptr, a.yg = nullptr;
-  if (split) {
-    PA_REQUIRE(split->n_true >= 0 && split->n_true <= so.lsize, "split point outside the local vector");
-    a.nsplit = split->n_true;
-    a.xg0 = split->xg0 - split->n_true, a.xg1 = (split->xg1 ? split->xg1 : split->xg0) - split->n_true;
-    a.xg_sel = split->sel, a.yg = split->yg - split->n_true;
-  }
+  stream_set_split(a, split, so.lsize);
   a.ne = so.ne, a.nbatch = 0;
   a.idxw = so.d_idxc;
-  a.perm = all ? so.d_perm_s_all : (masked ? so.d_perm_s_bc : so.d_perm_s);  // (all: no entry exclusive -- the fused smoother step)
+  a.perm = so.stream[form].d_flags;
   a.qdata = so.qd->d;
   a.qdata1 = nullptr;
   for (int g = 0; g < 2; g++) a.qm[g] = a.qc[g] = -1, a.qn[g] = 0;
@@ -477,13 +452,12 @@ static void launch5_p(const SubOp &so, const double *x, double *y, bool masked, 
   }
 }
 
-void launch_nd_hex_stream5(const SubOp &so, const double *x, double *y, bool masked, hipStream_t s, const SplitIO *split,
-                           bool all) {
+void launch_nd_hex_stream5(const SubOp &so, const double *x, double *y, StreamForm form, hipStream_t s, const SplitIO *split) {
   switch (so.p) {
-    case 1: launch5_p<1>(so, x, y, masked, s, split, all); break;
-    case 2: launch5_p<2>(so, x, y, masked, s, split, all); break;
-    case 3: launch5_p<3>(so, x, y, masked, s, split, all); break;
-    case 4: launch5_p<4>(so, x, y, masked, s, split, all); break;
+    case 1: launch5_p<1>(so, x, y, form, s, split); break;
+    case 2: launch5_p<2>(so, x, y, form, s, split); break;
+    case 3: launch5_p<3>(so, x, y, form, s, split); break;
+    case 4: launch5_p<4>(so, x, y, form, s, split); break;
     default: throw Error("no five-point streaming H(curl) hex kernel for this order");
   }
 }
@@ -493,11 +467,11 @@ static void launch5_complex_p(const SubOp &sr, const SubOp &si, const double *xr
   NDStream5Args<P1> a;
   a.ne = sr.ne, a.nbatch = 0;
   a.idxw = sr.d_idxc;
-  a.perm = masked ? sr.d_perm_s_bc : sr.d_perm_s;
+  a.perm = sr.stream[stream_form(masked)].d_flags;
   a.qdata = sr.qd->d;
   a.coef = sr.d_coef_s, a.coef1 = si.d_coef_s;
   a.x = xr, a.x1 = xi, a.y = yr, a.y1 = yi, a.ye = sr.d_ye, a.ye1 = ye_i;
-  a.nsplit = -1, a.xg0 = a.xg1 = nullptr, a.xg_sel = nullptr, a.yg = nullptr;
+  stream_set_split(a, nullptr, sr.lsize);
   a.qdata1 = nullptr;
   const SubOp *ops[2] = {&sr, &si};
   for (int g = 0; g < 2; g++) {  // (pa_nd_hex.hip: packed q-data holds the mass block first, then the curl-curl block)

@@ -176,6 +176,80 @@ inline bool pack_index_wide(int ne, int P, int lsize, const int32_t *sidx, const
   return true;
 }
 
+// ---- where the flags live ------------------------------------------------------------------------------------------------
+// The flags of sorted entry m of element e (flipped, only copy of its dof, essential) in the three arrays that carry them:
+//   kFlagRow    pp of pack_index, [nep][npk + 1][16]: row npk of the element's block (what the H1 kernel reads; H(curl)
+//               blocks at three and four points are edited in this form and split off afterwards)
+//   kFlagSplit  that row on its own, [nep][16] (split_flag_rows: three- and four-point H(curl) kernels).  The library never
+//               edits this form -- it edits kFlagRow and splits; the kind is here for tests/cpu/stream_host_check.cpp, which
+//               checks that the same edit made on the split rows gives the same words
+//   kFlagWide   pp of pack_index_wide, [nep][npk][32]: the flags ride in the entry's slot half-word
+struct FlagLayout {
+  enum Kind { kFlagRow, kFlagSplit, kFlagWide } kind;
+  int P;
+  int lanes() const { return kind == kFlagWide ? 32 : 16; }
+  int slices() const { return (P + lanes() - 1) / lanes(); }
+  int padded(int ne) const { return kind == kFlagWide ? (ne + 1) & ~1 : (ne + 3) & ~3; }  // elements, whole batches
+  int elem_words() const {
+    return kind == kFlagWide ? (slices() + 1) / 2 * 32 : (kind == kFlagSplit ? 16 : ((slices() + 3) / 4 + 1) * 16);
+  }
+  size_t word(size_t e, int m) const {  // the word of the array that holds the flags of entry m
+    const int t = m & (lanes() - 1), r = m / lanes();
+    if (kind == kFlagWide) return e * elem_words() + (r >> 1) * 32 + t;
+    return (e + 1) * elem_words() - 16 + t;
+  }
+  // the flag bits of entry m in that word.  Wide: the half-word's bit moved to the entry's half; else slice r = m >> 4 of the lane
+  int half(int m) const { return 16 * ((m >> 5) & 1); }
+  uint32_t flipped(int m) const { return kind == kFlagWide ? kWideFlip << half(m) : 1u << (2 * (m >> 4)); }
+  uint32_t only_copy(int m) const { return kind == kFlagWide ? kWideExcl << half(m) : 2u << (2 * (m >> 4)); }  // straight to y
+  uint32_t essential(int m) const { return kind == kFlagWide ? kWideEss << half(m) : 1u << (18 + (m >> 4)); }  // read as zero
+};
+
+// no entry takes the direct path (the `all` form: the run gather owns every dof)
+inline void clear_only_copy(const FlagLayout &fl, std::vector<uint32_t> &w) {
+  const size_t nep = w.size() / fl.elem_words();
+  for (size_t e = 0; e < nep; e++)
+    for (int m = 0; m < fl.slices() * fl.lanes(); m++) w[fl.word(e, m)] &= ~fl.only_copy(m);
+}
+// entry m of element e belongs to an essential dof: read as zero and, off_direct, never stored straight to y
+inline void mark_essential(const FlagLayout &fl, std::vector<uint32_t> &w, size_t e, int m, bool off_direct) {
+  uint32_t &f = w[fl.word(e, m)];
+  if (off_direct) f &= ~fl.only_copy(m);
+  f |= fl.essential(m);
+}
+// ... of every entry whose dof is flagged in ess
+inline void mark_essential(const FlagLayout &fl, std::vector<uint32_t> &w, int ne, const int32_t *sidx, const char *ess,
+                           bool off_direct) {
+  for (size_t e = 0; e < (size_t)ne; e++)
+    for (int m = 0; m < fl.P; m++)
+      if (ess[dof_of(sidx[e * fl.P + m])]) mark_essential(fl, w, e, m, off_direct);
+}
+// a per-element bit (kAffBit / kColBit) on the sixteen lanes of element e
+inline void set_element_bit(const FlagLayout &fl, std::vector<uint32_t> &w, size_t e, uint32_t bit) {
+  for (int t = 0; t < 16; t++) w[fl.word(e, t)] |= bit;
+}
+// kFlagRow -> kFlagSplit
+inline std::vector<uint32_t> split_flag_rows(const FlagLayout &row, const std::vector<uint32_t> &pp) {
+  const size_t nep = pp.size() / row.elem_words();
+  std::vector<uint32_t> fw(nep * 16);
+  for (size_t e = 0; e < nep; e++)
+    for (int t = 0; t < 16; t++) fw[e * 16 + t] = pp[row.word(e, t)];
+  return fw;
+}
+
+// The dofs the run gather of a form owns, increasing: those that do not have exactly one copy, and the essential ones (ess,
+// optional: the gather writes their rows); all: every dof some element holds (the `all` form).  skip (optional): entries that
+// are not copies, as in build_runs.
+inline std::vector<int32_t> gather_rows(int ne, int P, int lsize, const int32_t *sidx, const char *ess, const char *skip, bool all) {
+  const size_t nnz = (size_t)ne * P;
+  std::vector<int32_t> count((size_t)lsize, 0), rows;
+  for (size_t k = 0; k < nnz; k++)
+    if (!skip || !skip[k]) count[dof_of(sidx[k])]++;
+  for (int d = 0; d < lsize; d++)
+    if ((all ? count[d] > 0 : count[d] != 1) || (ess && ess[d])) rows.push_back(d);
+  return rows;
+}
+
 // Runs over the shared dofs (`shared` increasing: every dof that does not have exactly one copy): consecutive dofs
 // with the same number of copies whose copies sit at consecutive E-vector positions, at most 16 long, all essential or none
 // (ess: optional flags per dof).

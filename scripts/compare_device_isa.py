@@ -45,6 +45,8 @@ def listing(tree, name):
 def kernels(asm):
     """name -> (text from the label to .end_amdhsa_kernel, metadata entry)"""
     lines = asm.splitlines()
+    if "amdhsa.kernels:" not in lines:  # a file of host code only
+        return {}
     names = [m.group(1) for l in lines if (m := re.match(r"\s*\.amdhsa_kernel\s+(\S+)", l))]
     start, wanted = {}, set(names)
     for i, l in enumerate(lines):
