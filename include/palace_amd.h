@@ -445,8 +445,9 @@ int pa_op_stream_affine(const pa_op *op, int32_t out[3]);
  * tensor H(curl) sub-operator; out[1] = out[2] = 0 when the form is off (PALACE_AMD_STREAM_COLUMN=0). */
 int pa_op_stream_column(const pa_op *op, int32_t out[3]);
 /* The E^T gather of the first dense-table sub-operator (round 6): out[0] = 1 if its E-vector keeps the dofs of an ELEMENT together
- * (chosen at creation by counting the 64-byte sectors the gather would read in either layout; PALACE_AMD_DENSE_ELAYOUT=rows | block
- * overrides), 0 for the rows by dof; out[1] = lanes that share the copies of one dof (1, 2, 4, 8: near the average number of copies;
+ * (chosen at creation by timing the gather on both layouts: the rows by element are taken when they are at least 15 % faster;
+ * spaces of fewer than 2^17 local dofs keep the rows by dof untimed; PALACE_AMD_DENSE_ELAYOUT=rows | block overrides), 0 for the rows
+ * by dof; out[1] = lanes that share the copies of one dof (1, 2, 4, 8: near the average number of copies;
  * PALACE_AMD_DENSE_GATHER_GROUP overrides).  Both zero when the operator has no dense block. */
 int pa_op_dense_gather_form(const pa_op *op, int32_t out[2]);
 /* number of dense sub-operators that run in the affine form: every element of the block has a constant Jacobian (straight-sided

@@ -493,14 +493,6 @@ MixedSub *make_mixed_hex_sub(pa_geom *geom, const pa_restriction_desc &r1, const
 
 // y (+)= A x.  overwrite: the first sub-operator writes y instead of accumulating (Mult without a
 // separate memset when E^T runs as a gather).
-// timing experiments (scripts/price_evec_cache.py): 1 = element kernel only, 2 = E^T run gather only (of the streaming form)
-#ifdef PA_ABLATION  // (the ablation library only, `make ablate`: the product library has no such switch)
-static int g_debug_phase = 0;
-extern "C" void pa_debug_apply_phase(int phase) { g_debug_phase = phase; }
-#else
-constexpr int g_debug_phase = 0;
-#endif
-
 static void apply(pa_op *op, const double *x, double *y, bool overwrite, hipStream_t s, bool masked = false,
                   int ess_policy = -1) {
   PA_REQUIRE(op && x && y, "null argument");
@@ -514,8 +506,8 @@ static void apply(pa_op *op, const double *x, double *y, bool overwrite, hipStre
   for (const SubOp *so : op->subs) {
     if (so->fe_type == PA_FE_HCURL) {
       if (so->d_idxc && overwrite && first && (!masked || so->stream[kStreamMasked].ready())) {  // streaming kernel (y = A x) + E^T of the shared dofs by runs
-        if (g_debug_phase != 2) launch_nd_hex_stream(*so, x, y, form, s);
-        if (g_debug_phase != 1) launch_et_run_gather(*so, y, false, s, x, form, ess_policy);
+        launch_nd_hex_stream(*so, x, y, form, s);
+        launch_et_run_gather(*so, y, false, s, x, form, ess_policy);
       } else if (so->d_ye) {
         launch_nd_hex_apply(*so, x, y, so->d_ye, masked, s, !(overwrite && first), ess_policy);
         launch_et_gather(*so, y, !(overwrite && first), s, x, ess_policy);

@@ -31,10 +31,6 @@
 #include "pa_device.hpp"
 #include "pa_internal.hpp"
 
-#ifndef PA_DENSE_XEARLY
-#define PA_DENSE_XEARLY 0
-#endif
-
 namespace pa {
 
 namespace {
@@ -152,7 +148,8 @@ struct DenseArgs {
   const double *qdata_i;
   int ncq_i, qi_mass, qi_curl;
   const double *wrel;     // [Q4] w_q / w_0
-  int dbg;  // ablation bits (PA_ABLATION builds only)
+  int : 32;  // reserved: keeps the offsets of the members behind it.  Without these eight bytes (with the padding) hipcc merges the
+             // argument loads differently: other instruction counts in 228 of this file's 329 kernels, another SGPR count in 15
   const double *x;
   double *ye;
   int ye_rows;  // E-vector layout inside a block of 16 elements: 0 = [dof][element] (one 128-byte row per dof: what the kernels' lanes
@@ -545,10 +542,7 @@ __device__ __forceinline__ void load_qd6(const double *__restrict__ q, const int
 
 // AFFINE: every block consists of elements with a constant Jacobian (dense_affine_kernel): the D of a point is the D of point 0
 // times the relative quadrature weight -- 6 values per field and element instead of 6 Q, and no q-data registers to rotate.
-#ifndef PA_DENSE_AFF_WAVES
-#define PA_DENSE_AFF_WAVES 12
-#endif
-constexpr int kAffWaves = PA_DENSE_AFF_WAVES;  // the affine form needs fewer registers: three waves per SIMD
+constexpr int kAffWaves = 12;  // the affine form needs fewer registers: three waves per SIMD
 // CPLX (curl-curl + mass blocks, all affine or all curved): y = (A_r + i A_i) x for two operators on the same space and geometry.  A work unit is half
 // an element block: the 16 element columns of the matrix-core products carry 8 elements x {real, imaginary} part of x; both
 // parts read the element's index words and the D of both operators (one HBM read), the tables in LDS serve both as before,
@@ -606,11 +600,9 @@ __global__ __launch_bounds__(64 * ((AFFINE && !CPLX) ? kAffWaves : kResWaves), 1
   // are done (the q-data registers are free then) so that they fly during the E^T stores; a block starts with its
   // operands in registers instead of two dependent memory round trips.
   constexpr bool PREFETCH_IDX = KPMAX <= 16, PREFETCH_X = KPMAX <= 12;
-  // XEARLY (experiment builds, -DPA_DENSE_XEARLY=1): x of the next block requested BEFORE the matrix products of the current one,
-  // the index words two blocks ahead.  Measured in round 5 on 280k tets (profiles/r05_dense_ab.log): at twelve waves per
-  // workgroup the 24 extra live registers spill (0.190 / 0.286 ms against 0.183 / 0.265), at eight waves it equals the
-  // one-block distance at twelve (0.183 / 0.268): the kernel is not waiting for x.  Default off.
-  constexpr bool XEARLY = PREFETCH_X && AFFINE && !CPLX && (PA_DENSE_XEARLY != 0);
+  // (x of the next block requested BEFORE the products, the index words two blocks ahead, was measured in round 5 on 280k tets,
+  // profiles/r05_dense_ab.log: the 24 extra live registers spill at twelve waves per workgroup and nothing is gained at eight --
+  // the kernel is not waiting for x)
   int sgn[PREFETCH_IDX ? KPMAX : 1];
   double un[PREFETCH_X ? KPMAX : 1];
   // likewise the first chunk of q-data and the curl-orientation words of the next block (values the compiler cannot hold in
@@ -667,13 +659,6 @@ __global__ __launch_bounds__(64 * ((AFFINE && !CPLX) ? kAffWaves : kResWaves), 1
 #pragma unroll
         for (int s = 0; s < KPMAX / 2; s++) con[s] = (a.co2 + ublock(w0) * (KP / 2) * 64)[s * 64u + (unsigned)ulane(w0)];
       }
-      if (XEARLY) {  // index words of the second block of this wave (clamped): its x is requested inside the first iteration
-        const int b1 = b0 + (int)gridDim.x * NW, w1 = b1 < nunits ? b1 : w0;
-        const int32_t *idx1 = a.idx + ublock(w1) * KP * 64;
-        const unsigned l1 = (unsigned)ulane(w1);
-#pragma unroll
-        for (int s = 0; s < KPMAX; s++) sgn[s] = (s < KP) ? idx1[s * 64u + l1] : 0;
-      }
     }
   }
   for (int b = blockIdx.x * NW + wave; b < nunits; b += gridDim.x * NW) {
@@ -691,19 +676,11 @@ __global__ __launch_bounds__(64 * ((AFFINE && !CPLX) ? kAffWaves : kResWaves), 1
         }
         const int sg = PREFETCH_IDX ? sgn[s] : a.idx[bb * KP * 64 + s * 64 + gln];
         const int d = sg >= 0 ? sg : -1 - sg;
-#ifdef PA_ABLATION
-        const double xv = (a.dbg & 1) ? (double)d : ((d & kEssBit) ? 0.0 : (SPLIT ? dense_xbase(a, xsel, xgh, d & ~kEssBit) : xsel)[d & ~kEssBit]);
-#else
         const double xv = (d & kEssBit) ? 0.0 : (SPLIT ? dense_xbase(a, xsel, xgh, d & ~kEssBit) : xsel)[d & ~kEssBit];
-#endif
         u[s] = sg >= 0 ? xv : -xv;
       }
     }
-#ifdef PA_ABLATION
-    const double *q = a.qdata + ((a.dbg & 2) ? (size_t)0 : bb * a.ncq * cs) + lane;
-#else
     const double *q = a.qdata + bb * a.ncq * cs + gln;
-#endif
     [[maybe_unused]] const double *qim = (CPLX && !AFFINE) ? a.qdata_i + bb * a.ncq_i * cs + gln : nullptr;
     double qd[4][6];
     if (AFFINE) {  // qdn[0], qdn[1]: point-0 values of the two fields, kept until the next request
@@ -716,11 +693,7 @@ __global__ __launch_bounds__(64 * ((AFFINE && !CPLX) ? kAffWaves : kResWaves), 1
 #pragma unroll
         for (int k = 0; k < NQ0; k++) qd[gl][k] = qdn[gl][k];
     }
-#ifdef PA_ABLATION
-    const bool co = a.co2 && !(a.dbg & 16);
-#else
     const bool co = a.co2 != nullptr;
-#endif
     // this block's curl-orientation words, two per register, kept for E^T: re-reading them from memory there put twelve
     // load -> wait -> store round trips behind the x gather of the NEXT block (one in-order counter for loads and stores),
     // i.e. the whole latency the software pipeline exists to hide was paid once per block (round 5, found in the ISA;
@@ -759,18 +732,12 @@ __global__ __launch_bounds__(64 * ((AFFINE && !CPLX) ? kAffWaves : kResWaves), 1
 #pragma unroll
         for (int k = 0; k < 6; k++) qdic[f][k] = qdi[f][k];
     }
-    // XEARLY: the x values of the NEXT block are requested here, before the matrix products (they fly during the products instead of
-    // during the short E^T stage; its index words were requested one block earlier still, so the index prefetch below runs two
-    // blocks ahead)
-    if (XEARLY) gather_x(sgn, un);
     if (PREFETCH_IDX) {  // its index words
       // (the lane offset through an opaque copy: hoisted out of the loop as 64-bit per-lane pointers these two addresses were
       // spilled, and their scratch reload put a vmcnt(0) between the index prefetch and the matrix products)
       int ln = ulane(bnc);
       asm volatile("" : "+v"(ln));
-      const int bn2 = bn + (int)gridDim.x * NW;
-      const int bic = XEARLY ? (bn2 < nunits ? bn2 : bnc) : bnc;  // whose index words: two blocks ahead with XEARLY
-      const int32_t *idxn = a.idx + ublock(bic) * KP * 64 + (XEARLY ? ulane(bic) : ln);
+      const int32_t *idxn = a.idx + ublock(bnc) * KP * 64 + ln;
 #pragma unroll
       for (int s = 0; s < KPMAX; s++)
         if (s < KP) sgn[s] = idxn[s * 64];
@@ -781,23 +748,14 @@ __global__ __launch_bounds__(64 * ((AFFINE && !CPLX) ? kAffWaves : kResWaves), 1
       }
     }
 
-#ifdef PA_ABLATION
-    const int nch_eff = (a.dbg & 4) ? 0 : a.nch;
-    if (a.dbg & 4) {
-#pragma unroll
-      for (int pt = 0; pt < PT; pt++)
-        yacc[pt] = double4_t{u[(4 * pt) % KPMAX] + qd[0][0], u[(4 * pt + 1) % KPMAX], u[(4 * pt + 2) % KPMAX], u[(4 * pt + 3) % KPMAX]};
-    }
-#else
-    const int nch_eff = a.nch;
-#endif
     // (the table addresses of this lane re-derived from an opaque copy of the lane id: kept across the E / E^T stages they are
     // what the register allocator spills, and a scratch reload here waits -- one in-order counter -- for the index prefetch)
     int lo_ = lane;
     asm volatile("" : "+v"(lo_));
     const double *Lf = L + (lo_ & 15) * S + (lo_ >> 4);  // forward operand of this lane:   row 16 t + i, column 4 s + kq
     const double *Lb = L + (lo_ >> 4) * S + (lo_ & 15);  // transposed operand of this lane: row 4 pi + kq, column 16 pt + i
-    for (int c = 0; c < nch_eff; c++) {
+    const int nch = a.nch;  // (a copy: with a.nch in the loop condition hipcc emits other code for the PT = 1 affine kernels)
+    for (int c = 0; c < nch; c++) {
       const int r0 = c * NCT * 16;
       if (AFFINE) {
         const double *wc = wl + 16 * c + kq;
@@ -833,17 +791,13 @@ __global__ __launch_bounds__(64 * ((AFFINE && !CPLX) ? kAffWaves : kResWaves), 1
       }
     }
 
-    if (PREFETCH_X) {  // the first q-data chunk of the next block (and its x values, unless they were requested before the products)
-      if (!XEARLY) gather_x(sgn, un);
+    if (PREFETCH_X) {  // the x values and the first q-data chunk of the next block
+      gather_x(sgn, un);
       request_qd(bnc, qdn);
     }
 
     // ---- E^T, first half
-#ifdef PA_ABLATION
-    double *ye = a.ye + ((a.dbg & 8) ? (size_t)(blockIdx.x * NW + wave) : bb) * KP * 64;
-#else
     double *ye = ((CPLX && (j >> 3)) ? a.ye1 : a.ye) + bb * KP * 64;
-#endif
     // position of dof slot s of this lane: base + s * stride (ye_pos; two integers instead of the expression per slot)
     const int ye_stride = a.ye_rows ? 4 : 64;
     double *yel = ye + (a.ye_rows ? (gln & 15) * (4 * KP) + (gln >> 4) : gln);
@@ -1400,10 +1354,6 @@ DenseArgs make_args(const DenseSub &ds) {
   a.affine = ds.d_affine, a.wrel = ds.d_wrel;
   a.x1 = nullptr, a.ye1 = nullptr, a.qdata_i = nullptr, a.ncq_i = 0, a.qi_mass = a.qi_curl = -1;
   a.blist = nullptr, a.nblist = 0;
-  a.dbg = 0;
-#ifdef PA_ABLATION
-  a.dbg = getenv("PA_DBG") ? atoi(getenv("PA_DBG")) : 0;
-#endif
   a.x = nullptr, a.ye = ds.d_ye, a.ye_rows = ds.ye_rows ? 1 : 0;
   a.nsplit = 0x7fffffff, a.xg0 = a.xg1 = nullptr, a.xg_sel = nullptr;
   a.c0 = ds.c0.dev(), a.c1 = ds.c1.dev();

@@ -50,9 +50,6 @@ struct NDArgs {
   CoeffDev c_mass, c_curl;
   NDTab<P1, Q1> tab;
   const int32_t *attr_e;     // metric form: element attributes
-#ifdef PA_ABLATION
-  int dbg;  // timing experiments only: 1 no E-vector store, 4 no q-data/geometry loads, 8 no gather
-#endif
 };
 
 
@@ -102,12 +99,6 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, 2) void nd_hex_apply_kernel(co
       attr[gs * qz] = 0;
 #pragma unroll
       for (int c = 0; c < NG; c++) {
-#ifdef PA_ABLATION
-        if (a.dbg & 4) {
-          gd[gs * qz][c] = 1.0 + 0.01 * c + 1e-3 * lane;
-          continue;
-        }
-#endif
         gd[gs * qz][c] = g[nd_qd_offset(Q1, c, ta + Q1 * tb + Q1 * Q1 * qz)];
       }
     }
@@ -148,11 +139,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, 2) void nd_hex_apply_kernel(co
       const int s = (NRHS > 1) ? sg[r] : a.sidx_in[(size_t)e * PP + m];
       const int d = s >= 0 ? s : -1 - s;
       // essential dofs are flagged in the gather index: read as zero (ParOperator's tx[ess] = 0)
-#ifdef PA_ABLATION
-      const double xv = (a.dbg & 8) ? (double)d : ((d & kEssBit) ? 0.0 : xin[d & ~kEssBit]);
-#else
       const double xv = (d & kEssBit) ? 0.0 : xin[d & ~kEssBit];
-#endif
       sm[DIRECT ? (lp[r] & (kExclBit16 - 1)) : lp[r]] = s >= 0 ? xv : -xv;
     }
   }
@@ -279,12 +266,6 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, 2) void nd_hex_apply_kernel(co
     const int m = t + L::T * r;
     if (active && m < PP) {
       const double v = sm[DIRECT ? (lp[r] & (kExclBit16 - 1)) : lp[r]];
-#ifdef PA_ABLATION
-      if (a.dbg & 1) {
-        asm volatile("" ::"v"(v));
-        continue;
-      }
-#endif
       if (EVEC) {
         if (DIRECT && (lp[r] & kExclBit16)) {  // only copy of this dof: no E-vector round trip, no gather
           const int s = (NRHS > 1) ? sg[r] : a.sidx_in[(size_t)e * PP + m];  // carries kEssBit on essential dofs when masked
@@ -393,9 +374,6 @@ static void launch_pq(const SubOp &so, const double *x, double *y, double *ye, b
   a.ye = ye;
   a.x1 = x1, a.y1 = y1, a.ye1 = ye1;
   fill_tab(so, a.tab);
-#ifdef PA_ABLATION
-  a.dbg = getenv("PA_DBG") ? atoi(getenv("PA_DBG")) : 0;
-#endif
   const int epb = kWavesPerBlock * L::EPW;
   const int nblk = (so.ne + epb - 1) / epb;
   a.xcd_chunk = nblk >= 64 ? (nblk + 7) / 8 : 0;

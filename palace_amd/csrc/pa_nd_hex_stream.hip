@@ -24,38 +24,9 @@
 #include "pa_nd_hex_core.hpp"
 #include "pa_stream_launch.hpp"
 
-#ifndef PA_CPLX_QAHEAD
-#define PA_CPLX_QAHEAD 0  // (with PA_STREAM_QAHEAD: also the packed complex form)
-#endif
-#ifndef PA_STREAM_QAHEAD
-#define PA_STREAM_QAHEAD 0  // 1: the instantiations compiled for two waves per SIMD request the q-data one batch ahead
-#endif
-#ifndef PA_KM_MINW_LOW
-#define PA_KM_MINW_LOW 2  // ... and its p < 3 instantiations (the p-coarsened levels); experiment builds: 3
-#endif
-#ifndef PA_KM_MINW
-#define PA_KM_MINW 2  // waves per SIMD the p = 3 curl-curl + mass instantiation is compiled for (experiment builds: 3)
-#endif
-
 namespace pa {
 
 typedef double d2v __attribute__((ext_vector_type(2)));
-
-// Timeline instrumentation (timing experiments only, -DPA_STREAM_TRACE): wave 0 of the first kTraceWG workgroups stamps
-// s_memtime at the phase boundaries of its first kTraceBatches batches; pa_debug_stream_trace() copies the stamps out.
-#ifdef PA_STREAM_TRACE
-constexpr int kTraceWG = 64, kTraceBatches = 14, kTraceStamps = 12;
-__device__ unsigned long long g_trace[kTraceWG * kTraceBatches * kTraceStamps];
-#define PA_STAMP(k)                                                                                          \
-  do {                                                                                                       \
-    if (tr_on && tr_b < kTraceBatches && lane == 0)                                                          \
-      g_trace[((size_t)blockIdx.x * kTraceBatches + tr_b) * kTraceStamps + (k)] = __builtin_readcyclecounter(); \
-  } while (0)
-#else
-#define PA_STAMP(k) \
-  do {              \
-  } while (0)
-#endif
 
 // Element stride in LDS (doubles).  A wave holds four elements; ds_read_b64 serves lanes 0-31 and 32-63 -- two elements each --
 // in one cycle when they touch 32 different 8-byte banks.  Every contraction layout (swizzled p = 3, padded p < 3) spreads
@@ -65,11 +36,7 @@ __device__ unsigned long long g_trace[kTraceWG * kTraceBatches * kTraceStamps];
 // at p = 3 -- and so ran every second read two- to four-way conflicted: 236 extra LDS cycles per batch on 204
 // (scripts/lds_conflict_model.py restates the kernel's access patterns under the guide's banking rules; SQ_LDS_BANK_CONFLICT
 // in profiles/r03_apply_pmc.json saw them).
-#ifdef PA_STREAM_OLD_LDS  // (A / B builds: the element stride and parity flip of rounds 1-3)
-__host__ __device__ constexpr int stream_lds_elem(const int raw) { return raw; }
-#else
 __host__ __device__ constexpr int stream_lds_elem(const int raw) { return (raw + 15) / 32 * 32 + 16; }
-#endif
 
 template <int P1>
 struct NDStreamArgs {
@@ -137,23 +104,15 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, MINW) void nd_hex_stream_kerne
   // for the whole element instead of per lane) and the D stage's result scaled by the in-plane weight; real forms on packed data
   // column batches (extruded elements): D(ta, tb, qz) = wz(qz) r(ta, tb) read from the compact rows of QData::d_col (same number of
   // loads; 8 bytes per component and lane, fetched as the aligned 16 bytes that hold them) and multiplied by wz(qz) ahead of the D stage
-  constexpr bool AFF = (!CPLX || METRIC) && !GEOMN && !(PA_STREAM_QAHEAD && MINW == 2);
-#ifdef PA_STREAM_EARLY  // experiment builds
-  constexpr bool EARLY_IDX = true;
-#else
+  constexpr bool AFF = (!CPLX || METRIC) && !GEOMN;
   constexpr bool EARLY_IDX = P1 < 3;
-#endif
   // p = 3 curl-curl: the two contraction buffers share their LDS (pa_nd_hex_core.hpp: in-place layout), 2.4 instead of
   // 3.4 KB per element, so that the twelve waves per CU its 168 registers allow are resident instead of ten (measured on the
   // 10M-dof case: 174 -> 167 us per ParOperator::Mult; the kernels with a mass term, two waves per SIMD, gain nothing and the
   // mass kernel loses 2 %, so they keep the separate buffers)
   using L = typename std::conditional<P1 == 3 && !CPLX && USE_C && !USE_U, NDLayoutInPlaceSwz3, NDLayout<P1, Q1>>::type;
   constexpr int NC = P1 + 1, PP = 3 * P1 * NC * NC, NPL = (PP + 15) / 16, NPK = (NPL + 3) / 4;
-#ifdef PA_METRIC6  // experiment build: |detJ| / w of the metric form recomputed as w^2 / det(H) instead of read (6 rows instead of 7)
-  constexpr int NG = METRIC ? 6 : 6 * ((USE_U ? 1 : 0) + (USE_C ? 1 : 0));
-#else
   constexpr int NG = METRIC ? (USE_U ? 7 : 6) : 6 * ((USE_U ? 1 : 0) + (USE_C ? 1 : 0));
-#endif
   static_assert(PP <= 256, "8-bit slots");
   using streamhost::kIdxPattern;
   using streamhost::kIdxStart0;
@@ -232,10 +191,6 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, MINW) void nd_hex_stream_kerne
   for (int r = 0; r < NPL; r++) asm volatile("" : "+v"(xv[r]));
   settle(pA);
 
-  // QAHEAD (kernels compiled for two waves per SIMD: they have the registers): the q-data of a batch is requested right after
-  // the D stage of the batch before it -- its registers are free from there on -- instead of at the top of its own batch, where
-  // only the E stage and the forward passes of the same batch (short at p < 3) stand between the request and the first use
-  constexpr bool QAHEAD = PA_STREAM_QAHEAD && MINW == 2 && (!CPLX || (PA_CPLX_QAHEAD && !METRIC));
   d2v gq[GEOMN ? 1 : 2 * NG];
   double xl[GEOMN ? 6 : 1];  // GEOMN: this lane's six of the element's 81 node coordinates, in flight during the forward passes
   auto load_xn = [&](const int ee, const int t) {
@@ -276,17 +231,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, MINW) void nd_hex_stream_kerne
     // (read once: non-temporal, so the stream does not displace x / y lines in L2; measured 5 - 7 % on the apply)
     for (int k = 0; k < (GEOMN ? 1 : 2 * NG); k++) gq[k] = __builtin_nontemporal_load(&g[16 * k]);
   };
-  if (QAHEAD) {
-    load_q(CPLX ? b * 2 + (lane >> 5) : b * 4 + (lane >> 4), lane & 15, 0);
-#pragma unroll
-    for (int k = 0; k < 2 * NG; k++) asm volatile("" : "+v"(gq[k]));
-  }
-#ifdef PA_STREAM_TRACE
-  const bool tr_on = blockIdx.x < kTraceWG && wave == 0;
-  int tr_b = 0;
-#endif
   for (;;) {
-    PA_STAMP(0);
     // lane constants are re-derived from an opaque copy of the lane id in every iteration: hoisted out of the loop, the
     // few dozen LDS addresses and predicates of the passes stay live across it and end up in scratch memory
     // (the lane id itself is recomputed, not copied: one register less live across the batch -- the p = 3 curl-curl kernels sit at
@@ -299,17 +244,13 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, MINW) void nd_hex_stream_kerne
     int *stab = side + 2 * LDS_SIDE;                        // run starts of the next batch (decode)
     // (no parity flip of the swizzled layouts here: the element stride itself puts the two elements of a 32-lane read group
     // on opposite halves of the banks, stream_lds_elem)
-#ifdef PA_STREAM_OLD_LDS
-    const int lx = L::parity_xor(sub);
-#else
     constexpr int lx = 0;
-#endif
     const int e = CPLX ? b * 2 + (sub >> 1) : b * 4 + sub;
 
     // q-data of this batch: consumed after the forward contraction
     const int kind = AFF ? __builtin_amdgcn_readfirstlane((int)(pA[NPK] >> 30)) : 0;  // (the same for the 64 lanes: build_stream)
     const int aff = kind >> 1, col = kind & 1;
-    if (!QAHEAD) load_q(e, t, kind);
+    load_q(e, t, kind);
     d2v ce = {0.0, 0.0}, ci = {0.0, 0.0};
     if (METRIC || GEOMN) ce = reinterpret_cast<const d2v *>(a.coef)[e];
     if (CPLX && METRIC) ci = reinterpret_cast<const d2v *>(a.coef1)[e];
@@ -326,7 +267,6 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, MINW) void nd_hex_stream_kerne
     }
 #pragma unroll
     for (int k = 0; k <= NPK; k++) side[2 * ((PP + 1) / 2) + 16 * k + t] = (int)pA[k];
-    PA_STAMP(1);  // x arrived, staged
     wave_sync();
     double uin[3][NC];
 #pragma unroll
@@ -349,7 +289,6 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, MINW) void nd_hex_stream_kerne
       load_idx(bn, sub, t, sB, pB);
       __builtin_amdgcn_sched_barrier(0);
     }
-    PA_STAMP(2);  // q-data requested
     double U[3][Q1], CU[3][Q1];
 #pragma unroll
     for (int c = 0; c < 3; c++)
@@ -359,8 +298,6 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, MINW) void nd_hex_stream_kerne
     nd_fwd_comp<1, P1, Q1, USE_U, USE_C, L>(a, e, true, true, ta, tb, lx, sm, uin[1], U, CU);
     nd_fwd_comp<2, P1, Q1, USE_U, USE_C, L>(a, e, true, true, ta, tb, lx, sm, uin[2], U, CU);
 
-    PA_STAMP(3);  // forward done
-    PA_STAMP(4);
     // index words of the next batch, if not requested at the top
     if (!EARLY_IDX) {
       __builtin_amdgcn_sched_barrier(0);
@@ -500,16 +437,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, MINW) void nd_hex_stream_kerne
           cmass = 1.0, ccurl = 1.0;
         }
         if (USE_U) {
-#ifdef PA_METRIC6
-          // |detJ| / w = w^2 / det(H)  (det(H) = w^3 / |detJ|); affine rows are H / wab: the factor becomes wz^2 and the common
-          // scaling by wab below completes it
-          const double c00 = H[3] * H[5] - H[4] * H[4], c01 = H[2] * H[4] - H[1] * H[5], c02 = H[1] * H[4] - H[2] * H[3];
-          const double det = H[0] * c00 + H[1] * c01 + H[2] * c02;
-          const double wq_ = (aff ? 1.0 : wxy) * ((qz == 0 || qz == 3) ? a.wq2[0] : a.wq2[1]);
-          const double cm = cmass * wq_ * wq_ / det;
-#else
           const double cm = H[6] * cmass;
-#endif
           const double m[6] = {cm * (H[3] * H[5] - H[4] * H[4]), cm * (H[2] * H[4] - H[1] * H[5]), cm * (H[1] * H[4] - H[2] * H[3]),
                                cm * (H[0] * H[5] - H[2] * H[2]), cm * (H[1] * H[2] - H[0] * H[4]), cm * (H[0] * H[3] - H[1] * H[1])};
           sym_mv(m, U[0][qz], U[1][qz], U[2][qz], U[0][qz], U[1][qz], U[2][qz]);
@@ -563,24 +491,16 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, MINW) void nd_hex_stream_kerne
     }
 
     if (GEOMN == 2) wave_sync();  // (the parked sums have been read: the contraction buffers are the transposed passes' again)
-    PA_STAMP(5);  // D done
 
-    if (QAHEAD) {  // q-data of the next batch (the last one re-reads its own)
-      __builtin_amdgcn_sched_barrier(0);
-      load_q(CPLX ? bn * 2 + (sub >> 1) : bn * 4 + sub, t, 0);
-      __builtin_amdgcn_sched_barrier(0);
-    }
     // x of the next batch: in flight during the transposed passes
     double xB[NPL];
     nd_bwd_comp<0, P1, Q1, USE_U, USE_C, L>(a, e, true, true, ta, tb, lx, sm, uin[0], U, CU);
-    PA_STAMP(6);  // first transposed component done
     if (GPOS == 1) {
       __builtin_amdgcn_sched_barrier(0);
       gather(sB, pB, xB, stab, t);
       settle(pB);
       __builtin_amdgcn_sched_barrier(0);
     }
-    PA_STAMP(7);  // (GPOS 1) index words landed, x requested
     nd_bwd_comp<1, P1, Q1, USE_U, USE_C, L>(a, e, true, true, ta, tb, lx, sm, uin[1], U, CU);
     if (GPOS == 2) {
       __builtin_amdgcn_sched_barrier(0);
@@ -590,7 +510,6 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, MINW) void nd_hex_stream_kerne
     }
     nd_bwd_comp<2, P1, Q1, USE_U, USE_C, L>(a, e, true, true, ta, tb, lx, sm, uin[2], U, CU);
 
-    PA_STAMP(8);  // transposed passes done
     // E^T: back to tensor order in LDS, out in sorted order, signed; exclusive dofs straight to y
 #pragma unroll
     for (int C = 0; C < 3; C++) {
@@ -618,10 +537,6 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, MINW) void nd_hex_stream_kerne
       *dst = (fl & 1u) ? -v : v;
     }
     wave_sync();  // the LDS strip is reused by the next batch
-    PA_STAMP(9);  // stores issued
-#ifdef PA_STREAM_TRACE
-    tr_b++;
-#endif
     if (!more) break;
     b = bn;
 #pragma unroll
@@ -945,20 +860,17 @@ static uint32_t *upload_flags(const SubOp &so, const std::vector<uint32_t> &pp) 
 }
 
 // the run form of E^T over `rows` (increasing), essential rows flagged in their headers
-static void upload_runs(StreamTables &t, const SubOp &so, const std::vector<int32_t> &rows, const char *ess, const char *skip) {
+static void upload_runs(StreamTables &t, const SubOp &so, const std::vector<int32_t> &rows, const char *ess) {
   std::vector<uint32_t> code;
   std::vector<RunHdr> hdr;
   std::vector<int32_t> rpos;
-  streamhost::build_runs(so.ne, so.P, so.lsize, so.h_sidx.data(), rows, code, hdr, rpos, ess, skip);  // (runs: all essential or none)
+  streamhost::build_runs(so.ne, so.P, so.lsize, so.h_sidx.data(), rows, code, hdr, rpos, ess);  // (runs: all essential or none)
   const std::vector<RunChunk> ch = streamhost::run_chunks(code);
   t.d_rchunk = dev_upload(reinterpret_cast<const uint32_t *>(ch.data()), 4 * ch.size());
   t.d_rhdr = dev_upload(reinterpret_cast<const int32_t *>(hdr.data()), 2 * hdr.size());
   t.d_rpos = dev_upload(rpos.data(), rpos.size());
   t.n_rows = (int)rows.size(), t.n_runs = (int)hdr.size() - 1;
 }
-
-// (pricing experiment: copies taken off the E-vector are not copies)
-static const char *price_skip(const SubOp &so) { return so.h_price_skip.empty() ? nullptr : so.h_price_skip.data(); }
 
 // Index arrays of the streaming kernel and the run form of the transpose map (after finalize_exclusive: needs the
 // exclusive flags).  Host work proportional to the index array, once per operator.  Every per-element array is padded
@@ -975,42 +887,6 @@ void build_stream(SubOp &so) {
   } else if (!streamhost::pack_index(ne, P, so.lsize, so.h_sidx.data(), so.h_perm.data(), ic, pp,
                                      so.fe_type == PA_FE_H1 ? streamhost::kIdxStart0H1 : streamhost::kIdxStart0))
     return;
-  // PRICING EXPERIMENT (wrong results, right bytes; never set in product runs): PALACE_AMD_PRICE_BLOCK=G with G = 4 (the elements of
-  // one wave) or 8 (of one workgroup) prices an E-vector in which the copies of a dof inside a group of G consecutive elements
-  // are assembled on chip before the store: every copy but the group's first is taken off the E-vector (its store goes
-  // straight to y instead, like an exclusive dof's) and out of the run lists; a dof whose copies all sit in one group leaves
-  // the gather altogether.  What is NOT priced: the LDS traffic and barrier of the on-chip assembly itself.
-#ifdef PA_ABLATION  // (the ablation library only, `make ablate`: the product library has no such switch)
-  const int price_group = (lane16_curl && getenv("PALACE_AMD_PRICE_BLOCK")) ? atoi(getenv("PALACE_AMD_PRICE_BLOCK")) : 0;
-#else
-  constexpr int price_group = 0;
-#endif
-  if (price_group > 1) {
-    const size_t nnz = (size_t)ne * P;
-    so.h_price_skip.assign(nnz, 0);
-    std::vector<int32_t> seen((size_t)so.lsize, -1), cnt((size_t)so.lsize, 0), cnt2((size_t)so.lsize, 0);
-    for (size_t k = 0; k < nnz; k++) {
-      const int d = streamhost::dof_of(so.h_sidx[k]), g = (int)(k / P) / price_group;
-      cnt[d]++;
-      if (seen[d] == g) so.h_price_skip[k] = 1; else seen[d] = g, cnt2[d]++;
-    }
-    size_t dropped = 0, freed = 0;
-    for (size_t k = 0; k < nnz; k++) {
-      const int d = streamhost::dof_of(so.h_sidx[k]);
-      const bool direct = so.h_price_skip[k] || (cnt2[d] == 1 && cnt[d] > 1);
-      if (!direct) continue;
-      const int m = (int)(k % P);
-      pp[fl.word(k / P, m)] |= fl.only_copy(m);
-      dropped += so.h_price_skip[k] ? 1 : 0, freed += so.h_price_skip[k] ? 0 : 1;
-    }
-    std::vector<int32_t> shared2;
-    for (int d = 0; d < so.lsize; d++)
-      if (cnt2[d] > 1) shared2.push_back(d);
-    fprintf(stderr, "PALACE_AMD_PRICE_BLOCK=%d: %zu of %zu E-vector entries dropped, %zu more leave the gather; shared dofs %zu -> %zu\n",
-            price_group, dropped, nnz, freed, so.h_shared.size(), shared2.size());
-    so.h_shared = shared2;
-    so.n_shared = (int)shared2.size();
-  }
   if (lane16_curl) {
     // batches of four affine elements: kAffBit in the flag words of their 4 x 16 (element, lane) pairs -- the flag arrives with the
     // index words, one batch ahead of the q-data request it steers
@@ -1044,7 +920,7 @@ void build_stream(SubOp &so) {
   if (so.qd->metric || (so.iso && so.qf == PA_QF_HDIV_33 && so.geom->d_xnodes)) stream_element_coefficients(so);
   StreamTables &t = so.stream[kStreamPlain];
   t.d_flags = upload_flags(so, pp);
-  upload_runs(t, so, so.h_shared, nullptr, price_skip(so));
+  upload_runs(t, so, so.h_shared, nullptr);
 }
 
 // Essential dofs (pa_op_set_essential): flagged (read as zero) and never exclusive in the masked form's copy of
@@ -1060,8 +936,7 @@ void stream_set_essential(SubOp &so, const std::vector<char> &flag) {
   StreamTables &t = so.stream[kStreamMasked];
   t.release();
   t.d_flags = upload_flags(so, pb);
-  upload_runs(t, so, streamhost::gather_rows(so.ne, so.P, so.lsize, so.h_sidx.data(), flag.data(), price_skip(so), false), flag.data(),
-              price_skip(so));
+  upload_runs(t, so, streamhost::gather_rows(so.ne, so.P, so.lsize, so.h_sidx.data(), flag.data(), false), flag.data());
 }
 
 void free_stream(SubOp &so) {
@@ -1099,13 +974,8 @@ static void launch_gpos(const SubOp &so, NDStreamArgs<P1> &a, hipStream_t s) {
 // for the kernels with a mass term (their index words are requested just before D and need time to arrive and to be
 // decoded; later = fewer live registers: 202 instead of 248 VGPRs for K + M at p = 3; measured on the 10M-dof case with the
 // run-compressed index: curl-curl 0.180 / 0.181 ms, K + M 0.187 / 0.185 ms, mass 0.168 / 0.156 ms for positions 1 / 2).
-template <int P1, bool U, bool C, bool METRIC, int MINW_>
+template <int P1, bool U, bool C, bool METRIC, int MINW>
 static void launch_variant(const SubOp &so, NDStreamArgs<P1> &a, hipStream_t s) {
-#ifdef PA_STREAM_MINW2  // experiment builds: two waves per SIMD everywhere
-  constexpr int MINW = 2;
-#else
-  constexpr int MINW = MINW_;
-#endif
   constexpr int GPOS = U ? 2 : 1;
   if (a.nsplit >= 0)  // split vectors (one more instantiation per operator kind)
     return launch_gpos<P1, U, C, METRIC, MINW, GPOS, false, true>(so, a, s);
@@ -1123,9 +993,6 @@ static void launch_p(const SubOp &so, const double *x, double *y, StreamForm for
   a.qdata = so.qd->d;
   a.qaff = so.qd->d_aff, a.qcol = so.qd->d_col, a.wq2[0] = so.qd->wq2[0], a.wq2[1] = so.qd->wq2[1];
   if (so.qd->d_col) a.wqi2[0] = 1.0 / so.qd->wq2[0], a.wqi2[1] = 1.0 / so.qd->wq2[1];
-#ifdef PA_METRIC6
-  if (so.geom->w1.size() == 4) a.wq2[0] = so.geom->w1[0], a.wq2[1] = so.geom->w1[1];
-#endif
   a.coef = so.d_coef_s;
   a.xn = nullptr, a.gtab = nullptr;
   a.x = x, a.y = y, a.ye = so.d_ye;
@@ -1155,7 +1022,8 @@ static void launch_p(const SubOp &so, const double *x, double *y, StreamForm for
       break;
     case PA_QF_HDIVMASS_33:
       // (packed D of both terms, anisotropic materials: twelve doubles per point, 96 registers of q-data per lane; round 5)
-      if (m) launch_variant<P1, true, true, true, (P1 == 3 ? PA_KM_MINW : PA_KM_MINW_LOW)>(so, a, s);
+      // (metric form: compiled for two waves per SIMD at p = 3 and at the p-coarsened levels alike; three were measured)
+      if (m) launch_variant<P1, true, true, true, 2>(so, a, s);
       else launch_variant<P1, true, true, false, 2>(so, a, s);
       break;
     default: throw Error("QFunction not available for H(curl) hexahedra");
@@ -1288,14 +1156,14 @@ bool stream_build_all(SubOp &so) {
   if (!so.stream[kStreamPlain].ready() || (so.fe_type != PA_FE_H1 && so.fe_type != PA_FE_HCURL) || so.h_perm_s.empty()) return false;
   std::vector<char> flag(so.h_ess_flag);
   flag.resize((size_t)so.lsize, 0);
-  const std::vector<int32_t> all = streamhost::gather_rows(so.ne, so.P, so.lsize, so.h_sidx.data(), flag.data(), nullptr, true);
+  const std::vector<int32_t> all = streamhost::gather_rows(so.ne, so.P, so.lsize, so.h_sidx.data(), flag.data(), true);
   if ((int)all.size() != so.lsize) return false;  // (a dof no element holds: the plain forms leave it alone, the step must not)
   const streamhost::FlagLayout fl = flag_layout(so);
   std::vector<uint32_t> fw(so.h_perm_s);
   streamhost::clear_only_copy(fl, fw);
   streamhost::mark_essential(fl, fw, so.ne, so.h_sidx.data(), flag.data(), false);
   t.d_flags = upload_flags(so, fw);
-  upload_runs(t, so, all, flag.data(), nullptr);
+  upload_runs(t, so, all, flag.data());
   return true;
 }
 
@@ -1308,14 +1176,4 @@ void launch_et_run_gather_step(const SubOp &so, StreamForm form, const double *x
   launch_run_gather<true>(so, form, so.d_ye, nullptr, false, x, ess_policy, split, step, GatherPart2{}, s);
 }
 
-#ifdef PA_STREAM_TRACE
-}  // namespace pa
-extern "C" int pa_debug_stream_trace(unsigned long long *out, int n) {
-  const int total = pa::kTraceWG * pa::kTraceBatches * pa::kTraceStamps;
-  if (n < total) return -total;
-  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(pa::g_trace), sizeof(unsigned long long) * total) != hipSuccess) return -1;
-  return total;
-}
-namespace pa {
-#endif
 }  // namespace pa

@@ -385,7 +385,6 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, 2) void nd_hex_stream5_kernel(
   }
 }
 
-#ifndef PA_S5_ONLY  // (register-usage experiments instantiate single kernels without the dispatch below)
 // ---- host side ----------------------------------------------------------------------------------------------------------
 bool nd_hex_stream5_ok(const SubOp &so) {
   // (read at every operator creation, not cached: tests build both forms in one process)
@@ -498,6 +497,5 @@ void launch_nd_hex_stream5_complex(const SubOp &sr, const SubOp &si, const doubl
     default: throw Error("no five-point streaming H(curl) hex kernel for this order");
   }
 }
-#endif  // PA_S5_ONLY
 
 }  // namespace pa

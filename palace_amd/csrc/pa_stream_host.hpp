@@ -238,13 +238,11 @@ inline std::vector<uint32_t> split_flag_rows(const FlagLayout &row, const std::v
 }
 
 // The dofs the run gather of a form owns, increasing: those that do not have exactly one copy, and the essential ones (ess,
-// optional: the gather writes their rows); all: every dof some element holds (the `all` form).  skip (optional): entries that
-// are not copies, as in build_runs.
-inline std::vector<int32_t> gather_rows(int ne, int P, int lsize, const int32_t *sidx, const char *ess, const char *skip, bool all) {
+// optional: the gather writes their rows); all: every dof some element holds (the `all` form).
+inline std::vector<int32_t> gather_rows(int ne, int P, int lsize, const int32_t *sidx, const char *ess, bool all) {
   const size_t nnz = (size_t)ne * P;
   std::vector<int32_t> count((size_t)lsize, 0), rows;
-  for (size_t k = 0; k < nnz; k++)
-    if (!skip || !skip[k]) count[dof_of(sidx[k])]++;
+  for (size_t k = 0; k < nnz; k++) count[dof_of(sidx[k])]++;
   for (int d = 0; d < lsize; d++)
     if ((all ? count[d] > 0 : count[d] != 1) || (ess && ess[d])) rows.push_back(d);
   return rows;
@@ -259,17 +257,14 @@ inline std::vector<int32_t> gather_rows(int ne, int P, int lsize, const int32_t 
 //   lanes per run)
 inline void build_runs(int ne, int P, int lsize, const int32_t *sidx, const std::vector<int32_t> &shared,
                        std::vector<uint32_t> &code, std::vector<RunHdr> &hdr, std::vector<int32_t> &rpos,
-                       const char *ess = nullptr, const char *skip = nullptr) {
-  // (skip: entries that are not copies -- the pricing experiment of PALACE_AMD_PRICE_BLOCK, pa_nd_hex_stream.hip: build_stream)
+                       const char *ess = nullptr) {
   if (lsize > (int)kRunDofMask) throw std::runtime_error("too many local dofs for the run headers");
   const size_t nnz = (size_t)ne * P;
   std::vector<int32_t> tptr((size_t)lsize + 1, 0);
-  for (size_t k = 0; k < nnz; k++)
-    if (!skip || !skip[k]) tptr[(size_t)dof_of(sidx[k]) + 1]++;
+  for (size_t k = 0; k < nnz; k++) tptr[(size_t)dof_of(sidx[k]) + 1]++;
   for (int d = 0; d < lsize; d++) tptr[d + 1] += tptr[d];
   std::vector<int32_t> tpos(nnz), fill(tptr.begin(), tptr.end() - 1);
-  for (size_t k = 0; k < nnz; k++)
-    if (!skip || !skip[k]) tpos[fill[dof_of(sidx[k])]++] = (int32_t)k;
+  for (size_t k = 0; k < nnz; k++) tpos[fill[dof_of(sidx[k])]++] = (int32_t)k;
   code.clear(), hdr.clear(), rpos.clear();
   code.reserve(shared.size());
   int prev = -2, len = 0;

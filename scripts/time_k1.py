@@ -13,4 +13,4 @@ e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=Tr
 torch.cuda.synchronize(); e0.record()
 for _ in range(20): op.mult(x, y)
 e1.record(); torch.cuda.synchronize()
-print(f"PA_DBG={os.environ.get('PA_DBG','0'):>3} curl mult (K1+K2) {e0.elapsed_time(e1)/20:.4f} ms")
+print(f"curl mult (K1+K2) {e0.elapsed_time(e1)/20:.4f} ms")

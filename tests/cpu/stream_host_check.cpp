@@ -242,7 +242,7 @@ static int run_forms(const char *what, const Map &mp, const FlagLayout &fl, bool
   std::vector<int32_t> rows_def;
   for (int d = 0; d < mp.lsize; d++)
     if (mp.count[d] != 1 || mp.ess[d]) rows_def.push_back(d);
-  if (gather_rows(mp.ne, mp.P, mp.lsize, mp.sidx.data(), mp.ess.data(), nullptr, false) != rows_def)
+  if (gather_rows(mp.ne, mp.P, mp.lsize, mp.sidx.data(), mp.ess.data(), false) != rows_def)
     return std::printf("%s: gather_rows (masked) differs from its definition\n", what), 1;
   if (split) {  // the same edit made on the split rows themselves
     std::vector<uint32_t> fw = split_flag_rows(fl, pp);
@@ -263,7 +263,7 @@ static int run_forms(const char *what, const Map &mp, const FlagLayout &fl, bool
   std::vector<uint32_t> pa(pp);
   clear_only_copy(fl, pa);
   mark_essential(fl, pa, mp.ne, mp.sidx.data(), mp.ess.data(), false);
-  const std::vector<int32_t> rows_all = gather_rows(mp.ne, mp.P, mp.lsize, mp.sidx.data(), mp.ess.data(), nullptr, true);
+  const std::vector<int32_t> rows_all = gather_rows(mp.ne, mp.P, mp.lsize, mp.sidx.data(), mp.ess.data(), true);
   for (int d = 0; d < mp.lsize; d++)  // (stream_build_all refuses otherwise: the case's parameters are chosen so that this holds)
     if (mp.count[d] == 0) return std::printf("%s: dof %d is held by no element, the all form needs every dof held\n", what, d), 1;
   if ((int)rows_all.size() != mp.lsize) return std::printf("%s: the all form owns %zu of %d dofs\n", what, rows_all.size(), mp.lsize), 1;
