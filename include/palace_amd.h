@@ -260,6 +260,10 @@ const char *pa_last_error(void);
 const char *pa_version(void);
 /* Number of visible HIP devices (0 => none; every compute entry point then fails loudly). */
 int pa_device_count(void);
+/* Device arrays the library's objects own at this moment, process-wide: up by one with every allocation, down by one with every
+ * release.  Destroying everything that was created brings it back to where it stood (ownership tests: free-memory readings of a
+ * shared card belong to everybody). */
+int64_t pa_device_buffers_live(void);
 
 /* --- geometry factors: replaces AssembleCeedGeometryData + f_build_geom_factor_33
  *     (fem/libceed/integrator.cpp:335-421, fem/qfunctions/33/geom_33_qf.h:9-33).

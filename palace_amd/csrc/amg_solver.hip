@@ -20,10 +20,7 @@ DeviceCsr::DeviceCsr(const Context &ctx, const amg::HostCsr &h, bool symmetric) 
   m_.d_val = pa::dev_upload(h.val.data(), h.val.size(), ctx.stream);
   op_ = std::make_unique<CsrOperator>(ctx, &m_);
 }
-DeviceCsr::~DeviceCsr() {
-  op_.reset();
-  (void)hipFree(m_.d_rowptr), (void)hipFree(m_.d_col), (void)hipFree(m_.d_val);
-}
+DeviceCsr::~DeviceCsr() = default;
 
 amg::HostCsr DownloadCsr(const pa_csr &m, const int32_t *ess, int n_ess) {
   amg::HostCsr h;

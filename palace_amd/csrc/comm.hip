@@ -107,7 +107,7 @@ Comm::Comm(int rank, LocalGroup &group) : rank_(rank), size_(group.Size()), loca
 
 Comm::~Comm() {
   if (nccl_) rccl().CommDestroy(nccl_);
-  if (d_one_) (void)hipFree(d_one_);
+  d_one_.reset();
   for (size_t r = 0; r < remote_.size(); r++)
     if (remote_ipc_[r]) (void)hipIpcCloseMemHandle(remote_[r]);
   if (d_remote_) (void)hipFree(d_remote_);
@@ -121,11 +121,10 @@ std::vector<double> Comm::SetupGather(double mine, hipStream_t s) {
   std::vector<double> v((size_t)size_, 0.0);
   v[(size_t)rank_] = mine;
   if (size_ == 1) return v;
-  double *d = pa::dev_upload(v.data(), v.size(), s);
+  const pa::DevBuf<double> d = pa::dev_upload(v.data(), v.size(), s);
   PeerAllReduce(d, size_, s, 1);  // (every rank contributes zeros outside its own entry: the sum is the gather)
   PA_HIP(hipMemcpyAsync(v.data(), d, sizeof(double) * v.size(), hipMemcpyDeviceToHost, s));
   PA_HIP(hipStreamSynchronize(s));
-  (void)hipFree(d);
   PeerCheckNow();
   return v;
 }
@@ -215,8 +214,7 @@ void LocalGroup::Abort() {
 }
 
 Halo::~Halo() {
-  (void)hipFree(d_send_idx_), (void)hipFree(d_recv_idx_), (void)hipFree(d_sendbuf_), (void)hipFree(d_recvbuf_);
-  if (d_ghost_out_) (void)hipFree(d_ghost_out_);
+  d_send_idx_.reset(), d_recv_idx_.reset(), d_sendbuf_.reset(), d_recvbuf_.reset(), d_ghost_out_.reset();  // (before the peer block, as ever)
   FreePeer();
 }
 
@@ -846,7 +844,7 @@ Comm::Comm(int rank, int size) : rank_(rank), size_(size) {
   AllocArena();
   if (size == 1) {
     remote_.assign(1, arena_), remote_ipc_.assign(1, 0);
-    d_remote_ = pa::dev_upload(remote_.data(), 1);
+    d_remote_ = pa::dev_upload(remote_.data(), 1).release();
   }
 }
 
@@ -882,7 +880,7 @@ void Comm::PeerConnect(const char *handles) {
     remote_[r] = static_cast<char *>(p), remote_ipc_[r] = 1;
   }
   if (d_remote_) (void)hipFree(d_remote_);
-  d_remote_ = pa::dev_upload(remote_.data(), remote_.size());
+  d_remote_ = pa::dev_upload(remote_.data(), remote_.size()).release();
 }
 
 void Comm::PeerDisconnect() {
@@ -1027,7 +1025,7 @@ void Halo::PeerSetup(const int32_t *send_idx) {
   try {  // (a throwing constructor runs no destructor: the slot and the blocks go back here)
   pp->nnbr = nn;
   pp->local = reinterpret_cast<PeerLocal *>(c.arena_ + d.off_local);
-  pp->counters = pa::dev_alloc<PeerCounters>(1);
+  pp->counters = pa::dev_alloc<PeerCounters>(1).release();
   PA_HIP(hipMemset(pp->counters, 0, sizeof(PeerCounters)));
   pp->mb[0] = reinterpret_cast<double *>(c.arena_ + d.off_mb[0]);
   pp->mb[1] = reinterpret_cast<double *>(c.arena_ + d.off_mb[1]);
@@ -1056,7 +1054,7 @@ void Halo::PeerSetup(const int32_t *send_idx) {
     q.off[0] = send_off_[k], q.n[0] = ns, q.rn[0] = nr;
     q.off[1] = recv_off_[k], q.n[1] = nr, q.rn[1] = ns;
   }
-  pp->d_nbr = pa::dev_upload(nb.data(), nb.size());
+  pp->d_nbr = pa::dev_upload(nb.data(), nb.size()).release();
   // P^T: the owned dofs with sharers and the positions of their contributions in the mailbox, neighbour-major
   {
     std::vector<int32_t> order((size_t)nsend_);
@@ -1078,9 +1076,9 @@ void Halo::PeerSetup(const int32_t *send_idx) {
       const int b = rptr[i], e = rptr[i + 1];
       rinfo[i] = make_int4(rdof[i], rpos[b], e - b > 1 ? rpos[b + 1] : -1, e - b > 2 ? b + 2 : -1);
     }
-    pp->d_rinfo = pa::dev_upload(rinfo.data(), rinfo.size());
-    pp->d_rptr = pa::dev_upload(rptr.data(), rptr.size());
-    pp->d_rpos = pa::dev_upload(rpos.data(), rpos.size());
+    pp->d_rinfo = pa::dev_upload(rinfo.data(), rinfo.size()).release();
+    pp->d_rptr = pa::dev_upload(rptr.data(), rptr.size()).release();
+    pp->d_rpos = pa::dev_upload(rpos.data(), rpos.size()).release();
   }
   } catch (...) {
     FreePeer();
@@ -1254,9 +1252,12 @@ long long Comm::StressRing(const Halo &ring, int n, int rounds, bool direct, boo
   PA_REQUIRE(size_ > 1 && PeerReady() && ring.UsesPeerTransport(), "stress test: needs the connected peer transport");
   PA_REQUIRE(!direct || ring.DirectOk(n, 2 * n), "stress test: the plan has no direct form");
   const int left = (rank_ + size_ - 1) % size_, right = (rank_ + 1) % size_, nred = 5, nb = (n + 255) / 256;
-  double *lx = pa::dev_alloc<double>((size_t)2 * n), *red = pa::dev_alloc<double>(8);
-  unsigned long long *st = pa::dev_alloc<unsigned long long>(2);  // {round, failures}
-  uint8_t *mask = pa::dev_alloc<uint8_t>((size_t)n);
+  const pa::DevBuf<double> b_lx = pa::dev_alloc<double>((size_t)2 * n), b_red = pa::dev_alloc<double>(8);
+  const pa::DevBuf<unsigned long long> b_st = pa::dev_alloc<unsigned long long>(2);  // {round, failures}
+  const pa::DevBuf<uint8_t> b_mask = pa::dev_alloc<uint8_t>((size_t)n);
+  double *const lx = b_lx, *const red = b_red;
+  unsigned long long *const st = b_st;
+  uint8_t *const mask = b_mask;
   PA_HIP(hipMemsetAsync(st, 0, 2 * sizeof(unsigned long long), s));
   PA_HIP(hipMemsetAsync(mask, 0, (size_t)n, s));
   auto round = [&] {
@@ -1303,7 +1304,6 @@ long long Comm::StressRing(const Halo &ring, int n, int rounds, bool direct, boo
   PA_HIP(hipStreamSynchronize(s));
   if (ge) (void)hipGraphExecDestroy(ge);
   if (g) (void)hipGraphDestroy(g);
-  (void)hipFree(lx), (void)hipFree(red), (void)hipFree(st), (void)hipFree(mask);
   PeerCheckNow();
   PA_REQUIRE((int)h[0] == rounds, "stress test: round counter out of step");
   return (long long)h[1];

@@ -27,6 +27,8 @@
 #include <condition_variable>
 #include <mutex>
 
+#include "pa_devbuf.hpp"
+
 namespace palace {
 
 // In-process stand-in for the RCCL communicator: `size` ranks are THREADS of one process on one GPU, each with its own Context and
@@ -80,7 +82,7 @@ class Comm {
   unsigned long long *h_err_ = nullptr;  // error word of the wait loops: page-locked host memory the kernels write on a
                                          // time-out, so that every host synchronisation point can look at it for free
   char **d_remote_ = nullptr;          // device copy of remote_
-  double *d_one_ = nullptr;            // Barrier's operand (per communicator)
+  pa::DevBuf<double> d_one_;           // Barrier's operand (per communicator)
   hipStream_t setup_stream_ = nullptr; // the transport's own stream for set-up barriers (never the shared null stream:
                                        // the rank threads of an in-process group would queue behind each other's waits)
   void AllocArena();
@@ -160,9 +162,9 @@ class Halo {
   Comm *comm_;
   std::vector<int> nbr_;                  // neighbour ranks
   std::vector<int> send_off_, recv_off_;  // [nnbr + 1] offsets into the index lists / buffers
-  int32_t *d_send_idx_ = nullptr;  // owned dofs this rank sends in P (and receives-into in P^T)
-  int32_t *d_recv_idx_ = nullptr;  // ghost slots this rank receives in P (and sends in P^T)
-  double *d_sendbuf_ = nullptr, *d_recvbuf_ = nullptr;
+  pa::DevBuf<int32_t> d_send_idx_;  // owned dofs this rank sends in P (and receives-into in P^T)
+  pa::DevBuf<int32_t> d_recv_idx_;  // ghost slots this rank receives in P (and sends in P^T)
+  pa::DevBuf<double> d_sendbuf_, d_recvbuf_;
   int recv_first_ = -1;  // >= 0: the ghosts are the contiguous range [recv_first_, recv_first_ + nrecv_) of the local vector in
                          // receive order (ghosts last: the usual numbering) -- received into / sent from it in place
   int nsend_ = 0, nrecv_ = 0;
@@ -178,7 +180,7 @@ class Halo {
   void PeerExchange(int dir, double *d_v, hipStream_t s) const;
 
   std::vector<int32_t> shared_owned_;  // peer transport: the owned dofs that have sharers (sorted)
-  mutable double *d_ghost_out_ = nullptr;  // direct form: the ghost rows of the local apply
+  mutable pa::DevBuf<double> d_ghost_out_;  // direct form: the ghost rows of the local apply
 
 public:
   bool UsesPeerTransport() const { return peer_ != nullptr; }

@@ -521,17 +521,15 @@ void ComplexParOperator::UpdateFused() {
   if (n_ess_ && kind != 1 && !(RAPi_ && RAPi_->FusesEssential())) return;
   fused_r_ = cr, fused_i_ = ci;
 }
-ComplexParOperator::~ComplexParOperator() {
-  if (d_ess_) (void)hipFree(d_ess_);
-}
+ComplexParOperator::~ComplexParOperator() = default;
 
 void ComplexParOperator::SetEssentialTrueDofs(const int32_t *ess_host, int n_ess, ParOperator::DiagonalPolicy policy) {
   StreamGraph::Invalidate();
   PA_REQUIRE(policy != ParOperator::DiagonalPolicy::DIAG_ONE || RAPr_,
              "DiagonalPolicy::DIAG_ONE specified for ComplexParOperator with no real part!");
   for (int i = 0; i < n_ess; i++) PA_REQUIRE(ess_host[i] >= 0 && ess_host[i] < n_true_, "essential dof out of range");
-  if (d_ess_) (void)hipFree(d_ess_);
-  d_ess_ = n_ess ? pa::dev_upload(ess_host, (size_t)n_ess, ctx_->stream) : nullptr;
+  d_ess_.reset();
+  if (n_ess) d_ess_ = pa::dev_upload(ess_host, (size_t)n_ess, ctx_->stream);
   n_ess_ = n_ess, policy_ = policy;
   // the real ParOperators are rebuilt with the list (real part: the policy; imaginary part: DIAG_ZERO, rap.cpp:450-457)
   if (Ar_) RAPr_ = std::make_unique<ParOperator>(*ctx_, *Ar_, n_true_, ess_host, n_ess, policy, halo_, conf_);

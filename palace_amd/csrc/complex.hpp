@@ -184,7 +184,7 @@ class ComplexParOperator : public ComplexOperator {
   std::unique_ptr<ComplexWrapperOperator> RAP_;  // wrapper over RAPr / RAPi (single-rank fast path)
   const ceed::Operator *fused_r_ = nullptr, *fused_i_ = nullptr;  // single rank: one pass for both parts (pa_op_mult_complex)
   void UpdateFused();
-  int32_t *d_ess_ = nullptr;
+  pa::DevBuf<int32_t> d_ess_;
   int n_ess_ = 0;
   ParOperator::DiagonalPolicy policy_ = ParOperator::DiagonalPolicy::DIAG_ONE;
   mutable ComplexVector lx_, ly_, tt_;

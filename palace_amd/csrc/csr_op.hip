@@ -158,17 +158,16 @@ CsrOperator::CsrOperator(const Context &ctx, const pa_csr *m)
 CsrOperator::~CsrOperator() {
 }
 
-double *CsrOperator::EliminatedValues(const int32_t *d_ess, int n_ess, bool diag_one) const {
-  if (!height) return nullptr;
-  double *d_val_bc_ = pa::dev_alloc<double>((size_t)m_->nnz);
-  uint8_t *flag = pa::dev_alloc<uint8_t>((size_t)height);
+pa::DevBuf<double> CsrOperator::EliminatedValuesBuf(const int32_t *d_ess, int n_ess, bool diag_one) const {
+  if (!height) return {};
+  pa::DevBuf<double> d_val_bc_ = pa::dev_alloc<double>((size_t)m_->nnz);
+  const pa::DevBuf<uint8_t> flag = pa::dev_alloc<uint8_t>((size_t)height);
   PA_HIP(hipMemsetAsync(flag, 0, (size_t)height, ctx_->stream));
-  if (n_ess) hipLaunchKernelGGL(k_flag, dim3((n_ess + 255) / 256), dim3(256), 0, ctx_->stream, n_ess, d_ess, flag);
+  if (n_ess) hipLaunchKernelGGL(k_flag, dim3((n_ess + 255) / 256), dim3(256), 0, ctx_->stream, n_ess, d_ess, flag.get());
   hipLaunchKernelGGL(k_csr_eliminate, dim3((height + 255) / 256), dim3(256), 0, ctx_->stream, height, m_->d_rowptr,
-                     m_->d_col, m_->d_val, flag, diag_one ? 1.0 : 0.0, d_val_bc_);
+                     m_->d_col, m_->d_val, flag.get(), diag_one ? 1.0 : 0.0, d_val_bc_.get());
   PA_HIP(hipGetLastError());
   PA_HIP(hipStreamSynchronize(ctx_->stream));
-  PA_HIP(hipFree(flag));
   return d_val_bc_;
 }
 

@@ -63,11 +63,10 @@ amg::HostCsr AssembledLevelMatrix(const Operator &op, std::vector<char> &ess_fla
 // in-place sum over the ranks of a host array (Mpi::GlobalSum on a std::vector)
 void GlobalSumHost(const Context &ctx, std::vector<double> &v) {
   if (!ctx.comm || ctx.comm->Size() == 1 || v.empty()) return;
-  double *d = pa::dev_upload(v.data(), v.size(), ctx.stream);
+  const pa::DevBuf<double> d = pa::dev_upload(v.data(), v.size(), ctx.stream);
   ctx.comm->AllReduceSum(d, (int)v.size(), ctx.stream);
   PA_HIP(hipMemcpyAsync(v.data(), d, sizeof(double) * v.size(), hipMemcpyDeviceToHost, ctx.stream));
   PA_HIP(hipStreamSynchronize(ctx.stream));
-  (void)hipFree(d);
   ctx.comm->PeerCheckNow();
 }
 // the pieces of all ranks one after the other (rank order); counts / offsets of the pieces on request

@@ -31,7 +31,7 @@ Vector::~Vector() {
 void Vector::SetSize(int n) {
   if (own_ && n == n_) return;
   if (own_ && d_) (void)hipFree(d_);
-  d_ = pa::dev_alloc<double>((size_t)n);
+  d_ = pa::dev_alloc<double>((size_t)n).release();
   n_ = n, own_ = true;
 }
 void Vector::MakeRef(double *ext, int n) {
@@ -41,9 +41,7 @@ void Vector::MakeRef(double *ext, int n) {
 
 // ---- Workspace / StreamGraph -----------------------------------------------------------------
 Workspace::~Workspace() {
-  if (d_) (void)hipFree(d_);
   if (h_) (void)hipHostFree(h_);
-  if (gs_d_) (void)hipFree(gs_d_);
   if (gs_h_) (void)hipHostFree(gs_h_);
 }
 double *Workspace::Device(size_t n) {
@@ -59,10 +57,7 @@ double *Workspace::Pinned(size_t n) {
 
 double *Workspace::GsDevice(size_t n) {
   if (n > gs_dn_) {  // (the stream that used the old buffer has been synchronised: every column ends with a copy to the host)
-    if (gs_d_) {
-      PA_HIP(hipDeviceSynchronize());
-      (void)hipFree(gs_d_);
-    }
+    if (gs_d_) PA_HIP(hipDeviceSynchronize());
     gs_dn_ = std::max<size_t>(2 * n, 32768);
     gs_d_ = pa::dev_alloc<double>(gs_dn_);
     PA_HIP(hipMemset(gs_d_, 0, gs_dn_ * sizeof(double)));
@@ -1123,7 +1118,7 @@ ParOperator::ParOperator(const Context &ctx, const Operator &A, int n_true, cons
       }
     } else if (auto *m = dynamic_cast<const CsrOperator *>(&A)) {
       // assembled local operator: this wrapper's essential rows / columns folded into its own copy of the values
-      d_csr_bc_ = m->EliminatedValues(d_ess_, n_ess, policy == DiagonalPolicy::DIAG_ONE);
+      d_csr_bc_ = m->EliminatedValuesBuf(d_ess_, n_ess, policy == DiagonalPolicy::DIAG_ONE);
       if (d_csr_bc_) A_csr_split_ = A_csr_split_avail_ = m;
     }
   }
@@ -1137,16 +1132,12 @@ ParOperator::ParOperator(const Context &ctx, const Operator &A, int n_true, cons
   }
   if (!halo && !conf) {
     if (auto *m = dynamic_cast<const CsrOperator *>(&A)) {
-      d_csr_bc_ = m->EliminatedValues(d_ess_, n_ess, policy == DiagonalPolicy::DIAG_ONE);
+      d_csr_bc_ = m->EliminatedValuesBuf(d_ess_, n_ess, policy == DiagonalPolicy::DIAG_ONE);
       if (d_csr_bc_) A_csr_ = m;
     }
   }
 }
-ParOperator::~ParOperator() {
-  if (d_ess_mask_) (void)hipFree(d_ess_mask_);
-  if (d_ess_) (void)hipFree(d_ess_);
-  if (d_csr_bc_) (void)hipFree(d_csr_bc_);
-}
+ParOperator::~ParOperator() = default;
 
 bool ParOperator::PrepareChebyStep() const {
   if (conf_) return false;  // the step would have to run behind P^T: smoothers apply A and run the vector kernel
@@ -1545,7 +1536,7 @@ struct CgSolver::DeviceState {
     for (auto e : ev) (void)hipEventDestroy(e);
   }
   void Setup(int slots) {
-    if (!d_st) d_st = pa::dev_alloc<double>(CG_NSLOT);
+    if (!d_st) d_st = pa::dev_alloc<double>(CG_NSLOT).release();
     if (slots > ring) {
       if (h_ring) PA_HIP(hipHostFree(h_ring));
       PA_HIP(hipHostMalloc(reinterpret_cast<void **>(&h_ring), (size_t)slots * CG_NSLOT * sizeof(double), hipHostMallocDefault));
@@ -1849,10 +1840,7 @@ ReplicatedSolver::ReplicatedSolver(const Context &ctx, const Halo &gather, const
   gx_.SetSize(n_global), gy_.SetSize(n_global);
   linalg::Fill(ctx, gx_, 0.0);
 }
-ReplicatedSolver::~ReplicatedSolver() {
-  if (d_mine_) (void)hipFree(d_mine_);
-  if (d_sign_) (void)hipFree(d_sign_);
-}
+ReplicatedSolver::~ReplicatedSolver() = default;
 void ReplicatedSolver::Mult(const Vector &x, Vector &y) const {
   PhaseRange range("Coarse Solve / Replicated");
   const Context &c = *ctx_;

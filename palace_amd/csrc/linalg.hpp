@@ -31,7 +31,8 @@ struct HaloStep;
 // Reduction scratch of one context (per-block partial sums on the device, a pinned slot for the results); created on
 // first use and shared by the copies of a context -- never by two contexts, whose streams may reduce concurrently.
 class Workspace {
-  double *d_ = nullptr, *h_ = nullptr, *gs_d_ = nullptr, *gs_h_ = nullptr;
+  pa::DevBuf<double> d_, gs_d_;
+  double *h_ = nullptr, *gs_h_ = nullptr;
   size_t gs_dn_ = 0, gs_hn_ = 0;
 
 public:
@@ -354,7 +355,10 @@ public:
   // 1 | 0).  The copy belongs to the caller (hipFree): several wrappers with different essential lists can share one matrix,
   // and this operator itself always applies the unconstrained values.  Only stored entries are rewritten: an essential row
   // without a stored diagonal entry gets no unit entry (it becomes a zero row whatever `diag_one` says).
-  double *EliminatedValues(const int32_t *d_ess, int n_ess, bool diag_one) const;
+  double *EliminatedValues(const int32_t *d_ess, int n_ess, bool diag_one) const {
+    return EliminatedValuesBuf(d_ess, n_ess, diag_one).release();
+  }
+  pa::DevBuf<double> EliminatedValuesBuf(const int32_t *d_ess, int n_ess, bool diag_one) const;  // the same, owned (ParOperator)
   void MultValues(const double *d_vals, const Vector &x, Vector &y) const;  // y = A' x, A' = this pattern with `d_vals`
   // the same on split vectors (pa_op_mult_split's contract: true dofs in x / y, ghosts read from xg0 | xg1 by the parity of *sel
   // and written to yg); d_vals == nullptr: the unconstrained values
@@ -386,11 +390,10 @@ class Conforming {
   int n_true_, n_con_;
   int fwd_lanes_ = 1, tr_lanes_ = 1;  // lanes that share one row (powers of two, from the longest row)
   int n_touched_ = 0;                 // true dofs with at least one constrained dof hanging on them
-  int *d_row_ptr_ = nullptr, *d_t_ptr_ = nullptr;
-  int32_t *d_col_ = nullptr, *d_t_dof_ = nullptr, *d_t_slave_ = nullptr;
-  double *d_val_ = nullptr, *d_t_val_ = nullptr;
-  uint8_t *d_touched_ = nullptr;  // one byte per true dof: its row of C^T is not empty (the copy part of Restrict leaves it alone)
-  void Free();
+  pa::DevBuf<int> d_row_ptr_, d_t_ptr_;
+  pa::DevBuf<int32_t> d_col_, d_t_dof_, d_t_slave_;
+  pa::DevBuf<double> d_val_, d_t_val_;
+  pa::DevBuf<uint8_t> d_touched_;  // one byte per true dof: its row of C^T is not empty (the copy part of Restrict leaves it alone)
 
 public:
   enum : int { ADD = 1, ABS = 2, FIX_ONE = 4, FIX_ZERO = 8 };
@@ -428,14 +431,14 @@ private:
   const CsrOperator *A_csr_split_ = nullptr, *A_csr_split_avail_ = nullptr;  // the same for an assembled local operator
   bool split_ess_ = false;                     // ... with this wrapper's essential list fused into its index tables
   const CsrOperator *A_csr_ = nullptr;       // single rank, assembled local operator: BCs eliminated in the matrix values
-  double *d_csr_bc_ = nullptr;               // ... this wrapper's copy of them (CsrOperator::EliminatedValues)
+  pa::DevBuf<double> d_csr_bc_;              // ... this wrapper's copy of them (CsrOperator::EliminatedValuesBuf)
   const Halo *halo_;
   const Conforming *conf_ = nullptr;  // hanging-node constraints (one rank; never together with a halo)
   int n_true_, n_local_;
-  int32_t *d_ess_ = nullptr;
+  pa::DevBuf<int32_t> d_ess_;
   int n_ess_ = 0;
   std::vector<int32_t> ess_host_;
-  uint8_t *d_ess_mask_ = nullptr;  // with a halo: one byte per true dof, so that copy + mask and copy + fix-up are one launch each
+  pa::DevBuf<uint8_t> d_ess_mask_;  // with a halo: one byte per true dof, so that copy + mask and copy + fix-up are one launch each
   DiagonalPolicy policy_;
   mutable Vector lx_, ly_;
 
@@ -695,8 +698,8 @@ class ReplicatedSolver : public Solver {
   const Halo *gather_;    // plan on the global-numbered vector: send = my true dofs (global numbers), recv = the other ranks'
   const Solver *inner_;   // solver of the global problem (n_global x n_global)
   int n_true_, n_global_;
-  int32_t *d_mine_ = nullptr;  // [n_true] global number of my true dof i
-  double *d_sign_ = nullptr;   // [n_true] +-1: orientation of my dof relative to the global one (nullptr: all +1)
+  pa::DevBuf<int32_t> d_mine_;  // [n_true] global number of my true dof i
+  pa::DevBuf<double> d_sign_;   // [n_true] +-1: orientation of my dof relative to the global one (nullptr: all +1)
   mutable Vector gx_, gy_;
 
 public:

@@ -39,32 +39,13 @@ void apply_for_assembly(pa_op *op, const double *x, double *y, hipStream_t s);
 using namespace pa;
 
 namespace {
-// temporaries and the result of pa_op_full_assemble are released if anything in it throws
-struct AssembleGuard {
-  pa_csr *m = nullptr;
-  std::vector<void *> tmp;
-  ~AssembleGuard() {
-    for (void *p : tmp) (void)hipFree(p);
-    if (m) pa_csr_destroy(m);
-  }
-  template <typename T>
-  T *keep(T *p) {
-    tmp.push_back(p);
-    return p;
-  }
-  void release(void *p) {
-    for (auto &q : tmp)
-      if (q == p) q = nullptr;
-  }
-};
-
 // Two-space operators (BilinearForm(trial, test)::FullAssemble, e.g. Atn of models/modeeigensolver.cpp:45-56): rows are test
 // dofs, columns trial dofs.  Same probing as below; two columns may share a colour when no row holds both, which takes the
 // transposed pattern (column -> rows) next to the pattern itself.
-void assemble_two_space(pa_op *op, bool skip_zeros, hipStream_t s, pa_csr **out) {
+std::unique_ptr<pa_csr> assemble_two_space(pa_op *op, bool skip_zeros, hipStream_t s) {
   const int nr = op->height, nc = op->width;
   std::vector<int64_t> cnt((size_t)nr + 1, 0);
-  for (const MixedSub *ms : op->msubs) {
+  for (const auto &ms : op->msubs) {
     // (the gradient form has space_dim rows of test dofs per element: h_off of its test side lists them all)
     PA_REQUIRE(!ms->error && ms->ne > 0 && (int)ms->s1.h_off.size() == ms->ne * ms->s1.P && !ms->s2.h_off.empty() &&
                    ms->s2.h_off.size() % ((size_t)ms->ne * ms->s2.P) == 0,
@@ -76,7 +57,7 @@ void assemble_two_space(pa_op *op, bool skip_zeros, hipStream_t s, pa_csr **out)
   std::vector<int32_t> cols((size_t)cnt[nr]);
   {
     std::vector<int64_t> fill(cnt.begin(), cnt.end() - 1);
-    for (const MixedSub *ms : op->msubs)
+    for (const auto &ms : op->msubs)
       for (int e = 0; e < ms->ne; e++) {
         const int rows_e = (int)(ms->s2.h_off.size() / (size_t)ms->ne);
         const int32_t *re = &ms->s2.h_off[(size_t)e * rows_e], *ce = &ms->s1.h_off[(size_t)e * ms->s1.P];
@@ -123,20 +104,19 @@ void assemble_two_space(pa_op *op, bool skip_zeros, hipStream_t s, pa_csr **out)
     if (c == ncolors) ncolors++, mark.push_back(-1);
     color[d] = c;
   }
-  AssembleGuard guard;
-  auto *m = guard.m = new pa_csr;
+  auto m = std::make_unique<pa_csr>();
   m->nrows = nr, m->ncols = nc;
   m->symmetric = false;
-  int32_t *d_color = guard.keep(dev_upload(color.data(), color.size(), s)), *d_row_of = guard.keep(dev_upload(row_of.data(), row_of.size(), s));
-  int32_t *d_col = guard.keep(dev_upload(col.data(), col.size(), s));
-  double *d_val = guard.keep(dev_alloc<double>((size_t)std::max<int64_t>(nnz, 1))), *d_x = guard.keep(dev_alloc<double>((size_t)nc)),
-         *d_y = guard.keep(dev_alloc<double>((size_t)nr));
+  const DevBuf<int32_t> d_color = dev_upload(color.data(), color.size(), s), d_row_of = dev_upload(row_of.data(), row_of.size(), s);
+  DevBuf<int32_t> d_col = dev_upload(col.data(), col.size(), s);
+  DevBuf<double> d_val = dev_alloc<double>((size_t)nnz);
+  const DevBuf<double> d_x = dev_alloc<double>((size_t)nc), d_y = dev_alloc<double>((size_t)nr);
   PA_HIP(hipMemsetAsync(d_val, 0, sizeof(double) * (size_t)nnz, s));
   for (int c = 0; c < ncolors; c++) {
-    hipLaunchKernelGGL(k_probe_vector, dim3((nc + 255) / 256), dim3(256), 0, s, nc, d_color, c, d_x);
+    hipLaunchKernelGGL(k_probe_vector, dim3((nc + 255) / 256), dim3(256), 0, s, nc, d_color.get(), c, d_x.get());
     apply_for_assembly(op, d_x, d_y, s);
-    hipLaunchKernelGGL(k_extract, dim3((unsigned)((nnz + 255) / 256)), dim3(256), 0, s, (long long)nnz, d_row_of, d_col, d_color, c,
-                       d_y, d_val);
+    hipLaunchKernelGGL(k_extract, dim3((unsigned)((nnz + 255) / 256)), dim3(256), 0, s, (long long)nnz, d_row_of.get(), d_col.get(),
+                       d_color.get(), c, d_y.get(), d_val.get());
   }
   PA_HIP(hipGetLastError());
   PA_HIP(hipStreamSynchronize(s));
@@ -152,16 +132,13 @@ void assemble_two_space(pa_op *op, bool skip_zeros, hipStream_t s, pa_csr **out)
     }
     m->nnz = (int64_t)cl.size();
     m->d_rowptr = dev_upload(rp.data(), rp.size(), s);
-    m->d_col = cl.empty() ? nullptr : dev_upload(cl.data(), cl.size(), s);
-    m->d_val = vl.empty() ? nullptr : dev_upload(vl.data(), vl.size(), s);
+    if (!cl.empty()) m->d_col = dev_upload(cl.data(), cl.size(), s), m->d_val = dev_upload(vl.data(), vl.size(), s);
   } else {
     m->nnz = nnz;
     m->d_rowptr = dev_upload(rowptr.data(), rowptr.size(), s);
-    m->d_col = d_col, m->d_val = d_val;
-    guard.release(d_col), guard.release(d_val);
+    m->d_col = std::move(d_col), m->d_val = std::move(d_val);
   }
-  guard.m = nullptr;
-  *out = m;
+  return m;
 }
 }  // namespace
 
@@ -174,7 +151,7 @@ int pa_op_full_assemble(pa_op *op, int skip_zeros, void *stream, pa_csr **out) {
     hipStream_t s = (hipStream_t)stream;
     if (!op->msubs.empty()) {  // two-space operator: rectangular
       PA_REQUIRE(op->subs.empty() && op->dsubs.empty(), "two-space sub-operators are assembled on their own");
-      assemble_two_space(op, skip_zeros != 0, s, out);
+      *out = assemble_two_space(op, skip_zeros != 0, s).release();
       return;
     }
     PA_REQUIRE(op->height == op->width, "full assembly needs a square operator");
@@ -185,13 +162,13 @@ int pa_op_full_assemble(pa_op *op, int skip_zeros, void *stream, pa_csr **out) {
       std::vector<int32_t> off;
     };
     std::vector<Conn> conns;
-    for (const SubOp *so : op->subs) {
+    for (const auto &so : op->subs) {
       Conn c{so->ne, so->P, {}};
       c.off.resize(so->h_sidx.size());
       for (size_t k = 0; k < c.off.size(); k++) c.off[k] = so->h_sidx[k] >= 0 ? so->h_sidx[k] : -1 - so->h_sidx[k];
       conns.push_back(std::move(c));
     }
-    for (const DenseSub *ds : op->dsubs) conns.push_back(Conn{ds->ne, ds->P, ds->h_off});
+    for (const auto &ds : op->dsubs) conns.push_back(Conn{ds->ne, ds->P, ds->h_off});
     std::vector<int64_t> cnt((size_t)n + 1, 0);
     for (const Conn &c : conns)
       for (size_t k = 0; k < c.off.size(); k++) cnt[(size_t)c.off[k] + 1] += c.P;
@@ -242,19 +219,19 @@ int pa_op_full_assemble(pa_op *op, int skip_zeros, void *stream, pa_csr **out) {
     std::vector<int32_t> row_of((size_t)nnz);
     for (int r = 0; r < n; r++)
       for (int32_t a = rowptr[r]; a < rowptr[r + 1]; a++) row_of[a] = r;
-    AssembleGuard guard;
-    auto *m = guard.m = new pa_csr;
+    auto m = std::make_unique<pa_csr>();
     m->nrows = n;
     m->symmetric = op->symmetric();
-    int32_t *d_color = guard.keep(dev_upload(color.data(), color.size(), s)), *d_row_of = guard.keep(dev_upload(row_of.data(), row_of.size(), s));
-    int32_t *d_col = guard.keep(dev_upload(col.data(), col.size(), s));
-    double *d_val = guard.keep(dev_alloc<double>((size_t)nnz)), *d_x = guard.keep(dev_alloc<double>((size_t)n)), *d_y = guard.keep(dev_alloc<double>((size_t)n));
+    const DevBuf<int32_t> d_color = dev_upload(color.data(), color.size(), s), d_row_of = dev_upload(row_of.data(), row_of.size(), s);
+    DevBuf<int32_t> d_col = dev_upload(col.data(), col.size(), s);
+    DevBuf<double> d_val = dev_alloc<double>((size_t)nnz);
+    const DevBuf<double> d_x = dev_alloc<double>((size_t)n), d_y = dev_alloc<double>((size_t)n);
     PA_HIP(hipMemsetAsync(d_val, 0, sizeof(double) * (size_t)nnz, s));
     for (int c = 0; c < ncolors; c++) {
-      hipLaunchKernelGGL(k_probe_vector, dim3((n + 255) / 256), dim3(256), 0, s, n, d_color, c, d_x);
+      hipLaunchKernelGGL(k_probe_vector, dim3((n + 255) / 256), dim3(256), 0, s, n, d_color.get(), c, d_x.get());
       apply_for_assembly(op, d_x, d_y, s);
-      hipLaunchKernelGGL(k_extract, dim3((unsigned)((nnz + 255) / 256)), dim3(256), 0, s, (long long)nnz, d_row_of, d_col,
-                         d_color, c, d_y, d_val);
+      hipLaunchKernelGGL(k_extract, dim3((unsigned)((nnz + 255) / 256)), dim3(256), 0, s, (long long)nnz, d_row_of.get(), d_col.get(),
+                         d_color.get(), c, d_y.get(), d_val.get());
     }
     PA_HIP(hipGetLastError());
     PA_HIP(hipStreamSynchronize(s));
@@ -277,11 +254,9 @@ int pa_op_full_assemble(pa_op *op, int skip_zeros, void *stream, pa_csr **out) {
     } else {
       m->nnz = nnz;
       m->d_rowptr = dev_upload(rowptr.data(), rowptr.size(), s);
-      m->d_col = d_col, m->d_val = d_val;
-      guard.release(d_col), guard.release(d_val);
+      m->d_col = std::move(d_col), m->d_val = std::move(d_val);
     }
-    guard.m = nullptr;
-    *out = m;
+    *out = m.release();
   });
 }
 
@@ -299,10 +274,6 @@ int pa_csr_get(const pa_csr *m, int32_t *nrows, int64_t *nnz, const int32_t **ro
 
 int pa_csr_num_cols(const pa_csr *m) { return m ? (m->ncols ? m->ncols : m->nrows) : -1; }
 
-void pa_csr_destroy(pa_csr *m) {
-  if (!m) return;
-  hipFree(m->d_rowptr), hipFree(m->d_col), hipFree(m->d_val);
-  delete m;
-}
+void pa_csr_destroy(pa_csr *m) { delete m; }
 
 }  // extern "C"

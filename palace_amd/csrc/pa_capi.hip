@@ -13,6 +13,14 @@ namespace pa {
 static thread_local std::string g_error;
 void set_error(const std::string &msg) { g_error = msg; }
 
+// the device side of DevBuf (pa_devbuf.hpp)
+void *dev_malloc_bytes(size_t bytes) {
+  void *p = nullptr;
+  PA_HIP(hipMalloc(&p, bytes));
+  return p;
+}
+void dev_free_bytes(void *p) noexcept { (void)hipFree(p); }
+
 static void require_device() {
   int n = 0;
   const hipError_t err = hipGetDeviceCount(&n);
@@ -49,7 +57,7 @@ void parse_coeff(const void *blob, size_t bytes, int dim, CoeffHost &out, size_t
   for (int i = 0; i < nattr; i++)
     PA_REQUIRE(out.attr_mat[i] >= 0 && out.attr_mat[i] < nmat, "attribute maps to missing material");
   out.slots = 2 + nattr + out.mat.size();
-  out.d_attr_mat = nattr ? dev_upload(out.attr_mat.data(), (size_t)nattr) : nullptr;
+  if (nattr) out.d_attr_mat = dev_upload(out.attr_mat.data(), (size_t)nattr);
   out.d_mat = dev_upload(out.mat.data(), out.mat.size());
   // transposed copy for A^T (only when it differs)
   std::vector<double> mt(out.mat);
@@ -60,7 +68,7 @@ void parse_coeff(const void *blob, size_t bytes, int dim, CoeffHost &out, size_t
         mt[(size_t)k * dim * dim + i + dim * j] = out.mat[(size_t)k * dim * dim + j + dim * i];
         sym = sym && out.mat[(size_t)k * dim * dim + i + dim * j] == out.mat[(size_t)k * dim * dim + j + dim * i];
       }
-  out.d_mat_t = sym ? nullptr : dev_upload(mt.data(), mt.size());
+  if (!sym) out.d_mat_t = dev_upload(mt.data(), mt.size());
 }
 
 static thread_local bool g_transpose = false;
@@ -171,118 +179,113 @@ static void check_dense_tables(const pa_basis_desc &b, int P, int Q) {
 // The part of a tensor-product block that depends on the space alone: the 1-D tables (checked against the dense ones and for
 // mirror symmetry), the signed tensor-order index in the geometry data's element order, its sorted form and the transpose
 // map of the gather form of E^T.  always_gather: build that map whatever PALACE_AMD_SCATTER says (the two-space forms).
-static SubOp *new_hex_block(pa_geom *geom, const pa_restriction_desc &r, const pa_basis_desc &b, const int P, const bool always_gather) {
-  auto *so = new SubOp;
-  so->geom = geom;
-  geom->refcount++;
-  try {
-    so->fe_type = b.fe_type, so->p = b.order, so->q1d = b.q1d, so->P = P, so->Q = geom->Q;
-    so->ne = r.num_elem, so->lsize = r.lsize;
-    const int nc = b.order + 1;
-    so->Bc.assign(b.Bc, b.Bc + b.q1d * nc);
-    so->Gc.assign(b.Gc, b.Gc + b.q1d * nc);
-    if (b.Bo) so->Bo.assign(b.Bo, b.Bo + b.q1d * b.order);
-    check_dense_tables(b, P, geom->Q);
-    // the kernels rely on the mirror symmetry of Gauss-Legendre / Gauss-Lobatto tables
-    {
-      double worst = 0.0;
-      const int q1 = b.q1d;
-      for (int q = 0; q < q1; q++) {
-        for (int i = 0; i < nc; i++) {
-          worst = std::fmax(worst, std::fabs(so->Bc[q * nc + i] - so->Bc[(q1 - 1 - q) * nc + (nc - 1 - i)]));
-          worst = std::fmax(worst, std::fabs(so->Gc[q * nc + i] + so->Gc[(q1 - 1 - q) * nc + (nc - 1 - i)]));
-        }
-        if (b.Bo)
-          for (int i = 0; i < b.order; i++)
-            worst = std::fmax(worst, std::fabs(so->Bo[q * b.order + i] -
-                                               so->Bo[(q1 - 1 - q) * b.order + (b.order - 1 - i)]));
+static std::unique_ptr<SubOp> new_hex_block(pa_geom *geom, const pa_restriction_desc &r, const pa_basis_desc &b, const int P,
+                                            const bool always_gather) {
+  auto so = std::make_unique<SubOp>();
+  so->geom = Ref<Geom>(geom);
+  so->fe_type = b.fe_type, so->p = b.order, so->q1d = b.q1d, so->P = P, so->Q = geom->Q;
+  so->ne = r.num_elem, so->lsize = r.lsize;
+  const int nc = b.order + 1;
+  so->Bc.assign(b.Bc, b.Bc + b.q1d * nc);
+  so->Gc.assign(b.Gc, b.Gc + b.q1d * nc);
+  if (b.Bo) so->Bo.assign(b.Bo, b.Bo + b.q1d * b.order);
+  check_dense_tables(b, P, geom->Q);
+  // the kernels rely on the mirror symmetry of Gauss-Legendre / Gauss-Lobatto tables
+  {
+    double worst = 0.0;
+    const int q1 = b.q1d;
+    for (int q = 0; q < q1; q++) {
+      for (int i = 0; i < nc; i++) {
+        worst = std::fmax(worst, std::fabs(so->Bc[q * nc + i] - so->Bc[(q1 - 1 - q) * nc + (nc - 1 - i)]));
+        worst = std::fmax(worst, std::fabs(so->Gc[q * nc + i] + so->Gc[(q1 - 1 - q) * nc + (nc - 1 - i)]));
       }
-      if (!(worst < 1e-12)) throw Error("1-D basis tables are not mirror-symmetric (non Gauss-Legendre/Lobatto nodes?)");
-      std::vector<double> tab;
-      tab.insert(tab.end(), so->Bo.begin(), so->Bo.end());
-      if (so->Bo.empty()) tab.assign((size_t)b.q1d * b.order, 0.0);
-      tab.insert(tab.end(), so->Bc.begin(), so->Bc.end());
-      tab.insert(tab.end(), so->Gc.begin(), so->Gc.end());
-      so->d_tab = dev_upload(tab.data(), tab.size());
+      if (b.Bo)
+        for (int i = 0; i < b.order; i++)
+          worst = std::fmax(worst, std::fabs(so->Bo[q * b.order + i] -
+                                             so->Bo[(q1 - 1 - q) * b.order + (b.order - 1 - i)]));
     }
+    if (!(worst < 1e-12)) throw Error("1-D basis tables are not mirror-symmetric (non Gauss-Legendre/Lobatto nodes?)");
+    std::vector<double> tab;
+    tab.insert(tab.end(), so->Bo.begin(), so->Bo.end());
+    if (so->Bo.empty()) tab.assign((size_t)b.q1d * b.order, 0.0);
+    tab.insert(tab.end(), so->Bc.begin(), so->Bc.end());
+    tab.insert(tab.end(), so->Gc.begin(), so->Gc.end());
+    so->d_tab = dev_upload(tab.data(), tab.size());
+  }
 
-    // signed tensor-order index array (restriction.cpp:290-296 semantics folded with dof_map)
-    std::vector<int32_t> lidx((size_t)r.num_elem * P);
-    std::vector<char> seen(P);
+  // signed tensor-order index array (restriction.cpp:290-296 semantics folded with dof_map)
+  std::vector<int32_t> lidx((size_t)r.num_elem * P);
+  std::vector<char> seen(P);
+  for (int l = 0; l < P; l++) {
+    int n = b.dof_map ? b.dof_map[l] : l;
+    if (n < 0) n = -1 - n;
+    PA_REQUIRE(n >= 0 && n < P && !seen[n], "dof_map is not a signed permutation");
+    seen[n] = 1;
+  }
+  for (int e = 0; e < r.num_elem; e++)  // internal element order (the geometry data's, pa_geom.hip)
     for (int l = 0; l < P; l++) {
       int n = b.dof_map ? b.dof_map[l] : l;
-      if (n < 0) n = -1 - n;
-      PA_REQUIRE(n >= 0 && n < P && !seen[n], "dof_map is not a signed permutation");
-      seen[n] = 1;
+      bool neg = false;
+      if (n < 0) n = -1 - n, neg = true;
+      const size_t k = (size_t)(geom->eorder.empty() ? e : geom->eorder[e]) * P + n;
+      const int32_t off = r.offsets[k];
+      PA_REQUIRE(off >= 0 && off < r.lsize, "restriction offset out of range");
+      if (r.orients && r.orients[k]) neg = !neg;
+      lidx[(size_t)e * P + l] = neg ? -1 - off : off;
     }
-    for (int e = 0; e < r.num_elem; e++)  // internal element order (the geometry data's, pa_geom.hip)
-      for (int l = 0; l < P; l++) {
-        int n = b.dof_map ? b.dof_map[l] : l;
-        bool neg = false;
-        if (n < 0) n = -1 - n, neg = true;
-        const size_t k = (size_t)(geom->eorder.empty() ? e : geom->eorder[e]) * P + n;
-        const int32_t off = r.offsets[k];
-        PA_REQUIRE(off >= 0 && off < r.lsize, "restriction offset out of range");
-        if (r.orients && r.orients[k]) neg = !neg;
-        lidx[(size_t)e * P + l] = neg ? -1 - off : off;
-      }
-    so->d_lidx = dev_upload(lidx.data(), lidx.size());
-    PA_REQUIRE(r.lsize < kEssBit, "too many local dofs for the index encoding");
-    PA_REQUIRE(P < 65536, "element too large for the 16-bit slot permutation");
-    // Sorted order of the element's entries (by global dof, stable): what E gathers and E^T stores
-    // in, so that one load/store instruction touches neighbouring dofs.
-    const size_t nnz = lidx.size();
-    std::vector<int32_t> sidx(nnz);
-    std::vector<uint16_t> perm(nnz);
-    {
-      std::vector<int> ord(P);
-      for (int e = 0; e < r.num_elem; e++) {
-        const int32_t *le = &lidx[(size_t)e * P];
-        for (int l = 0; l < P; l++) ord[l] = l;
-        std::stable_sort(ord.begin(), ord.end(), [&](int a, int c2) {
-          const int da = le[a] >= 0 ? le[a] : -1 - le[a], dc = le[c2] >= 0 ? le[c2] : -1 - le[c2];
-          return da < dc;
-        });
-        for (int m = 0; m < P; m++) {
-          sidx[(size_t)e * P + m] = le[ord[m]];
-          perm[(size_t)e * P + m] = (uint16_t)ord[m];
-        }
+  so->d_lidx = dev_upload(lidx.data(), lidx.size());
+  PA_REQUIRE(r.lsize < kEssBit, "too many local dofs for the index encoding");
+  PA_REQUIRE(P < 65536, "element too large for the 16-bit slot permutation");
+  // Sorted order of the element's entries (by global dof, stable): what E gathers and E^T stores
+  // in, so that one load/store instruction touches neighbouring dofs.
+  const size_t nnz = lidx.size();
+  std::vector<int32_t> sidx(nnz);
+  std::vector<uint16_t> perm(nnz);
+  {
+    std::vector<int> ord(P);
+    for (int e = 0; e < r.num_elem; e++) {
+      const int32_t *le = &lidx[(size_t)e * P];
+      for (int l = 0; l < P; l++) ord[l] = l;
+      std::stable_sort(ord.begin(), ord.end(), [&](int a, int c2) {
+        const int da = le[a] >= 0 ? le[a] : -1 - le[a], dc = le[c2] >= 0 ? le[c2] : -1 - le[c2];
+        return da < dc;
+      });
+      for (int m = 0; m < P; m++) {
+        sidx[(size_t)e * P + m] = le[ord[m]];
+        perm[(size_t)e * P + m] = (uint16_t)ord[m];
       }
     }
-    so->d_sidx = dev_upload(sidx.data(), nnz);
-    so->d_perm = dev_upload(perm.data(), nnz);
-    so->h_perm = perm;
-    // transpose map for the gather form of E^T (counting sort by dof; element order preserved, so the
-    // summation order of every dof is fixed) unless PALACE_AMD_SCATTER=atomic asks for the atomic form
-    const char *mode = getenv("PALACE_AMD_SCATTER");
-    if (always_gather || !(mode && std::string(mode) == "atomic") || b.fe_type != PA_FE_HCURL) {
-      std::vector<int32_t> tptr((size_t)r.lsize + 1, 0), tent(nnz);
-      for (size_t k = 0; k < nnz; k++) {
-        const int32_t s = sidx[k];
-        tptr[(size_t)(s >= 0 ? s : -1 - s) + 1]++;
-      }
-      for (int d = 0; d < r.lsize; d++) tptr[d + 1] += tptr[d];
-      std::vector<int32_t> fill(tptr.begin(), tptr.end() - 1);
-      for (size_t k = 0; k < nnz; k++) {  // E-vector position of a sorted entry is its own index
-        const int32_t s = sidx[k];
-        const int d = s >= 0 ? s : -1 - s;
-        tent[fill[d]++] = s >= 0 ? (int32_t)k : -1 - (int32_t)k;
-      }
-      so->d_tptr = dev_upload(tptr.data(), tptr.size());
-      so->d_tent = dev_upload(tent.data(), tent.size());
-      so->d_ye = dev_alloc<double>((size_t)((r.num_elem + 3) & ~3) * P);  // padded to whole batches of the streaming kernel
-    }
-    so->h_sidx = std::move(sidx);
-  } catch (...) {
-    free_sub(so);
-    throw;
   }
+  so->d_sidx = dev_upload(sidx.data(), nnz);
+  so->d_perm = dev_upload(perm.data(), nnz);
+  so->h_perm = perm;
+  // transpose map for the gather form of E^T (counting sort by dof; element order preserved, so the
+  // summation order of every dof is fixed) unless PALACE_AMD_SCATTER=atomic asks for the atomic form
+  const char *mode = getenv("PALACE_AMD_SCATTER");
+  if (always_gather || !(mode && std::string(mode) == "atomic") || b.fe_type != PA_FE_HCURL) {
+    std::vector<int32_t> tptr((size_t)r.lsize + 1, 0), tent(nnz);
+    for (size_t k = 0; k < nnz; k++) {
+      const int32_t s = sidx[k];
+      tptr[(size_t)(s >= 0 ? s : -1 - s) + 1]++;
+    }
+    for (int d = 0; d < r.lsize; d++) tptr[d + 1] += tptr[d];
+    std::vector<int32_t> fill(tptr.begin(), tptr.end() - 1);
+    for (size_t k = 0; k < nnz; k++) {  // E-vector position of a sorted entry is its own index
+      const int32_t s = sidx[k];
+      const int d = s >= 0 ? s : -1 - s;
+      tent[fill[d]++] = s >= 0 ? (int32_t)k : -1 - (int32_t)k;
+    }
+    so->d_tptr = dev_upload(tptr.data(), tptr.size());
+    so->d_tent = dev_upload(tent.data(), tent.size());
+    so->d_ye = dev_alloc<double>((size_t)((r.num_elem + 3) & ~3) * P);  // padded to whole batches of the streaming kernel
+  }
+  so->h_sidx = std::move(sidx);
   return so;
 }
 
-static SubOp *make_sub(pa_geom *geom, const pa_restriction_desc &r, const pa_basis_desc &b, int qf,
-                       const void *ctx, size_t ctx_size, uint32_t trial_ops, uint32_t test_ops,
-                       QData *shared_qd = nullptr) {
+static std::unique_ptr<SubOp> make_sub(pa_geom *geom, const pa_restriction_desc &r, const pa_basis_desc &b, int qf,
+                                       const void *ctx, size_t ctx_size, uint32_t trial_ops, uint32_t test_ops,
+                                       const Ref<QData> &shared_qd = Ref<QData>()) {
   require_device();
   PA_REQUIRE(geom && geom->d_geom, "geometry data missing");
   PA_REQUIRE(geom->eb == 0, "geometry data of a dense element block: use pa_op_add_sub_dense");
@@ -333,12 +336,12 @@ static SubOp *make_sub(pa_geom *geom, const pa_restriction_desc &r, const pa_bas
                      (qf == PA_QF_HCURL_33 && b.fe_type == PA_FE_HCURL);
   PA_REQUIRE(rt || nd_qf == (b.fe_type == PA_FE_HCURL), "QFunction does not match the element type");
 
-  SubOp *so = new_hex_block(geom, r, b, P, false);
+  PA_REQUIRE(ctx && ctx_size >= 24 && ctx_size % 8 == 0, "coefficient context missing or malformed");
+  std::unique_ptr<SubOp> so = new_hex_block(geom, r, b, P, false);
   so->qf = qf;
   so->trial_ops = trial_ops, so->test_ops = test_ops;
 
   so->ctx_blob.assign((const uint8_t *)ctx, (const uint8_t *)ctx + ctx_size);
-  PA_REQUIRE(ctx && ctx_size >= 24 && ctx_size % 8 == 0, "coefficient context missing or malformed");
   switch (qf) {
     case PA_QF_HDIV_33:
     case PA_QF_HCURL_33:
@@ -397,13 +400,11 @@ static SubOp *make_sub(pa_geom *geom, const pa_restriction_desc &r, const pa_bas
   if (metric_ok) {
     if (!geom->metric) launch_nd_hex_metric(*so, nullptr);
     so->qd = geom->metric;
-    geom->metric->refcount++;
   }
   if (so->qd) {
     // metric form chosen above
   } else if (shared_qd) {
     so->qd = shared_qd;
-    shared_qd->refcount++;
   } else if (want_qd) {
     if (b.fe_type == PA_FE_HCURL)
       launch_nd_hex_qdata(*so, nullptr);
@@ -416,26 +417,9 @@ static SubOp *make_sub(pa_geom *geom, const pa_restriction_desc &r, const pa_bas
   return so;
 }
 
-void free_sub(SubOp *so) {
-  if (!so) return;
-  hipFree(so->d_lidx);
-  hipFree(so->d_sidx), hipFree(so->d_sidx_bc), hipFree(so->d_perm), hipFree(so->d_perm_x), hipFree(so->d_shared), hipFree(so->d_shared_bc);
-  hipFree(so->d_ye), hipFree(so->d_ye2), hipFree(so->d_tptr), hipFree(so->d_tent);
-  free_stream(*so);
-  if (so->qd && --so->qd->refcount == 0) {
-    hipFree(so->qd->d), hipFree(so->qd->d_aff), hipFree(so->qd->d_col);
-    delete so->qd;
-  }
-  hipFree(so->d_tab);
-  hipFree(so->c0.d_attr_mat), hipFree(so->c0.d_mat), hipFree(so->c0.d_mat_t);
-  hipFree(so->c1.d_attr_mat), hipFree(so->c1.d_mat), hipFree(so->c1.d_mat_t);
-  pa_geom_destroy(static_cast<pa_geom *>(so->geom));
-  delete so;
-}
-
 // One Nedelec and one Raviart-Thomas tensor-product space of the same order on the same hexahedra: the mixed mass (kind 0 | 1) or
 // the element error integrator (2 | 3) of pa_mixed_hex.hip.  The argument checks are those of make_mixed_sub (pa_mixed.hip).
-MixedSub *make_mixed_hex_sub(pa_geom *geom, const pa_restriction_desc &r1, const pa_basis_desc &b1, const pa_restriction_desc &r2,
+std::unique_ptr<MixedSub> make_mixed_hex_sub(pa_geom *geom, const pa_restriction_desc &r1, const pa_basis_desc &b1, const pa_restriction_desc &r2,
                              const pa_basis_desc &b2, int qf, const void *ctx, size_t ctx_size) {
   require_device();
   PA_REQUIRE(geom && geom->d_geom && geom->eb == 0 && geom->dim == 3 && geom->sdim == 3,
@@ -461,32 +445,26 @@ MixedSub *make_mixed_hex_sub(pa_geom *geom, const pa_restriction_desc &r1, const
                  r2.offsets && r1.lsize > 0 && r2.lsize > 0,
              "restriction does not match the basis");
   PA_REQUIRE(ctx && ctx_size >= 16 && ctx_size % 8 == 0, "bad coefficient context");
-  auto *ms = new MixedSub;
-  try {
-    ms->geom = geom;
-    geom->refcount++;
-    ms->ne = geom->ne, ms->Q = geom->Q, ms->qf = qf, ms->kind = kind, ms->error = err;
-    ms->hex1 = new_hex_block(geom, r1, b1, r1.elem_size, true);
-    ms->hex2 = new_hex_block(geom, r2, b2, r2.elem_size, true);
-    for (size_t i = 0; i < ms->hex1->Bo.size(); i++)
-      PA_REQUIRE(ms->hex1->Bo[i] == ms->hex2->Bo[i], "the two spaces use different 1-D tables");
-    for (size_t i = 0; i < ms->hex1->Bc.size(); i++)
-      PA_REQUIRE(ms->hex1->Bc[i] == ms->hex2->Bc[i], "the two spaces use different 1-D tables");
-    // what full assembly reads of a two-space operator: the plain dof lists of the two sides (internal element order)
-    auto plain = [](const SubOp &so, MixedSide &sd) {
-      sd.fe_type = so.fe_type, sd.P = so.P, sd.lsize = so.lsize;
-      sd.h_off.resize(so.h_sidx.size());
-      for (size_t k = 0; k < sd.h_off.size(); k++) sd.h_off[k] = so.h_sidx[k] >= 0 ? so.h_sidx[k] : -1 - so.h_sidx[k];
-    };
-    plain(*ms->hex1, ms->s1), plain(*ms->hex2, ms->s2);
-    parse_coeff(ctx, ctx_size, 3, ms->c0, 0);
-    if (err) {
-      parse_coeff(ctx, ctx_size, 3, ms->c1, ms->c0.slots);  // PopulateCoefficientContext(dim, first, dim, second)
-      if (!geom->eorder.empty()) ms->d_eorder = dev_upload(geom->eorder.data(), geom->eorder.size());
-    }
-  } catch (...) {
-    free_mixed_sub(ms);
-    throw;
+  auto ms = std::make_unique<MixedSub>();
+  ms->geom = Ref<Geom>(geom);
+  ms->ne = geom->ne, ms->Q = geom->Q, ms->qf = qf, ms->kind = kind, ms->error = err;
+  ms->hex1 = new_hex_block(geom, r1, b1, r1.elem_size, true);
+  ms->hex2 = new_hex_block(geom, r2, b2, r2.elem_size, true);
+  for (size_t i = 0; i < ms->hex1->Bo.size(); i++)
+    PA_REQUIRE(ms->hex1->Bo[i] == ms->hex2->Bo[i], "the two spaces use different 1-D tables");
+  for (size_t i = 0; i < ms->hex1->Bc.size(); i++)
+    PA_REQUIRE(ms->hex1->Bc[i] == ms->hex2->Bc[i], "the two spaces use different 1-D tables");
+  // what full assembly reads of a two-space operator: the plain dof lists of the two sides (internal element order)
+  auto plain = [](const SubOp &so, MixedSide &sd) {
+    sd.fe_type = so.fe_type, sd.P = so.P, sd.lsize = so.lsize;
+    sd.h_off.resize(so.h_sidx.size());
+    for (size_t k = 0; k < sd.h_off.size(); k++) sd.h_off[k] = so.h_sidx[k] >= 0 ? so.h_sidx[k] : -1 - so.h_sidx[k];
+  };
+  plain(*ms->hex1, ms->s1), plain(*ms->hex2, ms->s2);
+  parse_coeff(ctx, ctx_size, 3, ms->c0, 0);
+  if (err) {
+    parse_coeff(ctx, ctx_size, 3, ms->c1, ms->c0.slots);  // PopulateCoefficientContext(dim, first, dim, second)
+    if (!geom->eorder.empty()) ms->d_eorder = dev_upload(geom->eorder.data(), geom->eorder.size());
   }
   return ms;
 }
@@ -503,7 +481,7 @@ static void apply(pa_op *op, const double *x, double *y, bool overwrite, hipStre
              "transposed apply of an operator with two-space sub-operators: those only");
   bool first = true;
   const StreamForm form = stream_form(masked);
-  for (const SubOp *so : op->subs) {
+  for (const auto &so : op->subs) {
     if (so->fe_type == PA_FE_HCURL) {
       if (so->d_idxc && overwrite && first && (!masked || so->stream[kStreamMasked].ready())) {  // streaming kernel (y = A x) + E^T of the shared dofs by runs
         launch_nd_hex_stream(*so, x, y, form, s);
@@ -530,12 +508,12 @@ static void apply(pa_op *op, const double *x, double *y, bool overwrite, hipStre
     }
     first = false;
   }
-  for (const DenseSub *ds : op->dsubs) {
+  for (const auto &ds : op->dsubs) {
     launch_dense_apply(*ds, x, masked, s);
     launch_dense_gather(*ds, y, !(overwrite && first), s);
     first = false;
   }
-  for (const MixedSub *ms : op->msubs) {
+  for (const auto &ms : op->msubs) {
     launch_mixed_apply(*ms, x, y, !(overwrite && first), s, TransposeScope::active());
     first = false;
   }
@@ -548,7 +526,7 @@ void finalize_exclusive(pa_op *op) {
   const char *mode = getenv("PALACE_AMD_DIRECT");
   if (mode && std::string(mode) == "0") return;
   if (op->subs.size() != 1 || !op->msubs.empty()) return;
-  SubOp *so = op->subs[0];
+  SubOp *so = op->subs[0].get();
   if (!so->d_ye || so->d_perm_x || !so->h_shared.empty()) return;
   if (so->fe_type == PA_FE_H1) {
     // H1 blocks: only the streaming kernel stores exclusive dofs directly; the one-shot kernel and its gather keep the
@@ -591,7 +569,7 @@ static bool apply2(pa_op *op, const double *x0, const double *x1, double *y0, do
   PA_REQUIRE(op && x0 && x1 && y0 && y1, "null argument");
   PA_REQUIRE(x0 != y0 && x0 != y1 && x1 != y0 && x1 != y1 && y0 != y1, "in-place apply is not supported");
   if (op->subs.size() == 1 && op->dsubs.empty() && nd_hex_supports_two_rhs(*op->subs[0])) {
-    SubOp *so = op->subs[0];
+    SubOp *so = op->subs[0].get();
     if (!so->d_ye2) so->d_ye2 = dev_alloc<double>((size_t)((so->ne + 3) & ~3) * so->P);
     const int pol = nd_hex_fuses_essential(*so) ? ess_policy : -1;
     launch_nd_hex_apply(*so, x0, y0, so->d_ye, masked, s, false, pol, x1, y1, so->d_ye2);
@@ -601,7 +579,7 @@ static bool apply2(pa_op *op, const double *x0, const double *x1, double *y0, do
   // a single Raviart-Thomas block on packed D: one element pass, one gather over the (flagged) dof list for both vectors
   if (op->subs.size() == 1 && op->dsubs.empty() && op->msubs.empty() && !TransposeScope::active() &&
       rt_hex_supports_two_rhs(*op->subs[0])) {
-    SubOp *so = op->subs[0];
+    SubOp *so = op->subs[0].get();
     launch_rt_hex_apply2(*so, x0, x1, masked, s);
     const bool fuse = masked && ess_policy >= 0 && so->d_shared_bc;
     launch_et_gather2_raw(so->lsize, so->d_tptr, so->d_tent, so->d_ye, so->d_ye2, y0, y1, false, s, fuse ? so->d_shared_bc : nullptr,
@@ -643,11 +621,11 @@ static uint64_t next_op_id() {
 }
 
 bool pa_op::symmetric() const {
-  for (const pa::SubOp *so : subs)  // (C u, curl v) and (C curl u, v) are each other's transposes, never their own
+  for (const auto &so : subs)  // (C u, curl v) and (C curl u, v) are each other's transposes, never their own
     if (so->qf == PA_QF_HCURLHDIV_33 || so->qf == PA_QF_HDIVHCURL_33) return false;
-  for (const pa::SubOp *so : subs)
+  for (const auto &so : subs)
     if (!so->c0.symmetric() || !so->c1.symmetric()) return false;
-  for (const pa::DenseSub *ds : dsubs)
+  for (const auto &ds : dsubs)
     if (!ds->c0.symmetric() || !ds->c1.symmetric()) return false;
   if (!msubs.empty()) return false;
   return true;
@@ -660,6 +638,8 @@ extern "C" {
 const char *pa_last_error(void) { return g_error.c_str(); }
 
 const char *pa_version(void) { return "palace_amd 0.1 (gfx950)"; }
+
+int64_t pa_device_buffers_live(void) { return g_dev_buffers_live.load(); }
 
 int pa_device_count(void) {
   int n = 0;
@@ -676,14 +656,9 @@ int pa_geom_create(const pa_mesh_desc *mesh, void *stream, pa_geom **geom) {
     PA_REQUIRE(mesh->node_offsets && mesh->nodes && mesh->attr && mesh->mesh_B && mesh->mesh_G &&
                    mesh->qweight1d,
                "mesh descriptor arrays missing");
-    auto *g = new pa_geom;
-    try {
-      launch_geom(*mesh, *g, (hipStream_t)stream);
-    } catch (...) {
-      delete g;
-      throw;
-    }
-    *geom = g;
+    auto g = std::make_unique<pa_geom>();
+    launch_geom(*mesh, *g, (hipStream_t)stream);
+    *geom = g.release();
   });
 }
 
@@ -691,14 +666,9 @@ int pa_geom_create_dense(const pa_mesh_dense_desc *mesh, void *stream, pa_geom *
   return guarded([&] {
     require_device();
     PA_REQUIRE(mesh && geom, "null argument");
-    auto *g = new pa_geom;
-    try {
-      launch_geom_dense(*mesh, *g, (hipStream_t)stream);
-    } catch (...) {
-      delete g;
-      throw;
-    }
-    *geom = g;
+    auto g = std::make_unique<pa_geom>();
+    launch_geom_dense(*mesh, *g, (hipStream_t)stream);
+    *geom = g.release();
   });
 }
 
@@ -725,20 +695,7 @@ int pa_geom_retain(pa_geom *geom) {
   });
 }
 
-void pa_geom_destroy(pa_geom *geom) {
-  if (!geom) return;
-  if (--geom->refcount == 0) {
-    hipFree(geom->d_geom);
-    hipFree(geom->d_qw);
-    hipFree(geom->d_attr_e);
-    hipFree(geom->d_xnodes), hipFree(geom->d_gtab);
-    if (geom->metric) {
-      hipFree(geom->metric->d), hipFree(geom->metric->d_aff), hipFree(geom->metric->d_col);
-      delete geom->metric;
-    }
-    delete geom;
-  }
-}
+void pa_geom_destroy(pa_geom *geom) { Ref<Geom>::drop(geom); }
 
 int pa_geom_data(const pa_geom *geom, const double **dev_ptr, size_t *count) {
   return guarded([&] {
@@ -849,7 +806,6 @@ int pa_op_add_sub_dense_vector_mass(pa_op *op, pa_geom *geom, const pa_restricti
     CoeffHost C;
     parse_coeff(ctx, ctx_size, num_comp, C, 0);
     const int nattr = (int)C.attr_mat.size(), nmat = (int)(C.mat.size() / ((size_t)num_comp * num_comp));
-    hipFree(C.d_attr_mat), hipFree(C.d_mat), hipFree(C.d_mat_t);
     const size_t ndof = (size_t)restr->num_elem * restr->elem_size;
     std::vector<std::vector<int32_t>> off((size_t)num_comp, std::vector<int32_t>(ndof));
     for (int c = 0; c < num_comp; c++)
@@ -884,7 +840,7 @@ int pa_op_add_sub_dense_vector_mass(pa_op *op, pa_geom *geom, const pa_restricti
 }
 
 struct pa_error_op {
-  MixedSub *ms = nullptr;
+  std::unique_ptr<MixedSub> ms;
 };
 
 int pa_error_op_create(pa_geom *geom, const pa_restriction_desc *restr1, const pa_dense_basis_desc *basis1,
@@ -897,14 +853,9 @@ int pa_error_op_create(pa_geom *geom, const pa_restriction_desc *restr1, const p
                    qfunction == PA_QF_HCURLHDIV_ERROR_22 || qfunction == PA_QF_HDIVHCURL_ERROR_22 ||
                    qfunction == PA_QF_L2H1_ERROR,
                "not an error QFunction");
-    auto *e = new pa_error_op;
-    try {
-      e->ms = make_mixed_sub(geom, *restr1, *basis1, *restr2, *basis2, qfunction, ctx, ctx_size);
-    } catch (...) {
-      delete e;
-      throw;
-    }
-    *out = e;
+    auto e = std::make_unique<pa_error_op>();
+    e->ms = make_mixed_sub(geom, *restr1, *basis1, *restr2, *basis2, qfunction, ctx, ctx_size);
+    *out = e.release();
   });
 }
 
@@ -915,14 +866,9 @@ int pa_error_op_create_tensor(pa_geom *geom, const pa_restriction_desc *restr1, 
     require_device();
     PA_REQUIRE(geom && restr1 && basis1 && restr2 && basis2 && out, "null argument");
     PA_REQUIRE(qfunction == PA_QF_HCURLHDIV_ERROR_33 || qfunction == PA_QF_HDIVHCURL_ERROR_33, "not an error QFunction");
-    auto *e = new pa_error_op;
-    try {
-      e->ms = make_mixed_hex_sub(geom, *restr1, *basis1, *restr2, *basis2, qfunction, ctx, ctx_size);
-    } catch (...) {
-      delete e;
-      throw;
-    }
-    *out = e;
+    auto e = std::make_unique<pa_error_op>();
+    e->ms = make_mixed_hex_sub(geom, *restr1, *basis1, *restr2, *basis2, qfunction, ctx, ctx_size);
+    *out = e.release();
   });
 }
 
@@ -945,11 +891,7 @@ int pa_error_op_two_parts(const pa_error_op *e) { return (e && e->ms && mixed_he
 
 int pa_error_op_num_elem(const pa_error_op *e) { return (e && e->ms) ? e->ms->ne : -1; }
 
-void pa_error_op_destroy(pa_error_op *e) {
-  if (!e) return;
-  free_mixed_sub(e->ms);
-  delete e;
-}
+void pa_error_op_destroy(pa_error_op *e) { delete e; }
 
 // Weighted sum of H(curl) integrators on one (geometry, space) pair as ONE sub-operator: D is linear in the material
 // coefficient, so sum_k a_k {K(mu^-1), M(eps), C(sigma), ...} is a single curl-curl + mass pass whose two contexts are
@@ -1084,25 +1026,19 @@ int pa_op_coarsen(const pa_op *fine, const pa_restriction_desc *restr, const pa_
   return guarded([&] {
     PA_REQUIRE(fine && restr && basis && coarse, "null argument");
     PA_REQUIRE(!fine->subs.empty(), "fine operator has no sub-operators");
-    auto *o = new pa_op;
+    auto o = std::make_unique<pa_op>();
     o->id = next_op_id();
     o->height = o->width = restr->lsize;
-    try {
-      for (const SubOp *fs : fine->subs) {
-        PA_REQUIRE(fs->fe_type != PA_FE_HDIV && basis->fe_type != PA_FE_HDIV,
-                   "p-coarsening is built for H(curl) and H1 hexahedra: an H(div) operator is assembled at its own order");
-        PA_REQUIRE(fs->ne == restr->num_elem, "coarsening needs one element block (same elements)");
-        o->subs.push_back(make_sub(static_cast<pa_geom *>(fs->geom), *restr, *basis, fs->qf,
-                                   fs->ctx_blob.data(), fs->ctx_blob.size(), fs->trial_ops,
-                                   fs->test_ops, fs->qd));
-      }
-    } catch (...) {
-      pa_op_destroy(o);
-      throw;
+    for (const auto &fs : fine->subs) {
+      PA_REQUIRE(fs->fe_type != PA_FE_HDIV && basis->fe_type != PA_FE_HDIV,
+                 "p-coarsening is built for H(curl) and H1 hexahedra: an H(div) operator is assembled at its own order");
+      PA_REQUIRE(fs->ne == restr->num_elem, "coarsening needs one element block (same elements)");
+      o->subs.push_back(make_sub(static_cast<pa_geom *>(fs->geom.get()), *restr, *basis, fs->qf, fs->ctx_blob.data(),
+                                 fs->ctx_blob.size(), fs->trial_ops, fs->test_ops, fs->qd));
     }
-    finalize_exclusive(o);
+    finalize_exclusive(o.get());
     o->finalized = true;
-    *coarse = o;
+    *coarse = o.release();
   });
 }
 
@@ -1111,19 +1047,14 @@ int pa_op_coarsen_dense(const pa_op *fine, const pa_restriction_desc *restr, con
   return guarded([&] {
     PA_REQUIRE(fine && restr && basis && coarse, "null argument");
     PA_REQUIRE(fine->finalized && fine->subs.empty() && !fine->dsubs.empty(), "fine operator has no dense sub-operators");
-    auto *o = new pa_op;
+    auto o = std::make_unique<pa_op>();
     o->id = next_op_id();
     o->height = o->width = restr->lsize;
-    try {
-      for (const DenseSub *fs : fine->dsubs)
-        o->dsubs.push_back(make_dense_sub(static_cast<pa_geom *>(fs->geom), *restr, *basis, fs->qf, fs->ctx_blob.data(),
-                                          fs->ctx_blob.size(), fs->trial_ops, fs->test_ops, o->height, fs->contra));
-    } catch (...) {
-      pa_op_destroy(o);
-      throw;
-    }
+    for (const auto &fs : fine->dsubs)
+      o->dsubs.push_back(make_dense_sub(static_cast<pa_geom *>(fs->geom.get()), *restr, *basis, fs->qf, fs->ctx_blob.data(),
+                                        fs->ctx_blob.size(), fs->trial_ops, fs->test_ops, o->height, fs->contra));
     o->finalized = true;
-    *coarse = o;
+    *coarse = o.release();
   });
 }
 
@@ -1187,7 +1118,7 @@ int pa_op_mult_complex(pa_op *op_r, pa_op *op_i, const double *xr, const double 
     const bool masked = ess_policy >= 0;
     hipStream_t s = (hipStream_t)stream;
     if (kind == 2) {  // dense tables (tetrahedra, ...)
-      DenseSub *dr = op_r->dsubs[0];
+      DenseSub *dr = op_r->dsubs[0].get();
       // ParOperator's essential dofs (round 5): entries read as zero through the flagged index copy of the REAL operator, rows
       // fixed by the two gathers -- yr[ess] = xr[ess] | 0, yi[ess] = xi[ess] | 0 (rap.cpp:450-457 on one rank, as the hex form)
       PA_REQUIRE(!masked || (op_r->has_essential && dr->d_idx_bc && dr->d_ess_flag),
@@ -1197,7 +1128,7 @@ int pa_op_mult_complex(pa_op *op_r, pa_op *op_i, const double *xr, const double 
       launch_dense_gather(*dr, yr, false, s, nullptr, nullptr, masked ? xr : nullptr, ess_policy);
       launch_dense_gather(*dr, yi, false, s, dr->d_ye2, nullptr, masked ? xi : nullptr, ess_policy);
     } else {
-      SubOp *sr = op_r->subs[0];
+      SubOp *sr = op_r->subs[0].get();
       PA_REQUIRE(!masked || (op_r->has_essential && sr->stream[kStreamMasked].ready()), "pa_op_set_essential has not been called on the real operator");
       if (!sr->d_ye2) sr->d_ye2 = dev_alloc<double>((size_t)((sr->ne + 3) & ~3) * sr->P);
       if (sr->qd->metric) stream_element_coefficients(*op_i->subs[0]);
@@ -1228,7 +1159,7 @@ int pa_op_is_symmetric(const pa_op *op) { return (op && op->symmetric()) ? 1 : 0
 int pa_op_dense_affine(const pa_op *op) {
   int n = 0;
   if (op)
-    for (const DenseSub *ds : op->dsubs) n += ds->d_affine ? 1 : 0;
+    for (const auto &ds : op->dsubs) n += ds->d_affine ? 1 : 0;
   return n;
 }
 int pa_op_streams(const pa_op *op) {
@@ -1259,29 +1190,26 @@ int pa_op_set_essential(pa_op *op, const int32_t *ess, int32_t n) {
       PA_REQUIRE(ess[i] >= 0 && ess[i] < op->width, "essential dof out of range");
       flag[ess[i]] = 1;
     }
-    for (SubOp *so : op->subs) {
+    for (const auto &so : op->subs) {
       std::vector<int32_t> bc(so->h_sidx);
       for (auto &s : bc) {
         const int d = s >= 0 ? s : -1 - s;
         if (flag[d]) s = s >= 0 ? (d | kEssBit) : -1 - (d | kEssBit);
       }
-      hipFree(so->d_sidx_bc);
       so->d_sidx_bc = dev_upload(bc.data(), bc.size());
     }
-    for (DenseSub *ds : op->dsubs) dense_set_essential(*ds, flag);
-    for (SubOp *so : op->subs) {
+    for (const auto &ds : op->dsubs) dense_set_essential(*ds, flag);
+    for (const auto &so : op->subs) {
       if (so->d_shared) {  // flagged copy of the gather list: essential rows are fixed up inside the gather kernel
         std::vector<int32_t> lb(so->h_shared);
         for (auto &d : lb)
           if (flag[d]) d |= kEssBit;
-        hipFree(so->d_shared_bc);
         so->d_shared_bc = dev_upload(lb.data(), lb.size());
       }
       if (so->d_idxc) stream_set_essential(*so, flag);
       if (so->fe_type == PA_FE_HDIV) {  // every dof goes through the gather: its list with the essential rows flagged
         std::vector<int32_t> lb((size_t)so->lsize);
         for (int d = 0; d < so->lsize; d++) lb[d] = flag[d] ? (d | kEssBit) : d;
-        hipFree(so->d_shared_bc);
         so->d_shared_bc = dev_upload(lb.data(), lb.size());
       }
     }
@@ -1308,7 +1236,7 @@ int pa_op_mult_essential_diag(pa_op *op, const double *x, double *y, int diag_po
       *handled = 1;
       return;
     }
-    const SubOp *s0 = op->subs.size() == 1 ? op->subs[0] : nullptr;
+    const SubOp *s0 = op->subs.size() == 1 ? op->subs[0].get() : nullptr;
     const bool fuse = s0 && op->dsubs.empty() && op->msubs.empty() &&
                       (s0->fe_type == PA_FE_HCURL  ? nd_hex_fuses_essential(*s0)
                        : s0->fe_type == PA_FE_HDIV ? s0->d_shared_bc != nullptr  // (the plain gather over the flagged dof list)
@@ -1373,7 +1301,7 @@ int pa_op_prepare_fused_step(pa_op *op, int *available) {
       return;
     }
     if (op->subs.size() != 1 || !op->dsubs.empty()) return;
-    SubOp *so = op->subs[0];
+    SubOp *so = op->subs[0].get();
     // (four points per direction: pa_nd_hex_stream.hip; five: pa_nd_hex_stream5.hip; three, where PALACE_AMD_STREAM3=1 built the
     // tables: pa_nd_hex_stream3.hip -- nd_hex_stream_ok covers them all; H1 blocks whose y = A x runs on the streaming kernel:
     // pa_h1_hex_stream.hip)
@@ -1474,13 +1402,13 @@ int pa_op_mult_split(pa_op *op, const double *x, const double *xg0, const double
     hipStream_t s = (hipStream_t)stream;
     if (!op->dsubs.empty()) {  // dense-table block: the essential entries are flagged in the masked index copy, the rows are
                                // fixed by its gather
-      DenseSub *ds = op->dsubs[0];
+      DenseSub *ds = op->dsubs[0].get();
       PA_REQUIRE(!masked || op->has_essential, "pa_op_set_essential has not been called");
       launch_dense_apply(*ds, x, masked, s, &io);
       launch_dense_gather(*ds, y, false, s, nullptr, &io, x, ess_policy);
       return;
     }
-    SubOp *so = op->subs[0];
+    SubOp *so = op->subs[0].get();
     PA_REQUIRE(!masked || (op->has_essential && so->stream[kStreamMasked].ready()), "pa_op_set_essential has not been called");
     launch_nd_hex_stream(*so, x, y, stream_form(masked), s, &io);
     launch_et_run_gather(*so, y, false, s, x, stream_form(masked), ess_policy, nullptr, &io);
@@ -1532,7 +1460,7 @@ int pa_op_assemble_diagonal(pa_op *op, double *diag, void *stream) {
     PA_REQUIRE(op && diag, "null argument");
     PA_REQUIRE(op->msubs.empty(), "mixed-space operators have no diagonal");
     PA_HIP(hipMemsetAsync(diag, 0, sizeof(double) * (size_t)op->height, (hipStream_t)stream));
-    for (const SubOp *so : op->subs) {
+    for (const auto &so : op->subs) {
       if (so->fe_type == PA_FE_HCURL)
         launch_nd_hex_diag(*so, diag, (hipStream_t)stream);
       else if (so->fe_type == PA_FE_HDIV)
@@ -1540,7 +1468,7 @@ int pa_op_assemble_diagonal(pa_op *op, double *diag, void *stream) {
       else
         launch_h1_hex_diag(*so, diag, (hipStream_t)stream);
     }
-    for (const DenseSub *ds : op->dsubs) launch_dense_diag(*ds, diag, (hipStream_t)stream);
+    for (const auto &ds : op->dsubs) launch_dense_diag(*ds, diag, (hipStream_t)stream);
   });
 }
 
@@ -1548,7 +1476,7 @@ int pa_op_stream_affine(const pa_op *op, int32_t out[3]) {
   return guarded([&] {
     PA_REQUIRE(op && out, "null argument");
     out[0] = out[1] = out[2] = 0;
-    for (const SubOp *so : op->subs)
+    for (const auto &so : op->subs)
       if (so->fe_type == PA_FE_HCURL && so->qd) {
         out[0] = so->ne, out[1] = so->qd->n_aff_elems, out[2] = so->qd->d_aff ? so->qd->n_aff_batch_elems : 0;
         return;
@@ -1559,7 +1487,7 @@ int pa_op_stream_column(const pa_op *op, int32_t out[3]) {
   return guarded([&] {
     PA_REQUIRE(op && out, "null argument");
     out[0] = out[1] = out[2] = 0;
-    for (const SubOp *so : op->subs)
+    for (const auto &so : op->subs)
       if (so->fe_type == PA_FE_HCURL && so->qd) {
         out[0] = so->ne, out[1] = so->qd->n_col_elems, out[2] = so->qd->d_col ? so->qd->n_col_batch_elems : 0;
         return;
@@ -1584,7 +1512,7 @@ double pa_op_algorithmic_bytes(const pa_op *op) {
   if (!op) return 0.0;
   double bytes = 0.0;
   // (o = 1 orientation byte per entry for the oriented restriction of H(curl) blocks, none for H1: SURVEY.md 8d)
-  for (const SubOp *so : op->subs) {
+  for (const auto &so : op->subs) {
     if (so->fe_type == PA_FE_HDIV) {
       // what pa_rt_hex.hip streams per element: the packed D rows (6 mass + 1 divergence), or of the geometry rows {attr, w detJ}
       // and, with a mass term, the nine of adj(J)^T / detJ; per entry the sorted index (4 B) and its tensor-order slot (2 B)
@@ -1595,21 +1523,13 @@ double pa_op_algorithmic_bytes(const pa_op *op) {
     }
     bytes += (double)so->ne * ((double)so->Q * 11 * 8 + (double)so->P * (so->fe_type == PA_FE_H1 ? 4 : 5));
   }
-  for (const DenseSub *ds : op->dsubs)  // o = 3 for the curl-oriented restriction; G = 11 (3-D) or 6 (2-D)
+  for (const auto &ds : op->dsubs)  // o = 3 for the curl-oriented restriction; G = 11 (3-D) or 6 (2-D)
     bytes += (double)ds->ne * ((double)ds->Q * ds->geom->nrows * 8 + (double)ds->P * (ds->d_co ? 7 : 5));
-  for (const MixedSub *ms : op->msubs)  // tensor-product two-space blocks (pa_mixed_hex.hip): the 11 geometry rows, 6 B per entry of both sides
+  for (const auto &ms : op->msubs)  // tensor-product two-space blocks (pa_mixed_hex.hip): the 11 geometry rows, 6 B per entry of both sides
     if (ms->hex1) bytes += (double)ms->ne * ((double)ms->Q * 11 * 8 + (double)(ms->hex1->P + ms->hex2->P) * 6);
   return bytes + 8.0 * op->height + 8.0 * op->width;  // y and x
 }
 
-void pa_op_destroy(pa_op *op) {
-  if (!op) return;
-  for (SubOp *so : op->subs) free_sub(so);
-  for (DenseSub *ds : op->dsubs) free_dense_sub(ds);
-  for (MixedSub *ms : op->msubs) free_mixed_sub(ms);
-  (void)hipFree(op->d_t_extra), (void)hipFree(op->d_extra_rows);
-  (void)hipFree(op->d_urow_ptr), (void)hipFree(op->d_uent), (void)hipFree(op->d_ublk);
-  delete op;
-}
+void pa_op_destroy(pa_op *op) { delete op; }
 
 }  // extern "C"

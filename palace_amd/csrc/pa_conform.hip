@@ -188,29 +188,17 @@ Conforming::Conforming(const Context &ctx, int n_true, int n_local, const int *r
       t_slave[at] = r, t_val[at] = val[k];
     }
   const int zero = 0;
-  try {  // (a constructor that throws runs no destructor: what was uploaded before a failing upload is released here)
-    d_row_ptr_ = pa::dev_upload(n_con_ ? row_ptr : &zero, (size_t)n_con_ + 1, ctx.stream);
-    d_col_ = pa::dev_upload(col, (size_t)nnz, ctx.stream);
-    d_val_ = pa::dev_upload(val, (size_t)nnz, ctx.stream);
-    d_t_ptr_ = pa::dev_upload(t_ptr.data(), t_ptr.size(), ctx.stream);
-    d_t_dof_ = pa::dev_upload(t_dof.data(), t_dof.size(), ctx.stream);
-    d_t_slave_ = pa::dev_upload(t_slave.data(), t_slave.size(), ctx.stream);
-    d_t_val_ = pa::dev_upload(t_val.data(), t_val.size(), ctx.stream);
-    d_touched_ = pa::dev_upload(touched.data(), touched.size(), ctx.stream);
-  } catch (...) {
-    Free();
-    throw;
-  }
+  d_row_ptr_ = pa::dev_upload(n_con_ ? row_ptr : &zero, (size_t)n_con_ + 1, ctx.stream);
+  d_col_ = pa::dev_upload(col, (size_t)nnz, ctx.stream);
+  d_val_ = pa::dev_upload(val, (size_t)nnz, ctx.stream);
+  d_t_ptr_ = pa::dev_upload(t_ptr.data(), t_ptr.size(), ctx.stream);
+  d_t_dof_ = pa::dev_upload(t_dof.data(), t_dof.size(), ctx.stream);
+  d_t_slave_ = pa::dev_upload(t_slave.data(), t_slave.size(), ctx.stream);
+  d_t_val_ = pa::dev_upload(t_val.data(), t_val.size(), ctx.stream);
+  d_touched_ = pa::dev_upload(touched.data(), touched.size(), ctx.stream);
 }
 
-void Conforming::Free() {
-  for (void *p : {(void *)d_row_ptr_, (void *)d_col_, (void *)d_val_, (void *)d_t_ptr_, (void *)d_t_dof_, (void *)d_t_slave_,
-                  (void *)d_t_val_, (void *)d_touched_})
-    if (p) (void)hipFree(p);
-  d_row_ptr_ = d_t_ptr_ = nullptr, d_col_ = d_t_dof_ = d_t_slave_ = nullptr, d_val_ = d_t_val_ = nullptr, d_touched_ = nullptr;
-}
-
-Conforming::~Conforming() { Free(); }
+Conforming::~Conforming() = default;
 
 void Conforming::Prolongate(const double *x, double *lx, const uint8_t *ess_mask, hipStream_t stream) const {
   if (n_true_ + n_con_ == 0) return;

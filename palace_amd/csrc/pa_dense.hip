@@ -1374,11 +1374,11 @@ void launch_geom_dense(const pa_mesh_dense_desc &mesh, Geom &g, hipStream_t s) {
   for (size_t i = 0; i < (size_t)ne * npe; i++)
     PA_REQUIRE(mesh.node_offsets[i] >= 0 && mesh.node_offsets[i] < mesh.num_nodes, "mesh node id out of range");
   for (int e = 0; e < ne; e++) PA_REQUIRE(mesh.attr[e] >= 1, "element attributes are 1-based");
-  int32_t *d_off = dev_upload(mesh.node_offsets, (size_t)ne * npe, s);
-  double *d_nodes = dev_upload(mesh.nodes, (size_t)mesh.num_nodes * sdim, s);
-  int32_t *d_attr = dev_upload(mesh.attr, (size_t)ne, s);
-  double *d_grad = dev_upload(mesh.mesh_grad, (size_t)dim * Q * npe, s);
-  double *d_w = dev_upload(mesh.qweight, (size_t)Q, s);
+  const DevBuf<int32_t> b_off = dev_upload(mesh.node_offsets, (size_t)ne * npe, s), b_attr = dev_upload(mesh.attr, (size_t)ne, s);
+  const DevBuf<double> b_nodes = dev_upload(mesh.nodes, (size_t)mesh.num_nodes * sdim, s),
+                       b_grad = dev_upload(mesh.mesh_grad, (size_t)dim * Q * npe, s), b_w = dev_upload(mesh.qweight, (size_t)Q, s);
+  const int32_t *d_off = b_off, *d_attr = b_attr;
+  const double *d_nodes = b_nodes, *d_grad = b_grad, *d_w = b_w;
   g.ne = ne, g.q1d = 0, g.Q = Q, g.eb = kEB, g.Qpad = (Q + 15) / 16 * 16;
   g.dim = dim, g.sdim = sdim, g.nrows = dim == 1 ? 2 + sdim : (dim == 3 ? 11 : (sdim == 3 ? 8 : 6));
   g.d_qw = dev_upload(mesh.qweight, (size_t)Q, s);
@@ -1390,26 +1390,26 @@ void launch_geom_dense(const pa_mesh_dense_desc &mesh, Geom &g, hipStream_t s) {
   const int bs = 256;
   if (dim == 1 && sdim == 3)
     hipLaunchKernelGGL(geom_dense1_kernel<3>, dim3((unsigned)((n + bs - 1) / bs)), dim3(bs), 0, s, ne, Q, g.Qpad, npe, d_off,
-                       d_nodes, d_attr, d_grad, d_w, g.d_geom);
+                       d_nodes, d_attr, d_grad, d_w, g.d_geom.get());
   else if (dim == 1)
     hipLaunchKernelGGL(geom_dense1_kernel<2>, dim3((unsigned)((n + bs - 1) / bs)), dim3(bs), 0, s, ne, Q, g.Qpad, npe, d_off,
-                       d_nodes, d_attr, d_grad, d_w, g.d_geom);
+                       d_nodes, d_attr, d_grad, d_w, g.d_geom.get());
   else if (dim == 2 && sdim == 3)
     hipLaunchKernelGGL(geom_dense32_kernel, dim3((unsigned)((n + bs - 1) / bs)), dim3(bs), 0, s, ne, Q, g.Qpad, npe, d_off,
-                       d_nodes, d_attr, d_grad, d_w, g.d_geom);
+                       d_nodes, d_attr, d_grad, d_w, g.d_geom.get());
   else if (dim == 2)
     hipLaunchKernelGGL(geom_dense2_kernel, dim3((unsigned)((n + bs - 1) / bs)), dim3(bs), 0, s, ne, Q, g.Qpad, npe, d_off,
-                       d_nodes, d_attr, d_grad, d_w, g.d_geom);
+                       d_nodes, d_attr, d_grad, d_w, g.d_geom.get());
   else
     hipLaunchKernelGGL(geom_dense_kernel, dim3((unsigned)((n + bs - 1) / bs)), dim3(bs), 0, s, ne, Q, g.Qpad, npe, d_off,
-                       d_nodes, d_attr, d_grad, d_w, g.d_geom);
+                       d_nodes, d_attr, d_grad, d_w, g.d_geom.get());
   PA_HIP(hipGetLastError());
   PA_HIP(hipStreamSynchronize(s));
-  hipFree(d_off), hipFree(d_nodes), hipFree(d_attr), hipFree(d_grad), hipFree(d_w);
 }
 
-DenseSub *make_dense_sub(pa_geom *geom, const pa_restriction_desc &r, const pa_dense_basis_desc &b, int qf,
-                         const void *ctx, size_t ctx_size, uint32_t trial_ops, uint32_t test_ops, int height, bool contra) {
+std::unique_ptr<DenseSub> make_dense_sub(pa_geom *geom, const pa_restriction_desc &r, const pa_dense_basis_desc &b, int qf,
+                                         const void *ctx, size_t ctx_size, uint32_t trial_ops, uint32_t test_ops, int height,
+                                         bool contra) {
   PA_REQUIRE(geom && geom->eb == kEB, "geometry data must come from pa_geom_create_dense");
   if (b.fe_type == PA_FE_HDIV) {
     // H(div) elements run on the arithmetic of an existing mode: the tables change places, the D of the values takes the
@@ -1497,9 +1497,8 @@ DenseSub *make_dense_sub(pa_geom *geom, const pa_restriction_desc &r, const pa_d
     }
   PA_REQUIRE(PT > 0, "element has more than 144 dofs: not instantiated");
 
-  auto *ds = new DenseSub;
-  ds->geom = geom;
-  geom->refcount++;
+  auto ds = std::make_unique<DenseSub>();
+  ds->geom = Ref<Geom>(geom);
   ds->fe_type = b.fe_type, ds->P = P, ds->Q = Q, ds->Qpad = geom->Qpad, ds->nch = geom->Qpad / 16;
   ds->ne = ne, ds->nb = (ne + kEB - 1) / kEB, ds->lsize = r.lsize, ds->KP = 4 * PT, ds->PT = PT;
   ds->qf = qf, ds->mode = mode, ds->trial_ops = trial_ops, ds->test_ops = test_ops, ds->contra = contra;
@@ -1572,9 +1571,8 @@ DenseSub *make_dense_sub(pa_geom *geom, const pa_restriction_desc &r, const pa_d
       double t[2];
       for (int rows = 0; rows < 2; rows++) {
         fill_tent(rows != 0);
-        int32_t *d_t = dev_upload(tent.data(), tent.size());
+        const DevBuf<int32_t> d_t = dev_upload(tent.data(), tent.size());
         t[rows] = time_dense_gather(*ds, d_t);
-        (void)hipFree(d_t);
       }
       ds->ye_rows = t[1] < 0.85 * t[0];
       if (getenv("PALACE_AMD_DENSE_VERBOSE"))
@@ -1792,14 +1790,13 @@ DenseSub *make_dense_sub(pa_geom *geom, const pa_restriction_desc &r, const pa_d
       if (!(aff_env && aff_env[0] == '0') && PT <= 3 && lds_aff <= 160 * 1024 && (int)geom->wq.size() == Q && Q > 1 &&
           geom->wq[0] != 0.0) {
         const int Q4 = (Q + 3) / 4 * 4;
-        unsigned int *d_na = dev_alloc<unsigned int>((size_t)nb);
+        const DevBuf<unsigned int> d_na = dev_alloc<unsigned int>((size_t)nb);
         PA_HIP(hipMemset(d_na, 0, sizeof(unsigned int) * nb));
         hipLaunchKernelGGL(dense_affine_kernel, dim3((unsigned)((nb * kEB + 255) / 256)), dim3(256), 0, nullptr, nb, ds->ncq, Q,
                            Q4, ds->d_qdata, geom->d_qw, d_na);
         PA_HIP(hipGetLastError());
         std::vector<unsigned int> na((size_t)nb);
         PA_HIP(hipMemcpy(na.data(), d_na, sizeof(unsigned int) * nb, hipMemcpyDeviceToHost));
-        hipFree(d_na);
         std::vector<uint8_t> flag((size_t)nb);
         for (int i = 0; i < nb; i++) flag[i] = na[i] ? 0 : 1, ds->n_affine += flag[i];
         if (ds->n_affine < nb && ds->n_affine * 4 >= nb) {  // a mesh with curved parts: the affine blocks get the affine kernel
@@ -1821,20 +1818,6 @@ DenseSub *make_dense_sub(pa_geom *geom, const pa_restriction_desc &r, const pa_d
   return ds;
 }
 
-void free_dense_sub(DenseSub *ds) {
-  if (ds) hipFree(ds->d_affine), hipFree(ds->d_wrel), hipFree(ds->d_ye2), hipFree(ds->d_blist[0]), hipFree(ds->d_blist[1]);
-  if (!ds) return;
-  hipFree(ds->d_idx), hipFree(ds->d_idx_bc), hipFree(ds->d_co), hipFree(ds->d_co2), hipFree(ds->d_ess_flag), hipFree(ds->d_rows);
-  hipFree(ds->d_Tf), hipFree(ds->d_Tt), hipFree(ds->d_interp), hipFree(ds->d_deriv);
-  hipFree(ds->d_L), hipFree(ds->d_qdata);
-  hipFree(ds->d_off), hipFree(ds->d_cor), hipFree(ds->d_ori);
-  hipFree(ds->d_ye), hipFree(ds->d_tptr), hipFree(ds->d_tent);
-  hipFree(ds->c0.d_attr_mat), hipFree(ds->c0.d_mat), hipFree(ds->c0.d_mat_t);
-  hipFree(ds->c1.d_attr_mat), hipFree(ds->c1.d_mat), hipFree(ds->c1.d_mat_t);
-  pa_geom_destroy(static_cast<pa_geom *>(ds->geom));
-  delete ds;
-}
-
 void dense_set_essential(DenseSub &ds, const std::vector<char> &flag) {
   std::vector<int32_t> bc(ds.h_idx);
   for (auto &s : bc) {
@@ -1842,11 +1825,9 @@ void dense_set_essential(DenseSub &ds, const std::vector<char> &flag) {
     if (d & kEssBit) continue;  // padding
     if (flag[d]) s = s >= 0 ? (d | kEssBit) : -1 - (d | kEssBit);
   }
-  hipFree(ds.d_idx_bc);
   ds.d_idx_bc = dev_upload(bc.data(), bc.size());
   std::vector<uint8_t> ef((size_t)ds.lsize, 0);
   for (int d = 0; d < ds.lsize && d < (int)flag.size(); d++) ef[d] = flag[d] ? 1 : 0;
-  hipFree(ds.d_ess_flag);
   ds.d_ess_flag = dev_upload(ef.data(), ef.size());
 }
 
@@ -2150,41 +2131,38 @@ int gather_group(long long nnz, int n) {
 int dense_gather_group(const DenseSub &ds) { return gather_group((long long)ds.ne * ds.P, ds.lsize); }
 template <bool STEP>
 void launch_gather_split(const DenseSub &ds, const double *ye, double *y, double *yg, int nsplit, const double *x, int ess_policy,
-                         const GatherStep &st, hipStream_t s) {
+                         const GatherStep &st, hipStream_t s, const int32_t *tent = nullptr) {
+  if (!tent) tent = ds.d_tent;  // (else: a map under test, time_dense_gather)
   const int G = gather_group((long long)ds.ne * ds.P, ds.lsize);
   const unsigned nb = (unsigned)(((long long)ds.lsize * G + 255) / 256);
 #define PA_GATHER_GROUP(GG)                                                                                                         \
-  hipLaunchKernelGGL((et_gather_group_kernel<STEP, GG>), dim3(nb), dim3(256), 0, s, ds.lsize, ds.d_tptr, ds.d_tent, ye, y, yg, nsplit, \
+  hipLaunchKernelGGL((et_gather_group_kernel<STEP, GG>), dim3(nb), dim3(256), 0, s, ds.lsize, ds.d_tptr, tent, ye, y, yg, nsplit, \
                      ds.d_ess_flag, x, ess_policy, st)
   if (G == 8) PA_GATHER_GROUP(8);
   else if (G == 4) PA_GATHER_GROUP(4);
   else if (G == 2) PA_GATHER_GROUP(2);
   else
-    hipLaunchKernelGGL((et_gather_split_kernel_t<STEP, 1>), dim3(nb), dim3(256), 0, s, ds.lsize, ds.d_tptr, ds.d_tent, ye, y, yg, nsplit,
+    hipLaunchKernelGGL((et_gather_split_kernel_t<STEP, 1>), dim3(nb), dim3(256), 0, s, ds.lsize, ds.d_tptr, tent, ye, y, yg, nsplit,
                        ds.d_ess_flag, x, ess_policy, st);
 #undef PA_GATHER_GROUP
 }
 
 double time_dense_gather(const DenseSub &ds, const int32_t *d_tent) {
-  DenseSub probe;  // (only what launch_gather_split reads: sizes and the map under test; nothing of it is freed here)
-  probe.ne = ds.ne, probe.P = ds.P, probe.lsize = ds.lsize, probe.d_tptr = ds.d_tptr;
-  probe.d_tent = const_cast<int32_t *>(d_tent);
-  double *y = dev_alloc<double>((size_t)ds.lsize);
+  const DevBuf<double> y = dev_alloc<double>((size_t)ds.lsize);
   hipEvent_t e0, e1;
   PA_HIP(hipEventCreate(&e0));
   PA_HIP(hipEventCreate(&e1));
   const int reps = 5;
   for (int it = 0; it < 2; it++)
-    launch_gather_split<false>(probe, ds.d_ye, y, y, 0x7fffffff, nullptr, -1, GatherStep{}, nullptr);
+    launch_gather_split<false>(ds, ds.d_ye, y, y, 0x7fffffff, nullptr, -1, GatherStep{}, nullptr, d_tent);
   PA_HIP(hipEventRecord(e0, nullptr));
   for (int it = 0; it < reps; it++)
-    launch_gather_split<false>(probe, ds.d_ye, y, y, 0x7fffffff, nullptr, -1, GatherStep{}, nullptr);
+    launch_gather_split<false>(ds, ds.d_ye, y, y, 0x7fffffff, nullptr, -1, GatherStep{}, nullptr, d_tent);
   PA_HIP(hipEventRecord(e1, nullptr));
   PA_HIP(hipEventSynchronize(e1));
   float ms = 0.f;
   PA_HIP(hipEventElapsedTime(&ms, e0, e1));
   (void)hipEventDestroy(e0), (void)hipEventDestroy(e1);
-  (void)hipFree(y);
   return ms / reps;
 }
 
@@ -2285,7 +2263,7 @@ void launch_dense_diag(const DenseSub &ds, double *diag_out, hipStream_t s) {
   DenseArgs a = make_args(ds);
   const long long n = (long long)ds.ne * ds.P;
   const dim3 grid((unsigned)((n + 255) / 256)), block(256);
-  double *diag = dev_alloc<double>((size_t)n);  // element diagonals [ne][P] (set-up path: allocated per call)
+  const DevBuf<double> diag = dev_alloc<double>((size_t)n);  // element diagonals [ne][P] (set-up path: allocated per call)
   if (ds.geom->dim == 3 && ds.mode < MODE_CURL2 && !ds.contra) switch (ds.mode) {
 #define PA_DIAG_CASE(MODE)                                                                                   \
   case MODE:                                                                                                 \
@@ -2324,7 +2302,6 @@ void launch_dense_diag(const DenseSub &ds, double *diag_out, hipStream_t s) {
   PA_HIP(hipGetLastError());
   launch_et_gather_raw(ds.lsize, ds.d_tptr, ds.d_tent, ds.d_ye, diag_out, true, s);
   PA_HIP(hipStreamSynchronize(s));
-  PA_HIP(hipFree(diag));
 }
 
 }  // namespace pa

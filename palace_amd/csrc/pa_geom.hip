@@ -120,21 +120,20 @@ void launch_geom(const pa_mesh_desc &mesh, Geom &g, hipStream_t s) {
     std::copy(mesh.node_offsets + (size_t)eo * npe, mesh.node_offsets + (size_t)(eo + 1) * npe, off.begin() + (size_t)e * npe);
     attr[e] = mesh.attr[eo];
   }
-  int32_t *d_off = dev_upload(off.data(), (size_t)ne * npe, s);
-  double *d_nodes = dev_upload(mesh.nodes, (size_t)mesh.num_nodes * 3, s);
-  int32_t *d_attr = dev_upload(attr.data(), (size_t)ne, s);
-  double *d_B = dev_upload(mesh.mesh_B, (size_t)q1d * m1, s);
-  double *d_G = dev_upload(mesh.mesh_G, (size_t)q1d * m1, s);
-  double *d_w = dev_upload(mesh.qweight1d, (size_t)q1d, s);
+  const DevBuf<int32_t> d_off = dev_upload(off.data(), (size_t)ne * npe, s);
+  const DevBuf<double> d_nodes = dev_upload(mesh.nodes, (size_t)mesh.num_nodes * 3, s);
+  g.d_attr_e = dev_upload(attr.data(), (size_t)ne, s);
+  const DevBuf<double> d_B = dev_upload(mesh.mesh_B, (size_t)q1d * m1, s);
+  const DevBuf<double> d_G = dev_upload(mesh.mesh_G, (size_t)q1d * m1, s);
+  const DevBuf<double> d_w = dev_upload(mesh.qweight1d, (size_t)q1d, s);
   g.ne = ne, g.q1d = q1d, g.Q = Q;
   g.d_geom = dev_alloc<double>((size_t)ne * 11 * Q);
   const long long n = (long long)ne * Q;
   const int bs = 256;
   hipLaunchKernelGGL(geom_factor_kernel, dim3((unsigned)((n + bs - 1) / bs)), dim3(bs), 0, s, ne,
-                     q1d, m1, d_off, d_nodes, d_attr, d_B, d_G, d_w, g.d_geom);
+                     q1d, m1, d_off.get(), d_nodes.get(), g.d_attr_e.get(), d_B.get(), d_G.get(), d_w.get(), g.d_geom.get());
   PA_HIP(hipGetLastError());
   PA_HIP(hipStreamSynchronize(s));
-  hipFree(d_off), hipFree(d_nodes), hipFree(d_B), hipFree(d_G), hipFree(d_w);
   if (m1 == 3 && q1d == 4) {  // what the GEOMN form of the streaming kernel reads instead of packed q-data: 648 B per element
     const size_t nep = (size_t)((ne + 3) & ~3);
     std::vector<double> xn(nep * 81, 0.0);
@@ -154,7 +153,6 @@ void launch_geom(const pa_mesh_desc &mesh, Geom &g, hipStream_t s) {
     g.d_gtab = dev_upload(gt.data(), gt.size(), s);
     PA_HIP(hipStreamSynchronize(s));
   }
-  g.d_attr_e = d_attr;
   g.h_attr = attr;
   g.w1.assign(mesh.qweight1d, mesh.qweight1d + q1d);
 }

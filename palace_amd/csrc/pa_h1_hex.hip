@@ -352,7 +352,7 @@ void launch_h1_hex_qdata(SubOp &so, hipStream_t s) {
   bool use_v, use_g;
   CoeffDev cm, cd;
   h1_terms(so, use_v, use_g, cm, cd);
-  auto *qd = new QData;
+  const Ref<QData> qd(new QData);
   qd->ncomp = (int)use_v + 6 * (int)use_g;
   {  // padded to whole batches of four elements (the streaming kernel reads them), pad = 0
     const size_t nq = (size_t)((so.ne + 3) & ~3) * qd->ncomp * so.Q;

@@ -5,11 +5,13 @@
 
 #include <cstdint>
 #include <cstdio>
+#include <memory>
 #include <stdexcept>
 #include <string>
 #include <vector>
 
 #include "../../include/palace_amd.h"
+#include "pa_devbuf.hpp"
 #include "pa_stream_host.hpp"  // kEssBit, kExclBit
 
 struct pa_op;
@@ -21,8 +23,8 @@ struct pa_csr {
   int32_t nrows = 0;
   int32_t ncols = 0;  // 0: square
   int64_t nnz = 0;
-  int32_t *d_rowptr = nullptr, *d_col = nullptr;
-  double *d_val = nullptr;
+  pa::DevBuf<int32_t> d_rowptr, d_col;
+  pa::DevBuf<double> d_val;
 };
 
 namespace pa {
@@ -62,16 +64,8 @@ int guarded(F &&f) {
 }
 
 template <typename T>
-T *dev_alloc(size_t n) {
-  T *p = nullptr;
-  if (n == 0) n = 1;
-  PA_HIP(hipMalloc(reinterpret_cast<void **>(&p), n * sizeof(T)));
-  return p;
-}
-
-template <typename T>
-T *dev_upload(const T *host, size_t n, hipStream_t s = nullptr) {
-  T *p = dev_alloc<T>(n);
+DevBuf<T> dev_upload(const T *host, size_t n, hipStream_t s = nullptr) {
+  DevBuf<T> p = dev_alloc<T>(n);
   if (n) PA_HIP(hipMemcpyAsync(p, host, n * sizeof(T), hipMemcpyHostToDevice, s));
   PA_HIP(hipStreamSynchronize(s));
   return p;
@@ -81,7 +75,43 @@ constexpr int kExclBit16 = 1 << 15;  // flag in the slot permutation: this entry
 constexpr int kMaxP1 = 6;  // closed nodes p+1 <= 7
 constexpr int kMaxQ1 = 7;
 
-struct QData;
+// Packed symmetric pointwise operators (pre-assembled D): double[ne][ncomp][Q], the six upper
+// entries of  w detJ adj^T C adj  (mass part, if any) followed by the six of  w detJ Jl^T C Jl
+// (curl-curl part, if any).  Shared between an operator and its p-coarsened copies.
+struct QData {
+  DevBuf<double> d;
+  int ncomp = 0;
+  int refcount = 0;  // one per Ref<QData>
+  // metric form (isotropic coefficients): H = (w / |detJ|) J^T J (six entries) and |detJ| / w per point, a
+  // property of the mesh alone, shared by every operator and p-level on it.  Both pointwise operators follow
+  // from it in registers:  (w / detJ) J^T c J = c H,   w detJ adj^T c adj = c (|detJ| / w) adj(H).
+  bool metric = false;
+  // Affine elements (round 6; four points per direction, the streaming H(curl) kernel): an element whose Jacobian is constant has
+  // D(q) = w_q D_e -- 6 | 7 | 12 numbers per element instead of per point.  d_aff [ne padded to 4][2 ncomp] pairs of doubles: row
+  // 2 c + h of element e = r_c {wz(2h), wz(2h + 1)} with r_c the point-independent factor of component c and wz the 1-D weight
+  // along the lane's column (metric component 6, |detJ| / w: g {1 / wz(2h), 1 / wz(2h + 1)}); the kernel multiplies the result of
+  // the D stage by the in-plane weight w(ta) w(tb).  batch_aff[b] != 0: the four elements of batch b are all affine (the
+  // streaming kernel then reads 4 x 2 ncomp x 16 B instead of 4 x ncomp x 512 B).  The per-point data stays in place: every
+  // other consumer (one-shot kernels, diagonal, assembly, the complex forms) is unaffected.  Built once per QData by
+  // stream_affine_setup (pa_nd_hex_stream.hip) -- coarsened operators share it with the q-data.
+  DevBuf<double> d_aff;
+  std::vector<unsigned char> batch_aff;
+  bool aff_done = false;
+  int n_aff_elems = 0, n_aff_batch_elems = 0;  // affine elements found / of them in all-affine batches (compressed)
+  double wq2[2] = {0.0, 0.0};                  // the two distinct 1-D weights (symmetric four-point rule)
+  // Column-separable elements (extruded along the local zeta axis: x, y independent of zeta, z linear in it): every component
+  // factors as D_c(ta, tb, qz) = wz(qz) r_c(ta, tb) (metric component 6: r / wz(qz)), and lane (ta, tb) of the streaming kernel
+  // owns exactly the column qz = 0..3 -- one number per component and lane instead of four.  d_col [ne padded to 4][ncomp][16]
+  // doubles (+ 8 of padding: the kernel's second request of a component reads 64 bytes further, unused): r_c(t), the mean over
+  // the column of D_c / wz (component 6: of D_6 wz); the kernel multiplies it by wz(qz) (component 6: by 1 / wz(qz)) in registers
+  // ahead of its D stage.  batch_col[b] != 0: the four elements of batch b are all column-separable
+  // and the batch is not all-affine (those keep the smaller affine rows): 4 x ncomp x 128 B instead of 4 x ncomp x 512 B.
+  // Separability along the other two local axes is not looked for.  Built with the affine rows by stream_affine_setup;
+  // PALACE_AMD_STREAM_COLUMN=0 switches the form off.  The per-point data stays in place for every other consumer.
+  DevBuf<double> d_col;
+  std::vector<unsigned char> batch_col;
+  int n_col_elems = 0, n_col_batch_elems = 0;  // column-separable elements found (affine ones included) / in column batches
+};
 
 // Geometry factor data (fem/mesh.hpp:27-69): double[ne][11][Q] in HBM.
 // Dense (non-tensor) element blocks keep it element-blocked for the MFMA kernel instead:
@@ -90,19 +120,20 @@ struct Geom {
   int ne = 0, q1d = 0, Q = 0;
   int eb = 0, Qpad = 0;
   int dim = 3, sdim = 3, nrows = 11;  // 2-D blocks: 6 rows {attr, w detJ, adj(J)^T/detJ (2x2)}; boundary (2 in 3): 8 rows
-  double *d_qw = nullptr;         // quadrature weights (the q_w input of the 2-D curl-curl QFunctions)
-  double *d_geom = nullptr;
-  QData *metric = nullptr;        // lazily built G = J^T J [ne][6][Q] (tensor hex blocks), see QData
-  int32_t *d_attr_e = nullptr;    // [ne] element attributes (metric form: coefficient lookup in the kernel)
+  DevBuf<double> d_qw;            // quadrature weights (the q_w input of the 2-D curl-curl QFunctions)
+  DevBuf<double> d_geom;
+  Ref<QData> metric;              // lazily built G = J^T J [ne][6][Q] (tensor hex blocks), see QData
+  DevBuf<int32_t> d_attr_e;       // [ne] element attributes (metric form: coefficient lookup in the kernel)
   std::vector<int32_t> h_attr;    // host copy (tensor hex blocks), internal element order
   std::vector<int32_t> eorder;    // internal element p is the caller's element eorder[p] (empty: same order)
   std::vector<double> w1;         // 1-D quadrature weights (tensor hex blocks)
   // geometry from the nodes (hex27 blocks at four points per direction: the streaming curl-curl kernel's GEOMN form, round 5):
   // the 27 x 3 node coordinates of every element in internal element order, [ne padded to 4][27][3], and the 1-D geometry basis
   // at the quadrature points {B [4][3], G [4][3], weights [4]} (device)
-  double *d_xnodes = nullptr, *d_gtab = nullptr;
+  DevBuf<double> d_xnodes, d_gtab;
   std::vector<double> wq;         // quadrature weights (dense blocks), host copy
-  int refcount = 1;
+  int refcount = 1;  // the caller's handle (pa_geom_retain / pa_geom_destroy) and one per Ref<Geom>
+  virtual ~Geom() = default;  // (deleted as the pa_geom it was created as)
 };
 
 // Parsed coefficient context (coeff_qf.h layout) living in device memory.
@@ -117,10 +148,10 @@ struct CoeffHost {
   std::vector<double> mat;
   int dim = 3;
   size_t slots = 0;  // number of 8-byte slots this context occupied in the blob
-  int32_t *d_attr_mat = nullptr;
-  double *d_mat = nullptr;
-  double *d_mat_t = nullptr;  // every matrix transposed; only when some matrix is not symmetric
-  bool symmetric() const { return d_mat_t == nullptr; }
+  DevBuf<int32_t> d_attr_mat;
+  DevBuf<double> d_mat;
+  DevBuf<double> d_mat_t;  // every matrix transposed; only when some matrix is not symmetric
+  bool symmetric() const { return !d_mat_t; }
   // the device view the kernels read; inside a TransposeScope (pa_op_mult_transpose: A^T = B^T D(C^T) B for the
   // same trial / test evaluation) the transposed matrices
   CoeffDev dev() const;
@@ -134,44 +165,6 @@ struct TransposeScope {
 
 private:
   bool prev_;
-};
-
-// Packed symmetric pointwise operators (pre-assembled D): double[ne][ncomp][Q], the six upper
-// entries of  w detJ adj^T C adj  (mass part, if any) followed by the six of  w detJ Jl^T C Jl
-// (curl-curl part, if any).  Shared between an operator and its p-coarsened copies.
-struct QData {
-  double *d = nullptr;
-  int ncomp = 0;
-  int refcount = 1;
-  // metric form (isotropic coefficients): H = (w / |detJ|) J^T J (six entries) and |detJ| / w per point, a
-  // property of the mesh alone, shared by every operator and p-level on it.  Both pointwise operators follow
-  // from it in registers:  (w / detJ) J^T c J = c H,   w detJ adj^T c adj = c (|detJ| / w) adj(H).
-  bool metric = false;
-  // Affine elements (round 6; four points per direction, the streaming H(curl) kernel): an element whose Jacobian is constant has
-  // D(q) = w_q D_e -- 6 | 7 | 12 numbers per element instead of per point.  d_aff [ne padded to 4][2 ncomp] pairs of doubles: row
-  // 2 c + h of element e = r_c {wz(2h), wz(2h + 1)} with r_c the point-independent factor of component c and wz the 1-D weight
-  // along the lane's column (metric component 6, |detJ| / w: g {1 / wz(2h), 1 / wz(2h + 1)}); the kernel multiplies the result of
-  // the D stage by the in-plane weight w(ta) w(tb).  batch_aff[b] != 0: the four elements of batch b are all affine (the
-  // streaming kernel then reads 4 x 2 ncomp x 16 B instead of 4 x ncomp x 512 B).  The per-point data stays in place: every
-  // other consumer (one-shot kernels, diagonal, assembly, the complex forms) is unaffected.  Built once per QData by
-  // stream_affine_setup (pa_nd_hex_stream.hip) -- coarsened operators share it with the q-data.
-  double *d_aff = nullptr;
-  std::vector<unsigned char> batch_aff;
-  bool aff_done = false;
-  int n_aff_elems = 0, n_aff_batch_elems = 0;  // affine elements found / of them in all-affine batches (compressed)
-  double wq2[2] = {0.0, 0.0};                  // the two distinct 1-D weights (symmetric four-point rule)
-  // Column-separable elements (extruded along the local zeta axis: x, y independent of zeta, z linear in it): every component
-  // factors as D_c(ta, tb, qz) = wz(qz) r_c(ta, tb) (metric component 6: r / wz(qz)), and lane (ta, tb) of the streaming kernel
-  // owns exactly the column qz = 0..3 -- one number per component and lane instead of four.  d_col [ne padded to 4][ncomp][16]
-  // doubles (+ 8 of padding: the kernel's second request of a component reads 64 bytes further, unused): r_c(t), the mean over
-  // the column of D_c / wz (component 6: of D_6 wz); the kernel multiplies it by wz(qz) (component 6: by 1 / wz(qz)) in registers
-  // ahead of its D stage.  batch_col[b] != 0: the four elements of batch b are all column-separable
-  // and the batch is not all-affine (those keep the smaller affine rows): 4 x ncomp x 128 B instead of 4 x ncomp x 512 B.
-  // Separability along the other two local axes is not looked for.  Built with the affine rows by stream_affine_setup;
-  // PALACE_AMD_STREAM_COLUMN=0 switches the form off.  The per-point data stays in place for every other consumer.
-  double *d_col = nullptr;
-  std::vector<unsigned char> batch_col;
-  int n_col_elems = 0, n_col_batch_elems = 0;  // column-separable elements found (affine ones included) / in column batches
 };
 
 // Offset of component c at point q inside one element's block of packed q-data (H(curl) hexahedra).  In general
@@ -203,58 +196,54 @@ inline StreamForm stream_form(bool masked) { return masked ? kStreamMasked : kSt
 struct StreamTables {
   // the words that carry the form's flags, as the block's element kernel reads them: three- and four-point H(curl) the flag
   // words on their own, [ne][16]; five-point H(curl) [ne][ceil(P/64)][32] and H1 [ne][ceil(P/64) + 1][16] the slot words with them
-  uint32_t *d_flags = nullptr;
-  uint32_t *d_rchunk = nullptr;  // [ceil(n_rows / 64)] RunChunk: run-start mask of 64 gathered dofs + run / offset of the first
-  int32_t *d_rhdr = nullptr;     // [n_runs + 1] run headers {first dof | length - 1 | essential, first copy entry}
-  int32_t *d_rpos = nullptr;     // copy positions in d_ye
+  DevBuf<uint32_t> d_flags;
+  DevBuf<uint32_t> d_rchunk;     // [ceil(n_rows / 64)] RunChunk: run-start mask of 64 gathered dofs + run / offset of the first
+  DevBuf<int32_t> d_rhdr;        // [n_runs + 1] run headers {first dof | length - 1 | essential, first copy entry}
+  DevBuf<int32_t> d_rpos;        // copy positions in d_ye
   int n_rows = 0, n_runs = 0;    // dofs the run gather owns, runs they fall into
   bool ready() const { return d_rhdr != nullptr; }  // the form has been built
-  void release() {
-    (void)hipFree(d_flags), (void)hipFree(d_rchunk), (void)hipFree(d_rhdr), (void)hipFree(d_rpos);
-    *this = StreamTables{};
-  }
 };
 
 struct SubOp {
-  Geom *geom = nullptr;
-  QData *qd = nullptr;  // nullptr: matrix-free D from the geometry data (the reference default)
+  Ref<Geom> geom;  // (first: the geometry goes after everything that was built on it)
+  Ref<QData> qd;  // nullptr: matrix-free D from the geometry data (the reference default)
   int fe_type = 0, p = 0, q1d = 0, P = 0, Q = 0, ne = 0, lsize = 0;
   int qf = 0;
   uint32_t trial_ops = 0, test_ops = 0;
-  int32_t *d_lidx = nullptr;  // [ne][P] signed tensor-order index: >=0 dof, <0 => -(1+dof) flipped
+  DevBuf<int32_t> d_lidx;  // [ne][P] signed tensor-order index: >=0 dof, <0 => -(1+dof) flipped
   // sorted order of E / E^T: entry m of element e is its m-th smallest global dof
-  int32_t *d_sidx = nullptr;     // [ne][P] signed sorted index
-  int32_t *d_sidx_bc = nullptr;  // copy with kEssBit on essential dofs (pa_op_set_essential)
-  uint16_t *d_perm = nullptr;    // [ne][P] tensor-order slot of sorted entry m
+  DevBuf<int32_t> d_sidx;     // [ne][P] signed sorted index
+  DevBuf<int32_t> d_sidx_bc;  // copy with kEssBit on essential dofs (pa_op_set_essential)
+  DevBuf<uint16_t> d_perm;    // [ne][P] tensor-order slot of sorted entry m
   // Exclusive dofs (one element copy only, e.g. element interiors): stored straight into y by the
   // element kernel instead of going through the E-vector; the gather kernel then only visits the rest.
-  uint16_t *d_perm_x = nullptr;  // perm with kExclBit16 on exclusive entries (set at finalize)
-  int32_t *d_shared = nullptr;   // list of the dofs the gather kernel still has to sum
-  int32_t *d_shared_bc = nullptr;  // the same with kEssBit on essential dofs (pa_op_set_essential)
+  DevBuf<uint16_t> d_perm_x;  // perm with kExclBit16 on exclusive entries (set at finalize)
+  DevBuf<int32_t> d_shared;   // list of the dofs the gather kernel still has to sum
+  DevBuf<int32_t> d_shared_bc;  // the same with kEssBit on essential dofs (pa_op_set_essential)
   std::vector<int32_t> h_shared;
   int n_shared = 0;
   std::vector<uint16_t> h_perm;
   std::vector<int32_t> h_sidx;   // host copy (needed to build d_sidx_bc)
   // E^T as a gather (default): E-vector scratch and the CSR transpose of lidx
-  double *d_ye = nullptr;      // [ne][P]
-  double *d_ye2 = nullptr;     // second E-vector (two right-hand sides), allocated on first use
-  int32_t *d_tptr = nullptr;   // [lsize + 1]
-  int32_t *d_tent = nullptr;   // [ne * P] signed positions into d_ye
+  DevBuf<double> d_ye;      // [ne][P]
+  DevBuf<double> d_ye2;     // second E-vector (two right-hand sides), allocated on first use
+  DevBuf<int32_t> d_tptr;   // [lsize + 1]
+  DevBuf<int32_t> d_tent;   // [ne * P] signed positions into d_ye
   // streaming form (pa_nd_hex_stream.hip): run-compressed index words, byte slots, E^T by runs.  Shared by every form:
-  uint32_t *d_idxc = nullptr;  // [ne][kIdxWords] run-compressed sorted element -> dof index (pa_stream_host.hpp)
+  DevBuf<uint32_t> d_idxc;  // [ne][kIdxWords] run-compressed sorted element -> dof index (pa_stream_host.hpp)
   bool stream_default = true;  // false: the tables exist for the split-vector apply only, y = A x keeps the one-shot kernel (H1, p < 3)
   std::vector<uint32_t> h_perm_s;  // slot + flag words as pack_index / pack_index_wide lay them out (host; the forms are edited copies)
   // three- and four-point H(curl) kernels: the slot words through a dictionary -- elements whose sorted -> tensor-order permutation
   // agrees share one entry (a structured mesh has a handful: 10 on the 125 440-element bench cylinder), the element's entry
   // number rides in a spare word of its index block
-  uint32_t *d_slots = nullptr;
+  DevBuf<uint32_t> d_slots;
   int n_slot_patterns = 0;
-  double *d_coef_s = nullptr;    // metric form: [ne][2] scalar mass / curl-curl coefficient per element
+  DevBuf<double> d_coef_s;    // metric form: [ne][2] scalar mass / curl-curl coefficient per element
   std::vector<char> h_ess_flag;  // the essential flags last fused (stream_set_essential), for stream_build_all
   // ... and per form (StreamForm): plain from build_stream, masked from stream_set_essential, all from stream_build_all
   StreamTables stream[3];
   std::vector<double> Bc, Gc, Bo;  // full 1-D tables [q1d][n] (host)
-  double *d_tab = nullptr;        // the same on the device: [Bo | Bc | Gc]
+  DevBuf<double> d_tab;        // the same on the device: [Bo | Bc | Gc]
   bool iso = false;               // every material coefficient is a multiple of the identity
   std::vector<uint8_t> ctx_blob;
   CoeffHost c0, c1;
@@ -262,39 +251,39 @@ struct SubOp {
 
 // One sub-operator on a non-tensor element block (pa_dense.hip): dense tables on the FP64 matrix cores.
 struct DenseSub {
-  Geom *geom = nullptr;
+  Ref<Geom> geom;
   int fe_type = 0, P = 0, Q = 0, Qpad = 0, nch = 0, ne = 0, nb = 0, lsize = 0, KP = 0, PT = 0;
   int qf = 0, mode = 0;
   bool contra = false;  // plane H(div) mass: contravariant map in the vector-mass D (f_apply_hdiv_22)
   bool ye_rows = false;  // E-vector rows by element ([block][element][dof]) instead of by dof (pa_dense.hip: DenseArgs::ye_rows)
   uint32_t trial_ops = 0, test_ops = 0;
-  int32_t *d_idx = nullptr;     // [nb][4 KP][16] signed index (oriented: <0 => -(1+dof) flipped); pads read zero
-  int32_t *d_idx_bc = nullptr;  // copy with kEssBit on essential dofs
-  uint8_t *d_ess_flag = nullptr;  // [lsize] 1 on essential dofs (row fix-up of the split-vector gather)
-  uint16_t *d_co = nullptr;     // [nb][4 KP][16] packed int8 rows / columns of T_e (curl-oriented) or nullptr
-  uint32_t *d_co2 = nullptr;    // the same, two dof slots per word: [nb][KP / 2][64] (resident kernel)
-  int32_t *d_rows = nullptr;    // blocks that touch few dofs: the rows they have (sorted), n_rows of them; else nullptr
+  DevBuf<int32_t> d_idx;     // [nb][4 KP][16] signed index (oriented: <0 => -(1+dof) flipped); pads read zero
+  DevBuf<int32_t> d_idx_bc;  // copy with kEssBit on essential dofs
+  DevBuf<uint8_t> d_ess_flag;  // [lsize] 1 on essential dofs (row fix-up of the split-vector gather)
+  DevBuf<uint16_t> d_co;     // [nb][4 KP][16] packed int8 rows / columns of T_e (curl-oriented) or nullptr
+  DevBuf<uint32_t> d_co2;    // the same, two dof slots per word: [nb][KP / 2][64] (resident kernel)
+  DevBuf<int32_t> d_rows;    // blocks that touch few dofs: the rows they have (sorted), n_rows of them; else nullptr
   int n_rows = 0;
   std::vector<int32_t> h_idx;
   std::vector<int32_t> h_off;  // plain [ne][P] offsets (full assembly)
-  double *d_Tf = nullptr, *d_Tt = nullptr;  // MFMA A-operand fragments of the tables (forward / transposed)
-  double *d_L = nullptr;       // LDS-resident form of the tables (fast path) or nullptr
-  double *d_qdata = nullptr;   // packed pre-assembled D [nb][ncq][Qpad][16] (fast path)
+  DevBuf<double> d_Tf, d_Tt;  // MFMA A-operand fragments of the tables (forward / transposed)
+  DevBuf<double> d_L;       // LDS-resident form of the tables (fast path) or nullptr
+  DevBuf<double> d_qdata;   // packed pre-assembled D [nb][ncq][Qpad][16] (fast path)
   std::vector<uint16_t> h_co;  // host copy of d_co (restriction compare of the complex form)
   double chk_interp = 0.0, chk_deriv = 0.0;  // checksums of the basis tables (same)
-  double *d_ye2 = nullptr;     // second E-vector (imaginary part of the complex form), allocated on first use
-  uint8_t *d_affine = nullptr; // [nb] blocks whose elements all have a constant Jacobian (D_q = (w_q / w_0) D_0) or nullptr
-  double *d_wrel = nullptr;    // [Q4] w_q / w_0
+  DevBuf<double> d_ye2;     // second E-vector (imaginary part of the complex form), allocated on first use
+  DevBuf<uint8_t> d_affine; // [nb] blocks whose elements all have a constant Jacobian (D_q = (w_q / w_0) D_0) or nullptr
+  DevBuf<double> d_wrel;    // [Q4] w_q / w_0
   int n_affine = 0;
-  int32_t *d_blist[2] = {nullptr, nullptr};  // mixed meshes: the affine blocks / the others (else nullptr: one kind only)
+  DevBuf<int32_t> d_blist[2];  // mixed meshes: the affine blocks / the others (else nullptr: one kind only)
   int n_blist[2] = {0, 0};
   int L_rows = 0, ncq = 0, num_cu = 0;
-  double *d_interp = nullptr, *d_deriv = nullptr;  // plain tables (diagonal assembly)
-  int32_t *d_off = nullptr;    // plain [ne][P] offsets (diagonal assembly)
-  int8_t *d_cor = nullptr;     // plain curl_orients or nullptr
-  uint8_t *d_ori = nullptr;
-  double *d_ye = nullptr;      // E-vector [nb][4 KP][16]
-  int32_t *d_tptr = nullptr, *d_tent = nullptr;
+  DevBuf<double> d_interp, d_deriv;  // plain tables (diagonal assembly)
+  DevBuf<int32_t> d_off;    // plain [ne][P] offsets (diagonal assembly)
+  DevBuf<int8_t> d_cor;     // plain curl_orients or nullptr
+  DevBuf<uint8_t> d_ori;
+  DevBuf<double> d_ye;      // E-vector [nb][4 KP][16]
+  DevBuf<int32_t> d_tptr, d_tent;
   std::vector<uint8_t> ctx_blob;
   CoeffHost c0, c1;
 };
@@ -303,23 +292,23 @@ struct DenseSub {
 struct MixedSide {
   int fe_type = 0, P = 0, lsize = 0, nc = 3;
   std::vector<int32_t> h_off;  // [ne][P] L-vector indices (full assembly)
-  int32_t *d_sidx = nullptr;
-  int8_t *d_cor = nullptr;
-  double *d_tabF = nullptr, *d_tabT = nullptr;
-  int32_t *d_tptr = nullptr, *d_tent = nullptr;
+  DevBuf<int32_t> d_sidx;
+  DevBuf<int8_t> d_cor;
+  DevBuf<double> d_tabF, d_tabT;
+  DevBuf<int32_t> d_tptr, d_tent;
 };
 struct MixedSub {
-  Geom *geom = nullptr;
+  Ref<Geom> geom;
   int ne = 0, Q = 0, qf = 0, kind = 0;
   bool error = false;
   MixedSide s1, s2;  // apply: trial, test; error: first and second input
   CoeffHost c0, c1;
-  double *d_ye = nullptr;
-  mutable double *d_ye_t = nullptr;  // E-vector of the transposed apply (trial side), allocated at its first use
+  DevBuf<double> d_ye;
+  mutable DevBuf<double> d_ye_t;  // E-vector of the transposed apply (trial side), allocated at its first use
   // sum-factorised form on tensor-product hexahedra (pa_mixed_hex.hip): the two spaces as index-only blocks (sorted signed
   // gather, slot permutation, transpose map and E-vector of each), the 1-D tables shared by both
-  SubOp *hex1 = nullptr, *hex2 = nullptr;
-  int32_t *d_eorder = nullptr;  // the caller's number of internal element e (error integrator), nullptr: the same order
+  std::unique_ptr<SubOp> hex1, hex2;
+  DevBuf<int32_t> d_eorder;  // the caller's number of internal element e (error integrator), nullptr: the same order
 };
 
 void parse_coeff(const void *blob, size_t bytes, int dim, CoeffHost &out, size_t slot_offset);
@@ -354,7 +343,6 @@ void launch_h1_hex_stream(const SubOp &so, const double *x, double *y, StreamFor
 bool nd_hex_stream_ok(const SubOp &so);
 void build_stream(SubOp &so);
 void stream_set_essential(SubOp &so, const std::vector<char> &flag);
-void free_stream(SubOp &so);
 // Split vectors of a multi-rank apply without L-vector copies: local dofs [0, n_true) are read from x and written to y,
 // the ghosts [n_true, lsize) are read from xg0 or xg1 (the parity of the device-resident counter *sel picks the buffer; sel ==
 // NULL: xg0) and written to yg (all three unshifted: entry 0 is local dof n_true)
@@ -424,9 +412,8 @@ bool two_part_enabled();
 
 // pa_dense.hip
 void launch_geom_dense(const pa_mesh_dense_desc &mesh, Geom &g, hipStream_t s);
-DenseSub *make_dense_sub(pa_geom *geom, const pa_restriction_desc &r, const pa_dense_basis_desc &b, int qf,
+std::unique_ptr<DenseSub> make_dense_sub(pa_geom *geom, const pa_restriction_desc &r, const pa_dense_basis_desc &b, int qf,
                          const void *ctx, size_t ctx_size, uint32_t trial_ops, uint32_t test_ops, int height, bool contra = false);
-void free_dense_sub(DenseSub *ds);
 void dense_set_essential(DenseSub &ds, const std::vector<char> &flag);
 void launch_dense_apply(const DenseSub &ds, const double *x, bool masked, hipStream_t s, const SplitIO *split = nullptr);
 // split: rows >= n_true go to split->yg; ess_policy >= 0 (with split only): essential rows are set to x (1) or 0 (0) here
@@ -461,19 +448,17 @@ void launch_et_gather2_raw(int n, const int32_t *tptr, const int32_t *tent, cons
                            const double *x1 = nullptr, int ess_policy = -1);
 
 // pa_mixed.hip
-MixedSub *make_mixed_sub(pa_geom *geom, const pa_restriction_desc &r1, const pa_dense_basis_desc &b1,
+std::unique_ptr<MixedSub> make_mixed_sub(pa_geom *geom, const pa_restriction_desc &r1, const pa_dense_basis_desc &b1,
                          const pa_restriction_desc &r2, const pa_dense_basis_desc &b2, int qf, const void *ctx,
                          size_t ctx_size);
-MixedSub *make_mixed_gradient_sub(pa_geom *geom, const pa_restriction_desc &r1, const pa_dense_basis_desc &b1,
+std::unique_ptr<MixedSub> make_mixed_gradient_sub(pa_geom *geom, const pa_restriction_desc &r1, const pa_dense_basis_desc &b1,
                                   const pa_restriction_desc &r2, const pa_dense_basis_desc &b2, int comp_stride, int qf,
                                   const void *ctx, size_t ctx_size);
-void free_mixed_sub(MixedSub *ms);
 void launch_mixed_apply(const MixedSub &ms, const double *x, double *y, bool accumulate, hipStream_t s, bool transpose = false);
 void launch_mixed_error(const MixedSub &ms, const double *u1, const double *u2, double *out, hipStream_t s);
 // pa_capi.hip: the tensor-product form of a two-space operator / error integrator; the blocks of its two spaces
-MixedSub *make_mixed_hex_sub(pa_geom *geom, const pa_restriction_desc &r1, const pa_basis_desc &b1, const pa_restriction_desc &r2,
+std::unique_ptr<MixedSub> make_mixed_hex_sub(pa_geom *geom, const pa_restriction_desc &r1, const pa_basis_desc &b1, const pa_restriction_desc &r2,
                              const pa_basis_desc &b2, int qf, const void *ctx, size_t ctx_size);
-void free_sub(SubOp *so);
 // pa_mixed_hex.hip: x1 -> the E-vector of the output block (apply; transpose: hex2 -> hex1) or x1, x2 -> out (error)
 void launch_mixed_hex(const MixedSub &ms, const double *x1, const double *x2, double *out, hipStream_t s, bool transpose);
 // six points per direction (pa_mixed_hex_q6.hip): so / s2 the input and the other block, kind with the transpose resolved
@@ -502,16 +487,16 @@ struct pa_op {
   bool has_essential = false;
   std::vector<int32_t> ess_sorted;  // the list fused into the index tables (pa_op_set_essential)
   bool symmetric() const;  // every coefficient matrix of every sub-operator is symmetric => A^T = A
-  std::vector<pa::SubOp *> subs;
-  std::vector<pa::DenseSub *> dsubs;
-  std::vector<pa::MixedSub *> msubs;  // trial space != test space (pa_op_add_sub_dense_mixed)
+  std::vector<std::unique_ptr<pa::SubOp>> subs;
+  std::vector<std::unique_ptr<pa::DenseSub>> dsubs;
+  std::vector<std::unique_ptr<pa::MixedSub>> msubs;  // trial space != test space (pa_op_add_sub_dense_mixed)
   // fused smoother step of a dense operator with surface blocks (round 6, pa_op_prepare_fused_step): the surface blocks accumulate into
   // t_extra (zero outside their rows; the union of their rows is reset before every use), the volume block's gather adds it
-  double *d_t_extra = nullptr;
-  int32_t *d_extra_rows = nullptr;
+  pa::DevBuf<double> d_t_extra;
+  pa::DevBuf<int32_t> d_extra_rows;
   int n_extra_rows = 0;
   // ... by ONE gather over the union of their rows (entries of every surface block, block by block: the order of the accumulating
   // gathers it replaces): row pointers, signed E-vector positions, block numbers
-  int32_t *d_urow_ptr = nullptr, *d_uent = nullptr;
-  uint8_t *d_ublk = nullptr;
+  pa::DevBuf<int32_t> d_urow_ptr, d_uent;
+  pa::DevBuf<uint8_t> d_ublk;
 };

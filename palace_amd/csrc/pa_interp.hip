@@ -853,11 +853,11 @@ class DenseInterpOperator : public Operator {
   const Context *ctx_;
   const Halo *halo_d_;
   int ne_, Pd_, Pr_, nl_d_, nl_r_, nt_d_, nt_r_;
-  int32_t *d_off_d_ = nullptr, *d_off_r_ = nullptr, *d_tptr_ = nullptr, *d_tent_ = nullptr;
-  int8_t *d_sgn_d_ = nullptr, *d_sgn_r_ = nullptr, *d_T_d_ = nullptr, *d_B_r_ = nullptr;
-  double *d_M_ = nullptr, *d_ye_ = nullptr;
-  uint8_t *d_mat_id_ = nullptr;
-  int32_t *d_pk_[4] = {nullptr, nullptr, nullptr, nullptr};  // register form: {domain rows, domain columns, range rows, range columns}
+  pa::DevBuf<int32_t> d_off_d_, d_off_r_, d_tptr_, d_tent_;
+  pa::DevBuf<int8_t> d_sgn_d_, d_sgn_r_, d_T_d_, d_B_r_;
+  pa::DevBuf<double> d_M_, d_ye_;
+  pa::DevBuf<uint8_t> d_mat_id_;
+  pa::DevBuf<int32_t> d_pk_[4];  // register form: {domain rows, domain columns, range rows, range columns}
   mutable Vector ld_, lr_;
 
   int nmat_ = 1, gather_group_ = 1;
@@ -906,8 +906,8 @@ class DenseInterpOperator : public Operator {
       hipLaunchKernelGGL((dense_interp_kernel<TR, 0>), dim3(grid), dim3(64 * kDenseInterpWaves), lds, ctx_->stream, a, lds_mats, pmax);
     PA_HIP(hipGetLastError());
   }
-  static int8_t *signs(const pa_restriction_desc &r, hipStream_t s) {
-    if (!r.orients) return nullptr;
+  static pa::DevBuf<int8_t> signs(const pa_restriction_desc &r, hipStream_t s) {
+    if (!r.orients) return {};
     std::vector<int8_t> v((size_t)r.num_elem * r.elem_size);
     for (size_t k = 0; k < v.size(); k++) v[k] = r.orients[k] ? -1 : 1;
     return pa::dev_upload(v.data(), v.size(), s);
@@ -989,12 +989,6 @@ public:
     }
     ld_.SetSize(nl_d_), lr_.SetSize(nl_r_);
   }
-  ~DenseInterpOperator() override {
-    (void)hipFree(d_off_d_), (void)hipFree(d_off_r_), (void)hipFree(d_tptr_), (void)hipFree(d_tent_);
-    (void)hipFree(d_sgn_d_), (void)hipFree(d_sgn_r_), (void)hipFree(d_T_d_), (void)hipFree(d_B_r_);
-    (void)hipFree(d_M_), (void)hipFree(d_ye_), (void)hipFree(d_mat_id_);
-    for (int32_t *p : d_pk_) (void)hipFree(p);
-  }
   void Mult(const Vector &x, Vector &y) const override {
     const Context &c = *ctx_;
     PA_REQUIRE(x.Size() == nt_d_ && y.Size() == nt_r_, "size mismatch in interpolation");
@@ -1053,9 +1047,9 @@ class InterpOperator : public Operator {
   const Conforming *conf_c_ = nullptr;  // hanging-node constraints of the coarse (domain) space: P_c is a sparse product
   int kind_ = 0;
   int fe_type_, pc_, pf_, ne_, nl_c_, nl_f_, nt_c_, nt_f_;
-  int32_t *d_lidx_c_ = nullptr, *d_lidx_f_ = nullptr;
-  double *d_Ic_ = nullptr, *d_Io_ = nullptr, *d_ye_c_ = nullptr;
-  int32_t *d_tptr_c_ = nullptr, *d_tent_c_ = nullptr;
+  pa::DevBuf<int32_t> d_lidx_c_, d_lidx_f_;
+  pa::DevBuf<double> d_Ic_, d_Io_, d_ye_c_;
+  pa::DevBuf<int32_t> d_tptr_c_, d_tent_c_;
   std::vector<double> h_Ic_, h_Io_;
   mutable Vector lc_, lf_;
 
@@ -1177,10 +1171,6 @@ public:
       h_Io_.assign(Io, Io + nio);
     }
     lc_.SetSize(nl_c_), lf_.SetSize(nl_f_);
-  }
-  ~InterpOperator() override {
-    (void)hipFree(d_lidx_c_), (void)hipFree(d_lidx_f_), (void)hipFree(d_Ic_), (void)hipFree(d_Io_),
-        (void)hipFree(d_ye_c_), (void)hipFree(d_tptr_c_), (void)hipFree(d_tent_c_);
   }
   // y_f = R_f D^-1 E_f^T I E_c P_c x_c
   void Mult(const Vector &x, Vector &y) const override {

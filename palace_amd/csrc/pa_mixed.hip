@@ -372,10 +372,6 @@ void build_side(const pa_restriction_desc &r, const pa_dense_basis_desc &b, int 
   sd.d_tent = dev_upload(tent.data(), tent.size());
 }
 
-void free_side(MixedSide &sd) {
-  hipFree(sd.d_sidx), hipFree(sd.d_cor), hipFree(sd.d_tabF), hipFree(sd.d_tabT), hipFree(sd.d_tptr), hipFree(sd.d_tent);
-}
-
 MixSideDev dev_side(const MixedSide &sd) { return MixSideDev{sd.P, sd.nc, sd.d_sidx, sd.d_cor, sd.d_tabF, sd.d_tabT}; }
 
 // transpose: A^T = B_1^T W^T B_2 -- the two sides change places, W^T is the other member of the QFunction pair (Jl^T C adj and
@@ -436,15 +432,14 @@ void build_transpose_map(const std::vector<int32_t> &off, const uint8_t *orients
   for (int d = 0; d < lsize; d++) tptr[d + 1] += tptr[d];
   std::vector<int32_t> fill(tptr.begin(), tptr.end() - 1);
   for (size_t k = 0; k < off.size(); k++) tent[fill[off[k]]++] = (orients && orients[k]) ? -1 - (int32_t)k : (int32_t)k;
-  hipFree(sd.d_tptr), hipFree(sd.d_tent);
   sd.d_tptr = dev_upload(tptr.data(), tptr.size());
   sd.d_tent = dev_upload(tent.data(), tent.size());
 }
 }  // namespace
 
-MixedSub *make_mixed_sub(pa_geom *geom, const pa_restriction_desc &r1, const pa_dense_basis_desc &b1,
-                         const pa_restriction_desc &r2, const pa_dense_basis_desc &b2, int qf, const void *ctx,
-                         size_t ctx_size) {
+std::unique_ptr<MixedSub> make_mixed_sub(pa_geom *geom, const pa_restriction_desc &r1, const pa_dense_basis_desc &b1,
+                                         const pa_restriction_desc &r2, const pa_dense_basis_desc &b2, int qf, const void *ctx,
+                                         size_t ctx_size) {
   PA_REQUIRE(geom && geom->eb == kEBm && geom->dim >= 1 && geom->dim <= geom->sdim && geom->sdim <= 3,
              "mixed-space operators need geometry data from pa_geom_create_dense");
   PA_REQUIRE(r1.num_elem == geom->ne && r2.num_elem == geom->ne, "restrictions do not match the mesh");
@@ -488,20 +483,14 @@ MixedSub *make_mixed_sub(pa_geom *geom, const pa_restriction_desc &r1, const pa_
                                   : ((cov1 ? covariant(b1) : b1.fe_type == PA_FE_HDIV) && (cov2 ? covariant(b2) : b2.fe_type == PA_FE_HDIV))),
              "element types do not match the QFunction (vecfemass.cpp:88-101, mixedvecgrad.cpp:43-76, mixedveccurl.cpp:41-58)");
   PA_REQUIRE(ctx && ctx_size >= 16 && ctx_size % 8 == 0, "bad coefficient context");
-  auto *ms = new MixedSub;
-  try {
-    ms->geom = geom;
-    geom->refcount++;
-    ms->ne = geom->ne, ms->Q = geom->Q, ms->qf = qf, ms->kind = kind, ms->error = err;
-    build_side(r1, b1, geom->Q, scalar ? 1 : dim, ms->s1, scalar, kind == 8);
-    build_side(r2, b2, geom->Q, scalar ? 1 : dim, ms->s2, scalar, kind == 8);
-    parse_coeff(ctx, ctx_size, scalar ? 1 : sdim, ms->c0, 0);
-    if (err) parse_coeff(ctx, ctx_size, scalar ? 1 : sdim, ms->c1, ms->c0.slots);  // PopulateCoefficientContext(dim, first, dim, second)
-    if (!err) ms->d_ye = dev_alloc<double>((size_t)ms->ne * ms->s2.P);
-  } catch (...) {
-    free_mixed_sub(ms);
-    throw;
-  }
+  auto ms = std::make_unique<MixedSub>();
+  ms->geom = Ref<Geom>(geom);
+  ms->ne = geom->ne, ms->Q = geom->Q, ms->qf = qf, ms->kind = kind, ms->error = err;
+  build_side(r1, b1, geom->Q, scalar ? 1 : dim, ms->s1, scalar, kind == 8);
+  build_side(r2, b2, geom->Q, scalar ? 1 : dim, ms->s2, scalar, kind == 8);
+  parse_coeff(ctx, ctx_size, scalar ? 1 : sdim, ms->c0, 0);
+  if (err) parse_coeff(ctx, ctx_size, scalar ? 1 : sdim, ms->c1, ms->c0.slots);  // PopulateCoefficientContext(dim, first, dim, second)
+  if (!err) ms->d_ye = dev_alloc<double>((size_t)ms->ne * ms->s2.P);
   return ms;
 }
 
@@ -510,9 +499,9 @@ MixedSub *make_mixed_sub(pa_geom *geom, const pa_restriction_desc &r1, const pa_
 // index of component 0), component c of a dof lives comp_stride entries further (restriction.cpp:137-142: 1 for byVDIM, where
 // the offsets are already multiplied by the vector dimension, the number of dofs for byNODES); r2.lsize is the size of the whole
 // vector L-vector.
-MixedSub *make_mixed_gradient_sub(pa_geom *geom, const pa_restriction_desc &r1, const pa_dense_basis_desc &b1,
-                                  const pa_restriction_desc &r2, const pa_dense_basis_desc &b2, int comp_stride, int qf,
-                                  const void *ctx, size_t ctx_size) {
+std::unique_ptr<MixedSub> make_mixed_gradient_sub(pa_geom *geom, const pa_restriction_desc &r1, const pa_dense_basis_desc &b1,
+                                                  const pa_restriction_desc &r2, const pa_dense_basis_desc &b2, int comp_stride,
+                                                  int qf, const void *ctx, size_t ctx_size) {
   PA_REQUIRE(geom && geom->eb == kEBm && geom->dim >= 1 && geom->dim <= geom->sdim && geom->sdim <= 3,
              "the gradient form needs geometry data from pa_geom_create_dense");
   PA_REQUIRE(r1.num_elem == geom->ne && r2.num_elem == geom->ne, "restrictions do not match the mesh");
@@ -527,44 +516,26 @@ MixedSub *make_mixed_gradient_sub(pa_geom *geom, const pa_restriction_desc &r1, 
              "GradientIntegrator requires a scalar H1 trial space (gradient table) and an H1 test space (value table)!");
   PA_REQUIRE(comp_stride >= 1 && !r2.orients && !r2.curl_orients, "bad component stride / oriented H1 restriction");
   PA_REQUIRE(ctx && ctx_size >= 16 && ctx_size % 8 == 0, "bad coefficient context");
-  auto *ms = new MixedSub;
-  try {
-    ms->geom = geom;
-    geom->refcount++;
-    ms->ne = geom->ne, ms->Q = geom->Q, ms->qf = qf, ms->kind = 7, ms->error = false;
-    build_side(r1, b1, geom->Q, dim, ms->s1, false);
-    build_side(r2, b2, geom->Q, 1, ms->s2, true);
-    // the E-vector block of an element is [sdim][P2]: its transpose map over the whole vector L-vector
-    const int P2 = ms->s2.P;
-    std::vector<int32_t> off((size_t)ms->ne * sdim * P2);
-    for (int e = 0; e < ms->ne; e++)
-      for (int c = 0; c < sdim; c++)
-        for (int i = 0; i < P2; i++) {
-          const int64_t v = (int64_t)r2.offsets[(size_t)e * P2 + i] + (int64_t)c * comp_stride;
-          PA_REQUIRE(v < r2.lsize, "component offset out of range (comp_stride and lsize of the vector space)");
-          off[((size_t)e * sdim + c) * P2 + i] = (int32_t)v;
-        }
-    build_transpose_map(off, nullptr, r2.lsize, ms->s2);
-    ms->s2.h_off = off;
-    parse_coeff(ctx, ctx_size, sdim, ms->c0, 0);
-    ms->d_ye = dev_alloc<double>((size_t)ms->ne * sdim * P2);
-  } catch (...) {
-    free_mixed_sub(ms);
-    throw;
-  }
+  auto ms = std::make_unique<MixedSub>();
+  ms->geom = Ref<Geom>(geom);
+  ms->ne = geom->ne, ms->Q = geom->Q, ms->qf = qf, ms->kind = 7, ms->error = false;
+  build_side(r1, b1, geom->Q, dim, ms->s1, false);
+  build_side(r2, b2, geom->Q, 1, ms->s2, true);
+  // the E-vector block of an element is [sdim][P2]: its transpose map over the whole vector L-vector
+  const int P2 = ms->s2.P;
+  std::vector<int32_t> off((size_t)ms->ne * sdim * P2);
+  for (int e = 0; e < ms->ne; e++)
+    for (int c = 0; c < sdim; c++)
+      for (int i = 0; i < P2; i++) {
+        const int64_t v = (int64_t)r2.offsets[(size_t)e * P2 + i] + (int64_t)c * comp_stride;
+        PA_REQUIRE(v < r2.lsize, "component offset out of range (comp_stride and lsize of the vector space)");
+        off[((size_t)e * sdim + c) * P2 + i] = (int32_t)v;
+      }
+  build_transpose_map(off, nullptr, r2.lsize, ms->s2);
+  ms->s2.h_off = off;
+  parse_coeff(ctx, ctx_size, sdim, ms->c0, 0);
+  ms->d_ye = dev_alloc<double>((size_t)ms->ne * sdim * P2);
   return ms;
-}
-
-void free_mixed_sub(MixedSub *ms) {
-  if (!ms) return;
-  free_sub(ms->hex1), free_sub(ms->hex2);
-  hipFree(ms->d_eorder);
-  free_side(ms->s1), free_side(ms->s2);
-  hipFree(ms->d_ye), hipFree(ms->d_ye_t);
-  hipFree(ms->c0.d_attr_mat), hipFree(ms->c0.d_mat), hipFree(ms->c0.d_mat_t);
-  hipFree(ms->c1.d_attr_mat), hipFree(ms->c1.d_mat), hipFree(ms->c1.d_mat_t);
-  pa_geom_destroy(static_cast<pa_geom *>(ms->geom));
-  delete ms;
 }
 
 void launch_mixed_apply(const MixedSub &ms, const double *x, double *y, bool accumulate, hipStream_t s, bool transpose) {

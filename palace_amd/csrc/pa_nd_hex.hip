@@ -559,7 +559,7 @@ void launch_nd_hex_qdata(SubOp &so, hipStream_t s) {
   CoeffDev cm, cc;
   int cross;  // (the mixed forms are matrix-free: no q-data is ever asked for them)
   nd_terms(so, use_u, use_c, cm, cc, cross);
-  auto *qd = new QData;
+  const Ref<QData> qd(new QData);
   qd->ncomp = 6 * ((int)use_u + (int)use_c);
   // (padded to a multiple of four elements for the streaming kernel; the pad is never used in a result)
   const size_t nq = (size_t)((so.ne + 3) & ~3) * qd->ncomp * nd_qd_cstride(so.q1d);
@@ -598,18 +598,17 @@ __global__ void nd_hex_metric_kernel(const int ne, const int q1d, const double *
 
 void launch_nd_hex_metric(SubOp &so, hipStream_t s) {
   Geom &g = *so.geom;
-  auto *qd = new QData;
+  const Ref<QData> qd(new QData);
   qd->ncomp = 7, qd->metric = true;
   const size_t nq = (size_t)((so.ne + 3) & ~3) * 7 * nd_qd_cstride(so.q1d);
   qd->d = dev_alloc<double>(nq);
   PA_HIP(hipMemsetAsync(qd->d, 0, nq * sizeof(double), s));
-  double *d_w = dev_upload(g.w1.data(), g.w1.size(), s);
+  const DevBuf<double> d_w = dev_upload(g.w1.data(), g.w1.size(), s);
   const long long n = (long long)so.ne * so.Q;
   hipLaunchKernelGGL(nd_hex_metric_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, so.ne, so.q1d, g.d_geom, d_w,
                      qd->d);
   PA_HIP(hipGetLastError());
   PA_HIP(hipStreamSynchronize(s));
-  hipFree(d_w);
   g.metric = qd;  // the geometry data holds the first reference
 }
 

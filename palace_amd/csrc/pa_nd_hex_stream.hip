@@ -802,23 +802,20 @@ static void stream_affine_setup(SubOp &so) {
   const int ne = so.ne, nep = (ne + 3) & ~3;
   const size_t nrow = (size_t)nep * 2 * qd.ncomp * 2;
   const size_t ncol = col_enabled ? (size_t)nep * qd.ncomp * 16 + 8 : 0;  // (+ 8: QData::d_col)
-  double *d_aff = nullptr, *d_col = nullptr;
-  unsigned char *d_flag = nullptr;
-  PA_HIP(hipMalloc(&d_aff, nrow * sizeof(double)));
+  DevBuf<double> d_aff = dev_alloc<double>(nrow), d_col;
   PA_HIP(hipMemset(d_aff, 0, nrow * sizeof(double)));
   if (col_enabled) {
-    PA_HIP(hipMalloc(&d_col, ncol * sizeof(double)));
+    d_col = dev_alloc<double>(ncol);
     PA_HIP(hipMemset(d_col, 0, ncol * sizeof(double)));
   }
-  PA_HIP(hipMalloc(&d_flag, (size_t)nep));
+  const DevBuf<unsigned char> d_flag = dev_alloc<unsigned char>((size_t)nep);
   PA_HIP(hipMemset(d_flag, 0, (size_t)nep));
   const double tol = getenv("PALACE_AMD_AFFINE_TOL") ? atof(getenv("PALACE_AMD_AFFINE_TOL")) : 1e-13;
-  hipLaunchKernelGGL(stream_affine_kernel, dim3(ne), dim3(64), 0, nullptr, ne, qd.ncomp, qd.metric ? 1 : 0, qd.d, w[0], w[1], tol, d_aff,
-                     d_col, d_flag);
+  hipLaunchKernelGGL(stream_affine_kernel, dim3(ne), dim3(64), 0, nullptr, ne, qd.ncomp, qd.metric ? 1 : 0, qd.d, w[0], w[1], tol,
+                     d_aff.get(), d_col.get(), d_flag.get());
   PA_HIP(hipGetLastError());
   std::vector<unsigned char> flag((size_t)nep, 0);
   PA_HIP(hipMemcpy(flag.data(), d_flag, (size_t)nep, hipMemcpyDeviceToHost));
-  (void)hipFree(d_flag);
   qd.wq2[0] = w[0], qd.wq2[1] = w[1];
   qd.batch_aff.assign((size_t)nep / 4, 0);
   if (enabled) {
@@ -832,19 +829,15 @@ static void stream_affine_setup(SubOp &so) {
     for (int b = 0; b < nep / 4; b++)
       if ((flag[4 * b] & flag[4 * b + 1] & flag[4 * b + 2] & flag[4 * b + 3] & 2) && !qd.batch_aff[b])
         qd.batch_col[b] = 1, qd.n_col_batch_elems += 4;
-    if (qd.n_col_batch_elems == 0) {
-      (void)hipFree(d_col);
+    if (qd.n_col_batch_elems == 0)
       qd.batch_col.clear();
-    } else {
-      qd.d_col = d_col;
-    }
+    else
+      qd.d_col = std::move(d_col);
   }
-  if (qd.n_aff_batch_elems == 0) {
-    (void)hipFree(d_aff);
+  if (qd.n_aff_batch_elems == 0)
     qd.batch_aff.clear();
-    return;
-  }
-  qd.d_aff = d_aff;
+  else
+    qd.d_aff = std::move(d_aff);
 }
 
 // the layout the slot + flag words of this block are packed and edited in (so.h_perm_s)
@@ -853,7 +846,7 @@ static streamhost::FlagLayout flag_layout(const SubOp &so) {
 }
 
 // the flag-carrying words of a form as the block's element kernel reads them (StreamTables::d_flags)
-static uint32_t *upload_flags(const SubOp &so, const std::vector<uint32_t> &pp) {
+static DevBuf<uint32_t> upload_flags(const SubOp &so, const std::vector<uint32_t> &pp) {
   if (so.fe_type != PA_FE_HCURL || wide_form(so)) return dev_upload(pp.data(), pp.size());
   const std::vector<uint32_t> fw = streamhost::split_flag_rows(flag_layout(so), pp);  // (the slot words: so.d_slots)
   return dev_upload(fw.data(), fw.size());
@@ -930,18 +923,13 @@ void build_stream(SubOp &so) {
 void stream_set_essential(SubOp &so, const std::vector<char> &flag) {
   if (!so.d_idxc) return;
   so.h_ess_flag = flag;
-  so.stream[kStreamAll].release();  // (built for another list: again on the next pa_op_prepare_fused_step)
+  so.stream[kStreamAll] = StreamTables{};  // (built for another list: again on the next pa_op_prepare_fused_step)
   std::vector<uint32_t> pb(so.h_perm_s);
   streamhost::mark_essential(flag_layout(so), pb, so.ne, so.h_sidx.data(), flag.data(), true);
   StreamTables &t = so.stream[kStreamMasked];
-  t.release();
+  t = StreamTables{};
   t.d_flags = upload_flags(so, pb);
   upload_runs(t, so, streamhost::gather_rows(so.ne, so.P, so.lsize, so.h_sidx.data(), flag.data(), false), flag.data());
-}
-
-void free_stream(SubOp &so) {
-  hipFree(so.d_idxc), hipFree(so.d_slots), hipFree(so.d_coef_s);
-  for (StreamTables &t : so.stream) t.release();
 }
 
 template <int P1, bool U, bool C, bool METRIC, int MINW, int GPOS, bool CPLX = false, bool SPLIT = false, int GEOMN = 0>
@@ -1131,7 +1119,7 @@ static void launch_run_gather(const SubOp &so, StreamForm form, const double *ye
   const int n = t.n_rows;
   if (n == 0) return;
   hipLaunchKernelGGL((et_run_gather_kernel_t<STEP, DUAL>), dim3((n + 256 * kGatherILP - 1) / (256 * kGatherILP)), dim3(256), 0, s, n,
-                     reinterpret_cast<const RunChunk *>(t.d_rchunk), reinterpret_cast<const RunHdr *>(t.d_rhdr), t.d_rpos, ye, y,
+                     reinterpret_cast<const RunChunk *>(t.d_rchunk.get()), reinterpret_cast<const RunHdr *>(t.d_rhdr.get()), t.d_rpos, ye, y,
                      accumulate ? 1 : 0, x, form != kStreamPlain ? ess_policy : -1, split ? split->n_true : 0x7fffffff,
                      split ? split->yg - split->n_true : nullptr, step, p2);
   PA_HIP(hipGetLastError());

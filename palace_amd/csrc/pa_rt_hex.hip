@@ -209,7 +209,7 @@ void launch_rt_hex_qdata(SubOp &so, hipStream_t s) {
   CoeffDev cm, cd;
   rt_terms(so, use_v, use_d, cm, cd);
   PA_REQUIRE((int)so.geom->w1.size() == so.q1d, "geometry data without its 1-D quadrature weights");
-  auto *qd = new QData;
+  const Ref<QData> qd(new QData);
   qd->ncomp = 6 * (int)use_v + (int)use_d;
   qd->d = dev_alloc<double>((size_t)so.ne * qd->ncomp * so.Q);
   RTWeights w{};

@@ -62,6 +62,8 @@ def load():
     lib = C.CDLL(LIB_PATH)
     lib.pa_last_error.restype = C.c_char_p
     lib.pa_version.restype = C.c_char_p
+    lib.pa_device_buffers_live.restype = C.c_int64
+    lib.pa_device_buffers_live.argtypes = []
     lib.pa_op_algorithmic_bytes.restype = C.c_double
     lib.pa_op_algorithmic_bytes.argtypes = [C.c_void_p]
     for name in ("pa_geom_destroy", "pa_op_destroy", "pa_error_op_destroy"):
@@ -74,6 +76,11 @@ def load():
 def last_error():
     """The message of this thread's last failed call (pa_last_error)."""
     return load().pa_last_error().decode()
+
+
+def device_buffers_live():
+    """Device arrays the library's objects own at this moment (pa_device_buffers_live)."""
+    return load().pa_device_buffers_live()
 
 
 def check(rc):
