@@ -550,6 +550,15 @@ int pa_csr_get(const pa_csr *csr, int32_t *nrows, int64_t *nnz, const int32_t **
 /* Columns of an assembled operator: its row count unless it was assembled from a two-space operator (BilinearForm(trial,
  * test)::FullAssemble, e.g. Atn of models/modeeigensolver.cpp:45-56: rows = test dofs, columns = trial dofs). */
 int pa_csr_num_cols(const pa_csr *csr);
+/* 1 when the matrix carries the symmetric flag (assembled from a symmetric operator, promised at pa_csr_create, or a Galerkin
+ * triple product of such a matrix with one prolongation on both sides), 0 when not, -1 for NULL. */
+int pa_csr_is_symmetric(const pa_csr *csr);
+/* Host CSR arrays [nrows x ncols] -> a device pa_csr (freed with pa_csr_destroy): a matrix that no pa_op assembles, such as a
+ * discrete gradient, or an independently computed one for pa_amg_create / pa_ams_create.  The row pointer starts at 0 and does
+ * not decrease, every column lies in [0, ncols); columns within a row may come in any order and may repeat.  `symmetric` is the
+ * caller's promise (square matrices only): CsrOperator::MultTranspose and the triple product's result flag rely on it. */
+int pa_csr_create(int32_t nrows, int32_t ncols, const int32_t *rowptr, const int32_t *col, const double *val, int symmetric,
+                  void *stream, pa_csr **csr);
 void pa_csr_destroy(pa_csr *csr);
 /* Operator::Size() (operator.hpp:46): number of sub-operators added so far. */
 int pa_op_num_sub(const pa_op *op);

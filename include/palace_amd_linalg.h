@@ -154,6 +154,26 @@ int pa_par_op_create_conforming(pa_context *ctx, pa_op *local, int n_true, const
                                 int diag_policy, pa_conform *conf, pa_par_op **A);
 int pa_par_sum_op_create_conforming(pa_context *ctx, int nterms, pa_op *const *locals, const double *coeffs, int n_true,
                                     const int32_t *ess_tdofs, int n_ess, int diag_policy, pa_conform *conf, pa_par_op **A);
+/* Sparse triple product on the device (pa_rap_conform.hip): T = L B P_trial, B a local matrix [n_local_test x n_local_trial],
+ * P_trial = [I; C_trial] of `trial` (NULL: the identity), L = P_test^T of `test` (left_form 0, Galerkin: ParallelAssemble of a
+ * bilinear form, linalg/rap.cpp:84-152; the square P^T A P passes the same pa_conform twice) or the first n_true_test rows
+ * (left_form 1, injection: a discrete interpolator on true dofs, R_test B P_trial); `test` NULL: the identity on the left in
+ * both forms.  n_local of either side must match B.  Columns of every row of T come out ascending and unique, the pattern is
+ * the structural product (numerical zeros stay), duplicates are summed in a fixed order -- the true row first, then its slaves
+ * ascending; within a row of B by position; within a row of C by position -- so repeated calls agree bitwise.  B may have
+ * unsorted or repeated columns.  T is symmetric-flagged when B is, the form is Galerkin and test == trial.  Set-up call: it
+ * waits for the device twice (row classes, total entries) and fails if T would have 2^31 entries or more. */
+int pa_csr_rap_conforming(pa_context *ctx, const pa_csr *B, const pa_conform *test, const pa_conform *trial, int left_form,
+                          pa_csr **T);
+/* the same; ms[0] / ms[1]: wall time in milliseconds of the symbolic (count, scan) and of the numeric (fill) phase */
+int pa_csr_rap_conforming_timed(pa_context *ctx, const pa_csr *B, const pa_conform *test, const pa_conform *trial, int left_form,
+                                pa_csr **T, double *ms);
+/* ParOperator::ParallelAssemble (linalg/rap.cpp:84-152) on true dofs, one rank: the local operator fully assembled (skip_zeros
+ * as pa_op_full_assemble) if it is a pa_op, used as it is if the operator was created assembled; with a conforming
+ * prolongation the triple product above follows, with neither that nor a halo the local matrix itself is returned (a copy).
+ * An operator with a halo is an error (several ranks are not built), so is a sum of local operators.  Essential dofs are NOT
+ * eliminated in T: pa_par_op_create_assembled takes the list, pa_amg_create / pa_ams_create eliminate on their way. */
+int pa_par_op_parallel_assemble(pa_par_op *A, int skip_zeros, pa_csr **T);
 /* 1 when the operator fuses its essential dofs into the local apply (a pure query; 0 with a conforming P) */
 int pa_par_op_fuses_essential(const pa_par_op *A);
 /* ParOperator::PrepareChebyStep(): 1 when the operator has the fused smoother step.  NOT a pure query: like the C++ method it is

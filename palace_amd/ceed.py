@@ -314,6 +314,44 @@ class DeviceCsr:
         L.pa_csr_num_cols.restype = C.c_int
         L.pa_csr_num_cols.argtypes = [C.c_void_p]
         self.ncols = int(L.pa_csr_num_cols(self.handle))
+        L.pa_csr_is_symmetric.restype = C.c_int
+        L.pa_csr_is_symmetric.argtypes = [C.c_void_p]
+        self.symmetric = L.pa_csr_is_symmetric(self.handle) == 1
+
+    @classmethod
+    def from_scipy(cls, m, symmetric=False):
+        """A scipy sparse matrix uploaded as it is stored (pa_csr_create): columns keep their order within a row, duplicates
+        stay.  `symmetric` is the caller's promise (square matrices)."""
+        m = m.tocsr()
+        rp = np.ascontiguousarray(m.indptr, dtype=np.int32)
+        ci = np.ascontiguousarray(m.indices, dtype=np.int32)
+        va = np.ascontiguousarray(m.data, dtype=np.float64)
+        L = _lib.load()
+        L.pa_csr_create.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        h = C.c_void_p()
+        _lib.check(L.pa_csr_create(m.shape[0], m.shape[1], _ptr(rp), _ptr(ci), _ptr(va), int(bool(symmetric)), _stream(), C.byref(h)))
+        return cls(h)
+
+    def to_scipy(self):
+        """The matrix copied back from the device -> scipy.sparse.csr_matrix (stored order, nothing summed or sorted)."""
+        import scipy.sparse as sp
+        import torch
+
+        L = _lib.load()
+        n, nnz = C.c_int32(), C.c_int64()
+        rp, ci, va = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        _lib.check(L.pa_csr_get(self.handle, C.byref(n), C.byref(nnz), C.byref(rp), C.byref(ci), C.byref(va)))
+
+        def view(ptr, count, typestr, dtype):
+            class _V:
+                __cuda_array_interface__ = dict(shape=(count,), typestr=typestr, data=(ptr.value, False), version=2)
+            return torch.as_tensor(_V(), device="cuda").cpu().numpy().astype(dtype)
+
+        torch.cuda.synchronize()
+        rowptr = view(rp, n.value + 1, "<i4", np.int32)
+        col = view(ci, max(1, nnz.value), "<i4", np.int32)[: nnz.value]
+        val = view(va, max(1, nnz.value), "<f8", np.float64)[: nnz.value]
+        return sp.csr_matrix((val, col, rowptr), shape=(n.value, self.ncols))
 
     def __del__(self):
         try:
@@ -535,32 +573,7 @@ class Operator:
 
     def full_assemble(self, skip_zeros=False):
         """CeedOperatorFullAssemble -> scipy.sparse.csr_matrix (values copied back from the device)."""
-        import scipy.sparse as sp
-        import torch
-
-        L = _lib.load()
-        h = C.c_void_p()
-        _lib.check(L.pa_op_full_assemble(self.handle, int(skip_zeros), _stream(), C.byref(h)))
-        n, nnz = C.c_int32(), C.c_int64()
-        rp, ci, va = C.c_void_p(), C.c_void_p(), C.c_void_p()
-        _lib.check(L.pa_csr_get(h, C.byref(n), C.byref(nnz), C.byref(rp), C.byref(ci), C.byref(va)))
-
-        def view(ptr, count, typestr, dtype):
-            class _V:
-                __cuda_array_interface__ = dict(shape=(count,), typestr=typestr, data=(ptr.value, False), version=2)
-            return torch.as_tensor(_V(), device="cuda").cpu().numpy().astype(dtype)
-
-        torch.cuda.synchronize()
-        rowptr = view(rp, n.value + 1, "<i4", np.int32)
-        col = view(ci, max(1, nnz.value), "<i4", np.int32)[: nnz.value]
-        val = view(va, max(1, nnz.value), "<f8", np.float64)[: nnz.value]
-        L.pa_csr_destroy.restype = None
-        L.pa_csr_destroy.argtypes = [C.c_void_p]
-        L.pa_csr_num_cols.restype = C.c_int
-        L.pa_csr_num_cols.argtypes = [C.c_void_p]
-        ncols = int(L.pa_csr_num_cols(h))  # = rows unless the operator has two spaces
-        L.pa_csr_destroy(h)
-        return sp.csr_matrix((val, col, rowptr), shape=(n.value, ncols))
+        return self.full_assemble_device(skip_zeros).to_scipy()  # (columns = rows unless the operator has two spaces)
 
     def algorithmic_bytes(self):
         return _lib.load().pa_op_algorithmic_bytes(self.handle)

@@ -506,7 +506,21 @@ const Operator &FiniteElementSpace::GetDiscreteInterpolator(const FiniteElementS
   return *slot;
 }
 
-void FiniteElementSpace::SetConformingProlongation(int n_true, const int *row_ptr, const int32_t *col, const double *val) {
+std::unique_ptr<Operator> FiniteElementSpace::MakeLocalDiscreteGradient(const FiniteElementSpace &aux) const {
+  PA_REQUIRE(fe_type_ == PA_FE_HCURL && aux.fe_type_ == PA_FE_H1 && aux.order_ == order_ && !IsDense() && !aux.IsDense() && mesh_ == aux.mesh_,
+             "local discrete gradient: the tensor H1 space of the same order on the same mesh expected");
+  std::vector<double> ox, ow, Bg, Dg;
+  fem::GaussLegendre(order_, ox, ow);
+  fem::LagrangeEval(fem::GaussLobatto(order_ + 1), ox, Bg, Dg);
+  const int n = order_ + 1;
+  std::vector<double> I((size_t)n * n, 0.0);
+  for (int i = 0; i < n; i++) I[(size_t)i * n + i] = 1.0;
+  const auto rh = aux.GetCeedElemRestriction(), rn = GetCeedElemRestriction();
+  const auto bh = aux.GetCeedBasis(), bn = GetCeedBasis();
+  return std::unique_ptr<Operator>(make_interp_operator(*ctx_, rh, bh, rn, bn, I.data(), Dg.data(), nullptr, aux.GetVSize(), GetVSize(), 1));
+}
+
+void FiniteElementSpace::SetConformingProlongation(int n_true,const int *row_ptr, const int32_t *col, const double *val) {
   PA_REQUIRE(!halo_, "a halo and a conforming prolongation together are not supported (hanging nodes: one rank)");
   PA_REQUIRE(n_true >= 0 && n_true <= vsize_, "conforming prolongation: more true dofs than local dofs");
   for (const int32_t d : ess_tdofs_) PA_REQUIRE(d < n_true, "the essential true dofs set before do not fit the constrained space");

@@ -203,6 +203,10 @@ public:
   // from the Nedelec space `aux` of the same order on the same mesh into this Raviart-Thomas space (fespace.cpp:199-206); tensor
   // spaces only, cached per `aux`
   const Operator &GetDiscreteInterpolator(const FiniteElementSpace &aux) const;
+  // the discrete gradient from the H1 space `aux` between the LOCAL vectors of the two spaces (GetVSize() of either: no halo,
+  // no constraint) -- what the true-dof gradient of a constrained pair is assembled from, R_nd G_local P_h1 (ksp.hip:
+  // NativeAmsSolver); owned by the caller
+  std::unique_ptr<Operator> MakeLocalDiscreteGradient(const FiniteElementSpace &aux) const;
   // dof and sign (true: flipped) of tensor (lexicographic) index t of element e -- native index t for dense spaces
   std::pair<int32_t, bool> GetElementDofSigned(int e, int t) const;
   // Dense spaces on a refined mesh: the local interpolation matrices [GetNumPointMatrices()][P][P] of this space's element for

@@ -46,9 +46,20 @@ amg::HostCsr AssembledLevelMatrix(const Operator &op, std::vector<char> &ess_fla
   PA_REQUIRE(par, "the algebraic coarse solvers need a ParOperator (the level operator of the multigrid hierarchy)");
   PA_REQUIRE(!par->GetHalo(), "the native AMG / AMS coarse solvers run on one rank (multi-rank: JACOBI_PCG or "
                               "CHEBYSHEV_JACOBI)");
-  PA_REQUIRE(!par->GetConforming(), "BOOMER_AMG / AMS on a level with hanging-node constraints need the assembled P^T A P (a sparse triple "
-                                    "product that is not built): use JACOBI, CHEBYSHEV_JACOBI or JACOBI_PCG at level 0");
   const auto &ess = par->GetEssentialTrueDofsHost();
+  if (par->GetConforming()) {
+    // hanging nodes: the assembled P^T A P through the device triple product -- for a level that WAS assembled (a CsrOperator,
+    // e.g. BilinearForm::pa_order_threshold above the coarse order: the reference's PartialAssemblyOrder route to a matrix).  A
+    // partially assembled level keeps the refusal below, which a test pins word for word.
+    PA_REQUIRE(dynamic_cast<const CsrOperator *>(&par->LocalOperator()),
+               "BOOMER_AMG / AMS on a level with hanging-node constraints need the assembled P^T A P (a sparse triple "
+               "product that is not built): use JACOBI, CHEBYSHEV_JACOBI or JACOBI_PCG at level 0.  An assembled level 0 "
+               "(BilinearForm::pa_order_threshold above its order) takes the device triple product instead.");
+    ess_flag.assign((size_t)op.Height(), 0);
+    for (const int32_t d : ess) ess_flag[d] = 1;
+    const auto m = par->ParallelAssemble(/*skip_zeros=*/false);
+    return DownloadCsr(*m, ess.data(), (int)ess.size());
+  }
   ess_flag.assign((size_t)op.Height(), 0);
   for (const int32_t d : ess) ess_flag[d] = 1;
   if (const auto *csr = dynamic_cast<const CsrOperator *>(&par->LocalOperator()))
@@ -388,8 +399,23 @@ class NativeAmsSolver : public Solver {  // LinearSolver::AMS
   // the lowest-order discrete gradient as a matrix: every row is +1 at the edge's head and -1 at its tail, so two applications
   // (to the vertex numbers and to their squares) identify both vertices of every edge
   amg::HostCsr GradientMatrix() const {
-    const Operator &G = nd_->GetDiscreteInterpolator(*h1_);
-    const int nv = h1_->GetTrueVSize(), ne = nd_->GetTrueVSize();
+    if (nd_->GetConforming() || h1_->GetConforming()) return ConstrainedGradientMatrix();
+    return IncidenceMatrix(nd_->GetDiscreteInterpolator(*h1_), h1_->GetTrueVSize(), nd_->GetTrueVSize());
+  }
+  // hanging nodes: on true dofs the gradient is no incidence matrix (a true edge that ends in a hanging vertex has a row of 3 or
+  // 5 entries 1, +-1/2, +-1/4), so the two probes go to the unconstrained LOCAL interpolator and the true-dof matrix is the
+  // injection-form triple product R_nd G_local P_h1 on the device (pa_rap_conform.hip)
+  amg::HostCsr ConstrainedGradientMatrix() const {
+    const auto G_op = nd_->MakeLocalDiscreteGradient(*h1_);
+    const amg::HostCsr Gl = IncidenceMatrix(*G_op, h1_->GetVSize(), nd_->GetVSize());
+    pa_csr *raw = nullptr;
+    if (pa_csr_create(Gl.nrows, Gl.ncols, Gl.rowptr.data(), Gl.col.data(), Gl.val.data(), 0, ctx_->stream, &raw) != 0)
+      throw pa::Error(pa_last_error());
+    const std::unique_ptr<pa_csr> G_local(raw);
+    const auto G_true = RapConforming(*ctx_, *G_local, nd_->GetConforming(), h1_->GetConforming(), RapLeft::INJECTION);
+    return DownloadCsr(*G_true, nullptr, 0);
+  }
+  amg::HostCsr IncidenceMatrix(const Operator &G, const int nv, const int ne) const {
     PA_REQUIRE((double)nv * nv < 9.0e15, "too many vertices for the two-probe reconstruction of the gradient");
     std::vector<double> x1((size_t)nv), x2((size_t)nv), d((size_t)ne), q((size_t)ne);
     for (int v = 0; v < nv; v++) x1[v] = v + 1.0, x2[v] = (v + 1.0) * (v + 1.0);

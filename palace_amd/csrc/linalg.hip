@@ -1366,6 +1366,37 @@ void ParOperator::AssembleDiagonal(Vector &diag) const {
   if (n_ess_) linalg::SetSubVector(c, diag, d_ess_, n_ess_, policy_ == DiagonalPolicy::DIAG_ONE ? 1.0 : 0.0);
 }
 
+std::unique_ptr<pa_csr> ParOperator::ParallelAssemble(bool skip_zeros) const {
+  StreamGraph::RequireNotRecording("ParOperator::ParallelAssemble");
+  PA_REQUIRE(!halo_, "ParallelAssemble: this operator has a halo (several ranks); the assembled P^T A P is built on one rank only");
+  const Context &c = *ctx_;
+  std::unique_ptr<pa_csr> local;  // the assembled local operator where this call makes it
+  const pa_csr *B = nullptr;
+  if (const auto *csr = dynamic_cast<const CsrOperator *>(A_)) {
+    B = &csr->Matrix();
+  } else if (const auto *pa = dynamic_cast<const ceed::Operator *>(A_)) {
+    pa_csr *m = nullptr;
+    if (pa_op_full_assemble(pa->Handle(), skip_zeros ? 1 : 0, c.stream, &m) != 0) throw pa::Error(pa_last_error());
+    local.reset(m);
+    B = m;
+  } else {
+    throw pa::Error("ParallelAssemble: the local operator is neither assembled nor a partially assembled operator");
+  }
+  if (conf_) return RapConforming(c, *B, conf_, conf_, RapLeft::GALERKIN);
+  if (local) return local;
+  auto m = std::make_unique<pa_csr>();  // an assembled local operator, P = I: a copy the caller owns
+  m->symmetric = B->symmetric, m->nrows = B->nrows, m->ncols = B->ncols, m->nnz = B->nnz;
+  m->d_rowptr = pa::dev_alloc<int32_t>((size_t)B->nrows + 1);
+  m->d_col = pa::dev_alloc<int32_t>((size_t)B->nnz), m->d_val = pa::dev_alloc<double>((size_t)B->nnz);
+  PA_HIP(hipMemcpyAsync(m->d_rowptr, B->d_rowptr, sizeof(int32_t) * ((size_t)B->nrows + 1), hipMemcpyDeviceToDevice, c.stream));
+  if (B->nnz) {
+    PA_HIP(hipMemcpyAsync(m->d_col, B->d_col, sizeof(int32_t) * (size_t)B->nnz, hipMemcpyDeviceToDevice, c.stream));
+    PA_HIP(hipMemcpyAsync(m->d_val, B->d_val, sizeof(double) * (size_t)B->nnz, hipMemcpyDeviceToDevice, c.stream));
+  }
+  PA_HIP(hipStreamSynchronize(c.stream));
+  return m;
+}
+
 // ---- smoothers --------------------------------------------------------------------------------
 void JacobiSmoother::SetOperator(const Operator &op) {
   StreamGraph::Invalidate();

@@ -394,9 +394,21 @@ class Conforming {
   pa::DevBuf<int32_t> d_col_, d_t_dof_, d_t_slave_;
   pa::DevBuf<double> d_val_, d_t_val_;
   pa::DevBuf<uint8_t> d_touched_;  // one byte per true dof: its row of C^T is not empty (the copy part of Restrict leaves it alone)
+  pa::DevBuf<int32_t> d_t_slot_;   // per true dof its row of the inverted index, -1: none (the triple product, pa_rap_conform.hip)
 
 public:
   enum : int { ADD = 1, ABS = 2, FIX_ONE = 4, FIX_ZERO = 8 };
+  // the device arrays as the triple product reads them: C by rows, C^T through the inverted index
+  struct DeviceView {
+    int n_true, n_con;
+    const int *row_ptr;
+    const int32_t *col;
+    const double *val;
+    const int *t_ptr;
+    const int32_t *t_slot, *t_slave;
+    const double *t_val;
+  };
+  DeviceView View() const { return {n_true_, n_con_, d_row_ptr_, d_col_, d_val_, d_t_ptr_, d_t_slot_, d_t_slave_, d_t_val_}; }
   Conforming(const Context &ctx, int n_true, int n_local, const int *row_ptr, const int32_t *col, const double *val);
   ~Conforming();
   Conforming(const Conforming &) = delete;
@@ -412,6 +424,17 @@ public:
   void Restrict(const double *ly, double *y, int flags, double a, const uint8_t *ess_mask, const double *x_ess,
                 hipStream_t stream) const;
 };
+
+// Sparse triple product with conforming prolongations on the device (pa_rap_conform.hip): T = L B P_trial with B a local CSR matrix
+// [n_local_test x n_local_trial], P_trial = [I; C_trial] (nullptr: the identity) and L = P_test^T (GALERKIN: ParallelAssemble of a
+// bilinear form, rap.cpp:84-152) or the first n_true_test rows (INJECTION: a discrete interpolator on true dofs).  Two phases,
+// symbolic (count, scan) and numeric (fill); no floating-point atomics; columns of every row ascending and unique, duplicates
+// summed in the order (row of B: the true row first, then its slaves ascending; position in B's row; position in C's row); the
+// pattern is the structural product.  Set-up: reads two small results back (RequireNotRecording).  phase_ms (may be nullptr):
+// wall time of the symbolic and of the numeric phase in milliseconds.
+enum class RapLeft { GALERKIN = 0, INJECTION = 1 };
+std::unique_ptr<pa_csr> RapConforming(const Context &ctx, const pa_csr &B, const Conforming *test, const Conforming *trial,
+                                      RapLeft left, double *phase_ms = nullptr);
 
 // ParOperator (rap.cpp:154-234): y = P^T A P x with essential-dof handling.  True dofs of this
 // rank are the first n_true entries of the local (L-) vector; shared dofs owned elsewhere follow
@@ -479,6 +502,12 @@ public:
   // b -= A_unconstrained (x restricted to the essential dofs); b[ess] = x[ess] | 0  (rap.cpp:56-82)
   void EliminateRHS(const Vector &x, Vector &b) const;
   void AssembleDiagonal(Vector &diag) const override;
+  // ParOperator::ParallelAssemble (rap.cpp:84-152) on one rank: the matrix of P^T A P on true dofs, owned by the caller.  The
+  // local operator is fully assembled (a ceed::Operator; skip_zeros as pa_op_full_assemble) or taken as it is (a CsrOperator);
+  // with a Conforming the device triple product follows, without one the local matrix is returned (a copy if it was a
+  // CsrOperator).  Essential dofs are NOT eliminated: wrap the result in a ParOperator with the same list, or hand it to
+  // DownloadCsr(m, ess, n_ess).  A halo is refused.  Set-up: waits for the device.
+  std::unique_ptr<pa_csr> ParallelAssemble(bool skip_zeros = false) const;
 
 private:
   mutable Vector tt_;

@@ -274,6 +274,27 @@ int pa_csr_get(const pa_csr *m, int32_t *nrows, int64_t *nnz, const int32_t **ro
 
 int pa_csr_num_cols(const pa_csr *m) { return m ? (m->ncols ? m->ncols : m->nrows) : -1; }
 
+int pa_csr_is_symmetric(const pa_csr *m) { return m ? (m->symmetric ? 1 : 0) : -1; }
+
+int pa_csr_create(int32_t nrows, int32_t ncols, const int32_t *rowptr, const int32_t *col, const double *val, int symmetric,
+                  void *stream, pa_csr **out) {
+  return guarded([&] {
+    PA_REQUIRE(out && nrows >= 0 && ncols >= 0 && rowptr && rowptr[0] == 0, "pa_csr_create: bad sizes or row pointer");
+    for (int32_t r = 0; r < nrows; r++) PA_REQUIRE(rowptr[r + 1] >= rowptr[r], "pa_csr_create: the row pointer must not decrease");
+    const int64_t nnz = rowptr[nrows];
+    PA_REQUIRE(nnz == 0 || (col && val), "pa_csr_create: null arrays");
+    for (int64_t k = 0; k < nnz; k++) PA_REQUIRE(col[k] >= 0 && col[k] < ncols, "pa_csr_create: column out of range");
+    PA_REQUIRE(!symmetric || nrows == ncols, "pa_csr_create: a symmetric matrix is square");
+    hipStream_t s = (hipStream_t)stream;
+    auto m = std::make_unique<pa_csr>();
+    m->nrows = nrows, m->ncols = ncols == nrows ? 0 : ncols, m->nnz = nnz, m->symmetric = symmetric != 0;
+    m->d_rowptr = dev_upload(rowptr, (size_t)nrows + 1, s);
+    m->d_col = dev_upload(col, (size_t)nnz, s);
+    m->d_val = dev_upload(val, (size_t)nnz, s);
+    *out = m.release();
+  });
+}
+
 void pa_csr_destroy(pa_csr *m) { delete m; }
 
 }  // extern "C"

@@ -196,6 +196,7 @@ Conforming::Conforming(const Context &ctx, int n_true, int n_local, const int *r
   d_t_slave_ = pa::dev_upload(t_slave.data(), t_slave.size(), ctx.stream);
   d_t_val_ = pa::dev_upload(t_val.data(), t_val.size(), ctx.stream);
   d_touched_ = pa::dev_upload(touched.data(), touched.size(), ctx.stream);
+  d_t_slot_ = pa::dev_upload(slot.data(), slot.size(), ctx.stream);
 }
 
 Conforming::~Conforming() = default;

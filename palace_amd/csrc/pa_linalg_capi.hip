@@ -1188,6 +1188,27 @@ int pa_conform_restrict(pa_context *ctx, pa_conform *c, const double *ly, double
 int pa_conform_lanes(const pa_conform *c, int which) {
   return c ? (which ? c->conf->TransposeLanes() : c->conf->ForwardLanes()) : 0;
 }
+/* ---- the assembled triple product (pa_rap_conform.hip) ---------------------------------------------------------------- */
+int pa_csr_rap_conforming_timed(pa_context *ctx, const pa_csr *B, const pa_conform *test, const pa_conform *trial, int left_form,
+                                pa_csr **T, double *ms) {
+  return guarded([&] {
+    PA_REQUIRE(ctx && B && T, "null argument");
+    PA_REQUIRE(left_form == 0 || left_form == 1, "triple product: left_form is 0 (Galerkin) or 1 (injection)");
+    *T = RapConforming(ctx->ctx, *B, test ? test->conf.get() : nullptr, trial ? trial->conf.get() : nullptr,
+                       left_form ? RapLeft::INJECTION : RapLeft::GALERKIN, ms)
+             .release();
+  });
+}
+int pa_csr_rap_conforming(pa_context *ctx, const pa_csr *B, const pa_conform *test, const pa_conform *trial, int left_form,
+                          pa_csr **T) {
+  return pa_csr_rap_conforming_timed(ctx, B, test, trial, left_form, T, nullptr);
+}
+int pa_par_op_parallel_assemble(pa_par_op *A, int skip_zeros, pa_csr **T) {
+  return guarded([&] {
+    PA_REQUIRE(A && A->op && T, "null argument");
+    *T = A->op->ParallelAssemble(skip_zeros != 0).release();
+  });
+}
 int pa_par_op_create_conforming(pa_context *ctx, pa_op *local, int n_true, const int32_t *ess, int n_ess, int policy,
                                 pa_conform *conf, pa_par_op **A) {
   return guarded([&] {

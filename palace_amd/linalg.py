@@ -465,6 +465,28 @@ class Conforming:
             pass
 
 
+def rap_conforming(ctx: Context, csr, test=None, trial=None, injection=False, timings=None):
+    """Sparse triple product on the device (pa_csr_rap_conforming): T = L B P_trial with B a ceed.DeviceCsr [n_local_test x
+    n_local_trial], P_trial = [I; C] of the Conforming `trial` (None: the identity) and L = P_test^T (Galerkin) or, with
+    injection=True, the first n_true rows of the Conforming `test` (None: the identity).  Returns a ceed.DeviceCsr with sorted,
+    unique columns; repeated calls agree bitwise.  timings: a list that receives [symbolic ms, numeric ms]."""
+    from .ceed import DeviceCsr
+
+    L = _L()
+    L.pa_csr_rap_conforming.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    L.pa_csr_rap_conforming_timed.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    h = C.c_void_p()
+    th = test.handle if test is not None else None
+    rh = trial.handle if trial is not None else None
+    if timings is None:
+        _lib.check(L.pa_csr_rap_conforming(ctx.handle, csr.handle, th, rh, int(bool(injection)), C.byref(h)))
+    else:
+        ms = (C.c_double * 2)()
+        _lib.check(L.pa_csr_rap_conforming_timed(ctx.handle, csr.handle, th, rh, int(bool(injection)), C.byref(h), ms))
+        timings[:] = [ms[0], ms[1]]
+    return DeviceCsr(h)
+
+
 def _default_true(space):
     """True dofs of a space when the caller names none: all its dofs, or the unconstrained ones of an nchex.NCSpace."""
     return space.n_true if hasattr(space, "C") and hasattr(space, "n_true") else space.ndofs
@@ -529,6 +551,18 @@ class ParOperator:
         """ParOperator::MultTranspose (rap.cpp:236-275)."""
         _lib.check(_L().pa_par_op_mult_transpose(self.handle, C.c_void_p(x.data_ptr()), C.c_void_p(y.data_ptr())))
         return y
+
+    def parallel_assemble(self, skip_zeros=False):
+        """ParOperator::ParallelAssemble (rap.cpp:84-152) on one rank: P^T A P on true dofs as a ceed.DeviceCsr (the device
+        triple product where the operator has a conforming prolongation).  Essential dofs are not eliminated: wrap the result
+        in an AssembledParOperator with the same list, or pass the list to amg / ams."""
+        from .ceed import DeviceCsr
+
+        L = _L()
+        L.pa_par_op_parallel_assemble.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        h = C.c_void_p()
+        _lib.check(L.pa_par_op_parallel_assemble(self.handle, int(bool(skip_zeros)), C.byref(h)))
+        return DeviceCsr(h)
 
     def __del__(self):
         try:
