@@ -448,6 +448,11 @@ int pa_op_stream_affine(const pa_op *op, int32_t out[3]);
  * out[0] elements, out[1] column-separable elements found (affine ones included), out[2] elements in column batches; first
  * tensor H(curl) sub-operator; out[1] = out[2] = 0 when the form is off (PALACE_AMD_STREAM_COLUMN=0). */
 int pa_op_stream_column(const pa_op *op, int32_t out[3]);
+/* Compact-only form of the same kernel: when EVERY batch of the first tensor H(curl) sub-operator is an affine or a column batch,
+ * the kernel that runs never reads per-point D (one 8-byte request per component and lane, fewer registers, one more wave per
+ * SIMD where that was measured to pay; same bits as the general form).  1 if that form runs at the next apply, 0 if the general
+ * form does (a per-point batch, the affine / column forms off, or PALACE_AMD_STREAM_COMPACT=0, read at every apply), < 0: error. */
+int pa_op_stream_compact(const pa_op *op);
 /* The E^T gather of the first dense-table sub-operator (round 6): out[0] = 1 if its E-vector keeps the dofs of an ELEMENT together
  * (chosen at creation by timing the gather on both layouts: the rows by element are taken when they are at least 15 % faster;
  * spaces of fewer than 2^17 local dofs keep the rows by dof untimed; PALACE_AMD_DENSE_ELAYOUT=rows | block overrides), 0 for the rows

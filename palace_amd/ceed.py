@@ -548,6 +548,13 @@ class Operator:
         _lib.check(_lib.load().pa_op_stream_column(self.handle, out))
         return int(out[0]), int(out[1]), int(out[2])
 
+    def stream_compact(self):
+        """True when the streaming H(curl) hex kernel runs its compact-only form at the next apply (pa_op_stream_compact)."""
+        r = _lib.load().pa_op_stream_compact(self.handle)
+        if r < 0:
+            raise RuntimeError("pa_op_stream_compact failed")
+        return bool(r)
+
     def dense_gather_form(self):
         """(E-vector rows by element?, lanes per dof) of the first dense-table block's E^T gather (pa_op_dense_gather_form)."""
         out = (C.c_int32 * 2)()

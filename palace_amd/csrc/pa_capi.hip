@@ -1494,6 +1494,12 @@ int pa_op_stream_column(const pa_op *op, int32_t out[3]) {
       }
   });
 }
+int pa_op_stream_compact(const pa_op *op) {
+  if (!op) return -1;
+  for (const auto &so : op->subs)
+    if (so->fe_type == PA_FE_HCURL && so->qd) return nd_hex_stream_compact(*so) ? 1 : 0;
+  return 0;
+}
 int pa_op_dense_gather_form(const pa_op *op, int32_t out[2]) {
   return guarded([&] {
     PA_REQUIRE(op && out, "null argument");

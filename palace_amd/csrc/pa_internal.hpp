@@ -111,6 +111,9 @@ struct QData {
   DevBuf<double> d_col;
   std::vector<unsigned char> batch_col;
   int n_col_elems = 0, n_col_batch_elems = 0;  // column-separable elements found (affine ones included) / in column batches
+  // every batch of the padded element array is an affine or a column batch: the streaming kernel runs its compact-only form, which
+  // never reads `d` (pa_nd_hex_stream.hip: COMPACT; PALACE_AMD_STREAM_COMPACT=0 forces the general form)
+  bool all_compact = false;
 };
 
 // Geometry factor data (fem/mesh.hpp:27-69): double[ne][11][Q] in HBM.
@@ -353,6 +356,8 @@ struct SplitIO {
   double *yg;
 };
 bool nd_hex_stream_split_ok(const SubOp &so);
+// the block's streaming kernel runs its compact-only form (every batch affine or column; PALACE_AMD_STREAM_COMPACT, read per call)
+bool nd_hex_stream_compact(const SubOp &so);
 // the element kernel of any streaming block on the tables of `form` (H(curl) at three, four or five points; H1 blocks are passed
 // on to launch_h1_hex_stream)
 void launch_nd_hex_stream(const SubOp &so, const double *x, double *y, StreamForm form, hipStream_t s, const SplitIO *split = nullptr);

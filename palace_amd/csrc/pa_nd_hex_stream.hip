@@ -94,8 +94,16 @@ struct NDStreamArgs {
 // per element, 6 per lane), parked in the element's LDS strip after the forward passes, and every lane contracts them with its own
 // in-plane basis values into 27 partial sums P[k][c][v] (v: d/dxi, d/deta, value; k: node layer), from which the Jacobian at its
 // four points along the column costs 27 multiply-adds each.
-template <int P1, bool USE_U, bool USE_C, bool METRIC, int MINW, int GPOS, bool CPLX = false, bool SPLIT = false, int GEOMN = 0>
+// COMPACT (real forms; a mesh whose batches are all affine or column batches, QData::all_compact): the kernel never reads per-point D.
+// A batch requests ONE double per component and lane -- a column batch its r_c(t) of QData::d_col, an affine batch the half of the
+// element's first row of component c in QData::d_aff that its parity names, {r wz(0), r wz(1)}[t & 1] -- and forms the two values the
+// D stage reads (points 0 | 3 and 1 | 2 of the column: the rule is symmetric) right ahead of it: the same products r wq2[.] as the
+// general form for a column batch, the other half from lane t ^ 1 for an affine one.  Same bits as the general form for both kinds;
+// 6 | 7 | 12 registers of D in flight across the forward passes instead of 24 | 28 | 48.
+template <int P1, bool USE_U, bool USE_C, bool METRIC, int MINW, int GPOS, bool CPLX = false, bool SPLIT = false, int GEOMN = 0,
+          bool COMPACT = false>
 __global__ __launch_bounds__(64 * kWavesPerBlock, MINW) void nd_hex_stream_kernel(const NDStreamArgs<P1> a) {
+  static_assert(!COMPACT || (!CPLX && !GEOMN), "the compact-only form: real kernels on packed or metric data");
   static_assert(!CPLX || (USE_U && USE_C), "the complex form is built on the curl-curl + mass kernels");
   static_assert(!(CPLX && SPLIT), "no split-vector form of the complex kernel");
   static_assert(!GEOMN || (!USE_U && USE_C && !METRIC && !CPLX), "geometry from the nodes: the curl-curl kernel");
@@ -191,7 +199,8 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, MINW) void nd_hex_stream_kerne
   for (int r = 0; r < NPL; r++) asm volatile("" : "+v"(xv[r]));
   settle(pA);
 
-  d2v gq[GEOMN ? 1 : 2 * NG];
+  d2v gq[(GEOMN || COMPACT) ? 1 : 2 * NG];
+  double gr[COMPACT ? NG : 1];  // COMPACT: this lane's number of every component, in flight during the forward passes
   double xl[GEOMN ? 6 : 1];  // GEOMN: this lane's six of the element's 81 node coordinates, in flight during the forward passes
   auto load_xn = [&](const int ee, const int t) {
     const double *xp = a.xn + (size_t)ee * 81;
@@ -200,6 +209,15 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, MINW) void nd_hex_stream_kerne
   };
   auto load_q = [&](const int ee, const int t, const int kind) {  // kind: 2 affine batch, 1 column batch, 0 per-point data
     if (GEOMN) return load_xn(ee, t);  // (the nodes of the batch: consumed in its D stage)
+    if (COMPACT) {
+      // one instruction stream for both kinds of batch, as below: the wave-uniform kind selects base, lane offset and stride
+      constexpr int NS = METRIC ? 7 : NG;
+      const int rs = kind == 2 ? 4 : 16;
+      const double *g = kind == 2 ? a.qaff + ((size_t)ee * (4 * NS) + (t & 1)) : a.qcol + ((size_t)ee * (NS * 16) + t);
+#pragma unroll
+      for (int c = 0; c < NG; c++) gr[c] = __builtin_nontemporal_load(&g[rs * c]);
+      return;
+    }
     if (AFF && !(CPLX && !METRIC)) {
       // one instruction stream for the three kinds of batch (the counted waits below depend on the number of loads in flight): the
       // wave-uniform kind selects the base, the lane offset and the row stride.  Column batches: a component's 16 numbers are 8 pairs,
@@ -363,7 +381,25 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, MINW) void nd_hex_stream_kerne
     // D at the four points of this lane's column
     double wab = 1.0;  // affine batch: the in-plane weight w(ta) w(tb) its compact D leaves out (1: exact no-op otherwise)
     double wxy = 1.0;
-    if (AFF) {
+    double gv[COMPACT ? NG : 1][2];  // COMPACT: D of every component at points 0 | 3 and 1 | 2 of the column
+    if (COMPACT) {
+      const bool odd = t & 1;
+#pragma unroll
+      for (int c = 0; c < NG; c++) {
+        const double r = gr[c];
+        if (aff) {  // (wave-uniform) the element's row {r wz(0), r wz(1)}: this lane holds entry t & 1, its neighbour the other
+          const double o = __hiloint2double(__builtin_amdgcn_mov_dpp(__double2hiint(r), 0xB1, 0xF, 0xF, true),
+                                            __builtin_amdgcn_mov_dpp(__double2loint(r), 0xB1, 0xF, 0xF, true));  // quad_perm 1 0 3 2
+          gv[c][0] = odd ? o : r, gv[c][1] = odd ? r : o;
+        } else {  // the products of the general form's column batches
+          const bool inv = METRIC && c == 6;
+          gv[c][0] = r * (inv ? a.wqi2[0] : a.wq2[0]), gv[c][1] = r * (inv ? a.wqi2[1] : a.wq2[1]);
+        }
+      }
+      const double wa = (ta == 0 || ta == 3) ? a.wq2[0] : a.wq2[1], wb = (tb == 0 || tb == 3) ? a.wq2[0] : a.wq2[1];
+      wxy = wa * wb;
+      wab = aff ? wxy : 1.0;
+    } else if (AFF) {
       if (col) {
         // (wave-uniform) the per-point values of the column from this lane's number of every component: r wz(qz), the metric form's
         // component 6 r / wz(qz), into the places the per-point data is read from (wz(2) = wz(1), wz(3) = wz(0)).  Done here, where the
@@ -418,7 +454,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, MINW) void nd_hex_stream_kerne
         }
       } else {
 #pragma unroll
-        for (int c = 0; c < NG; c++) H[c] = gq[2 * c + (qz >> 1)][qz & 1];
+        for (int c = 0; c < NG; c++) H[c] = COMPACT ? gv[c][(qz == 0 || qz == 3) ? 0 : 1] : gq[2 * c + (qz >> 1)][qz & 1];
       }
       if (METRIC) {
         // H = (w / |detJ|) J^T J {00, 01, 02, 11, 12, 22}, H[6] = |detJ| / w:
@@ -816,24 +852,31 @@ static void stream_affine_setup(SubOp &so) {
   PA_HIP(hipGetLastError());
   std::vector<unsigned char> flag((size_t)nep, 0);
   PA_HIP(hipMemcpy(flag.data(), d_flag, (size_t)nep, hipMemcpyDeviceToHost));
+  // the pad elements of the last batch (zero rows in both tables, their x reads as zero, their results go to E-vector rows nobody
+  // gathers) take the kind of the elements they share the batch with
+  for (int e = ne; e < nep; e++) flag[e] = 3;
+  auto real_elems = [&](const int b) { return std::min(4, ne - 4 * b); };
   qd.wq2[0] = w[0], qd.wq2[1] = w[1];
   qd.batch_aff.assign((size_t)nep / 4, 0);
   if (enabled) {
     for (int e = 0; e < ne; e++) qd.n_aff_elems += flag[e] & 1;
     for (int b = 0; b < nep / 4; b++)
-      if (flag[4 * b] & flag[4 * b + 1] & flag[4 * b + 2] & flag[4 * b + 3] & 1) qd.batch_aff[b] = 1, qd.n_aff_batch_elems += 4;
+      if (flag[4 * b] & flag[4 * b + 1] & flag[4 * b + 2] & flag[4 * b + 3] & 1) qd.batch_aff[b] = 1, qd.n_aff_batch_elems += real_elems(b);
   }
   if (col_enabled) {
     qd.batch_col.assign((size_t)nep / 4, 0);
     for (int e = 0; e < ne; e++) qd.n_col_elems += (flag[e] >> 1) & 1;
     for (int b = 0; b < nep / 4; b++)
       if ((flag[4 * b] & flag[4 * b + 1] & flag[4 * b + 2] & flag[4 * b + 3] & 2) && !qd.batch_aff[b])
-        qd.batch_col[b] = 1, qd.n_col_batch_elems += 4;
+        qd.batch_col[b] = 1, qd.n_col_batch_elems += real_elems(b);
     if (qd.n_col_batch_elems == 0)
       qd.batch_col.clear();
     else
       qd.d_col = std::move(d_col);
   }
+  // every batch compact: the operators on this data run the form of the kernel that never reads per-point D (launch_p)
+  qd.all_compact = nep > 0;
+  for (int b = 0; b < nep / 4; b++) qd.all_compact = qd.all_compact && (qd.batch_aff[b] || (!qd.batch_col.empty() && qd.batch_col[b]));
   if (qd.n_aff_batch_elems == 0)
     qd.batch_aff.clear();
   else
@@ -932,7 +975,8 @@ void stream_set_essential(SubOp &so, const std::vector<char> &flag) {
   upload_runs(t, so, streamhost::gather_rows(so.ne, so.P, so.lsize, so.h_sidx.data(), flag.data(), false), flag.data());
 }
 
-template <int P1, bool U, bool C, bool METRIC, int MINW, int GPOS, bool CPLX = false, bool SPLIT = false, int GEOMN = 0>
+template <int P1, bool U, bool C, bool METRIC, int MINW, int GPOS, bool CPLX = false, bool SPLIT = false, int GEOMN = 0,
+          bool COMPACT = false>
 static void launch_gpos(const SubOp &so, NDStreamArgs<P1> &a, hipStream_t s) {
   using L = typename std::conditional<P1 == 3 && !CPLX && C && !U, NDLayoutInPlaceSwz3, NDLayout<P1, 4>>::type;  // (as in the kernel)
   for (int i = 0; i < HalfTab<P1, 4>::LEN; i++) a.tab.Bo[i] = so.Bo[i];
@@ -941,19 +985,18 @@ static void launch_gpos(const SubOp &so, NDStreamArgs<P1> &a, hipStream_t s) {
   constexpr int NPK = ((PP + 15) / 16 + 3) / 4;
   const size_t lds = sizeof(double) * (size_t)(kWavesPerBlock * 4) *
                      stream_lds_elem(L::ELEM_PAD + (PP + 1) / 2 + (NPK + 1) * 8 + 12 + (GEOMN ? 82 : 0));
-  // resident workgroups per CU: registers (MINW waves per SIMD), LDS (160 KB), at most 8
-  // workgroups per CU: what the registers (MINW waves per SIMD) and the LDS admit, and not more than the occupancy query
-  // says -- with a fixed stride a workgroup that had to queue would run after the others and double the time
+  // resident workgroups per CU: what the registers (MINW waves per SIMD) and the LDS (160 KB) admit, at most 8, and not more than
+  // the occupancy query says -- with a fixed stride a workgroup that had to queue would run after the others and double the time
   static const int wg_env = stream_env_int("PALACE_AMD_STREAM_WG");
   static const int per_cu_query =
-      std::min({stream_occupancy(nd_hex_stream_kernel<P1, U, C, METRIC, MINW, GPOS, CPLX, SPLIT, GEOMN>, 64 * kWavesPerBlock, lds, 8),
+      std::min({stream_occupancy(nd_hex_stream_kernel<P1, U, C, METRIC, MINW, GPOS, CPLX, SPLIT, GEOMN, COMPACT>, 64 * kWavesPerBlock, lds, 8),
                 MINW * 4 / kWavesPerBlock, (int)(160 * 1024 / lds), 8});
   if (CPLX) a.nbatch = (so.ne + 1) / 2;  // two elements times two parts per batch
   else a.nbatch = (so.ne + 3) / 4;
   if (a.nbatch == 0) return;
   a.chunk = (a.nbatch + 7) / 8;
   const int wgx = stream_wgx(wg_env > 0 ? wg_env : per_cu_query, a.chunk, kWavesPerBlock, false);
-  hipLaunchKernelGGL((nd_hex_stream_kernel<P1, U, C, METRIC, MINW, GPOS, CPLX, SPLIT, GEOMN>), dim3(8 * wgx), dim3(64 * kWavesPerBlock),
+  hipLaunchKernelGGL((nd_hex_stream_kernel<P1, U, C, METRIC, MINW, GPOS, CPLX, SPLIT, GEOMN, COMPACT>), dim3(8 * wgx), dim3(64 * kWavesPerBlock),
                      lds, s, a);
   PA_HIP(hipGetLastError());
 }
@@ -962,12 +1005,36 @@ static void launch_gpos(const SubOp &so, NDStreamArgs<P1> &a, hipStream_t s) {
 // for the kernels with a mass term (their index words are requested just before D and need time to arrive and to be
 // decoded; later = fewer live registers: 202 instead of 248 VGPRs for K + M at p = 3; measured on the 10M-dof case with the
 // run-compressed index: curl-curl 0.180 / 0.181 ms, K + M 0.187 / 0.185 ms, mass 0.168 / 0.156 ms for positions 1 / 2).
-template <int P1, bool U, bool C, bool METRIC, int MINW>
+// COMPACT: MINW is the general form's bound; the compact form is compiled for one more wave per SIMD where it needs no scratch
+// memory at that bound AND was measured faster there in every round of an alternating A / B:
+//   K + M, packed and metric, p = 1, 2: three waves instead of two
+//   metric curl-curl at p = 3: three instead of two
+// and keeps the bound elsewhere: K + M at p = 3 gains 4 % at two waves and nothing at three (168 registers); the packed curl-curl
+// kernel at p = 3 fits four waves without scratch only with x of the next batch requested one transposed component later, is not
+// faster there than the general form (its gain at three waves: 2 - 6 %) and rounds differently (the later request changes which
+// products the compiler contracts).
+template <int P1, bool U, bool C, bool METRIC, int MINW, bool COMPACT = false>
 static void launch_variant(const SubOp &so, NDStreamArgs<P1> &a, hipStream_t s) {
   constexpr int GPOS = U ? 2 : 1;
+  constexpr bool RAISE = COMPACT && C && ((U && P1 < 3) || (!U && METRIC && P1 == 3));
+  constexpr int W = RAISE ? 3 : MINW;
   if (a.nsplit >= 0)  // split vectors (one more instantiation per operator kind)
-    return launch_gpos<P1, U, C, METRIC, MINW, GPOS, false, true>(so, a, s);
-  launch_gpos<P1, U, C, METRIC, MINW, GPOS>(so, a, s);
+    return launch_gpos<P1, U, C, METRIC, W, GPOS, false, true, 0, COMPACT>(so, a, s);
+  launch_gpos<P1, U, C, METRIC, W, GPOS, false, false, 0, COMPACT>(so, a, s);
+}
+
+// The form for this launch: compact-only (nd_hex_stream_kernel, COMPACT) when every batch of the operator's q-data is an affine or
+// a column batch (QData::all_compact) and PALACE_AMD_STREAM_COMPACT is not 0 (read at every launch: A / B runs in one process),
+// the general form otherwise.
+bool nd_hex_stream_compact(const SubOp &so) {
+  if (!so.qd || !so.qd->all_compact || so.fe_type != PA_FE_HCURL || so.q1d != 4 || !so.d_idxc) return false;
+  const char *e = getenv("PALACE_AMD_STREAM_COMPACT");
+  return !(e && atoi(e) == 0);
+}
+template <int P1, bool U, bool C, bool METRIC, int MINW>
+static void launch_form(const SubOp &so, NDStreamArgs<P1> &a, hipStream_t s) {
+  if (nd_hex_stream_compact(so)) return launch_variant<P1, U, C, METRIC, MINW, true>(so, a, s);
+  launch_variant<P1, U, C, METRIC, MINW>(so, a, s);
 }
 
 template <int P1>
@@ -1003,16 +1070,16 @@ static void launch_p(const SubOp &so, const double *x, double *y, StreamForm for
         else launch_gpos<P1, false, true, false, 2, 1, false, false, (P1 == 3 ? 1 : 0)>(so, a, s);
         break;
       }
-      if (m) launch_variant<P1, false, true, true, (P1 == 3 ? 2 : 3)>(so, a, s); else launch_variant<P1, false, true, false, 3>(so, a, s);
+      if (m) launch_form<P1, false, true, true, (P1 == 3 ? 2 : 3)>(so, a, s); else launch_form<P1, false, true, false, 3>(so, a, s);
     } break;
     case PA_QF_HCURL_33:
-      if (m) launch_variant<P1, true, false, true, 3>(so, a, s); else launch_variant<P1, true, false, false, 3>(so, a, s);
+      if (m) launch_form<P1, true, false, true, 3>(so, a, s); else launch_form<P1, true, false, false, 3>(so, a, s);
       break;
     case PA_QF_HDIVMASS_33:
       // (packed D of both terms, anisotropic materials: twelve doubles per point, 96 registers of q-data per lane; round 5)
       // (metric form: compiled for two waves per SIMD at p = 3 and at the p-coarsened levels alike; three were measured)
-      if (m) launch_variant<P1, true, true, true, 2>(so, a, s);
-      else launch_variant<P1, true, true, false, 2>(so, a, s);
+      if (m) launch_form<P1, true, true, true, 2>(so, a, s);
+      else launch_form<P1, true, true, false, 2>(so, a, s);
       break;
     default: throw Error("QFunction not available for H(curl) hexahedra");
   }
