@@ -234,6 +234,8 @@ struct SubOp {
   DevBuf<int32_t> d_tent;   // [ne * P] signed positions into d_ye
   // streaming form (pa_nd_hex_stream.hip): run-compressed index words, byte slots, E^T by runs.  Shared by every form:
   DevBuf<uint32_t> d_idxc;  // [ne][kIdxWords] run-compressed sorted element -> dof index (pa_stream_host.hpp)
+  DevBuf<int32_t> d_idxp;   // [ne][16 ceil(P / 16)] the same index word by word (pack_index_plain): four-point H(curl) blocks whose
+                            // q-data is all compact (QData::all_compact), read by the compact-only form of the kernel
   bool stream_default = true;  // false: the tables exist for the split-vector apply only, y = A x keeps the one-shot kernel (H1, p < 3)
   std::vector<uint32_t> h_perm_s;  // slot + flag words as pack_index / pack_index_wide lay them out (host; the forms are edited copies)
   // three- and four-point H(curl) kernels: the slot words through a dictionary -- elements whose sorted -> tensor-order permutation

@@ -75,6 +75,7 @@ struct NDStreamArgs {
   const unsigned long long *xg_sel;
   double *yg;
   NDTab<P1, 4> tab;
+  const int32_t *idxp;    // COMPACT: [ne][NPL 16] plain sorted element -> dof index, dof or -1 - dof when flipped (pack_index_plain)
 };
 
 // GPOS: where x of the next batch is requested (1 / 2 after the first / second transposed component).  Later = fewer live
@@ -100,6 +101,11 @@ struct NDStreamArgs {
 // D stage reads (points 0 | 3 and 1 | 2 of the column: the rule is symmetric) right ahead of it: the same products r wq2[.] as the
 // general form for a column batch, the other half from lane t ^ 1 for an affine one.  Same bits as the general form for both kinds;
 // 6 | 7 | 12 registers of D in flight across the forward passes instead of 24 | 28 | 48.
+// The compact form also reads its index ready-made: one word per entry and lane from idxp (576 / 256 / 64 B per element at
+// p = 3 / 2 / 1 instead of the 128 B of the run-compressed block) -- no decode, no run-start table in LDS and no wave_sync on the
+// way from the index words to the x requests -- and keeps the index, slot and flag words of the batch in registers from the E stage
+// to the E^T stores (the registers the compact D freed) instead of parking them in an LDS side buffer: its LDS strip is the
+// contraction buffers alone.  The flags stay in flagw (they differ between the plain, masked and `all` copies; the table does not).
 template <int P1, bool USE_U, bool USE_C, bool METRIC, int MINW, int GPOS, bool CPLX = false, bool SPLIT = false, int GEOMN = 0,
           bool COMPACT = false>
 __global__ __launch_bounds__(64 * kWavesPerBlock, MINW) void nd_hex_stream_kernel(const NDStreamArgs<P1> a) {
@@ -127,9 +133,10 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, MINW) void nd_hex_stream_kerne
   using streamhost::kIdxWords;
   // LDS per element (doubles): contraction buffers + the batch's index and slot / flag words, kept for the E^T stores,
   // + the run starts of the next batch while its index is decoded
-  constexpr int LDS_SIDE = (PP + 1) / 2 + (NPK + 1) * 8;
+  // (COMPACT: none of the three -- the words stay in registers and the index needs no decode)
+  constexpr int LDS_SIDE = COMPACT ? 0 : (PP + 1) / 2 + (NPK + 1) * 8;
   constexpr int LDS_XN = GEOMN ? 82 : 0;  // the element's node coordinates (GEOMN)
-  constexpr int LDS_ELEM = stream_lds_elem(L::ELEM_PAD + LDS_SIDE + 12 + LDS_XN);
+  constexpr int LDS_ELEM = stream_lds_elem(L::ELEM_PAD + LDS_SIDE + (COMPACT ? 0 : 12) + LDS_XN);
   extern __shared__ __attribute__((aligned(16))) double smem[];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -151,6 +158,14 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, MINW) void nd_hex_stream_kerne
   auto load_idx = [&](const int bb, const int sub, const int t, int (&s)[NPL + 2], unsigned (&p)[NPK + 1]) {
     const int e = CPLX ? bb * 2 + (sub >> 1) : bb * 4 + sub;
     const uint32_t *ic = a.idxc + (size_t)e * kIdxWords;
+    if (COMPACT) {  // s[r]: the signed index of entry t + 16 r itself; the pattern number still rides in the compressed block
+      const int32_t *ip = a.idxp + ((size_t)e * (NPL * 16) + t);
+#pragma unroll
+      for (int r = 0; r < NPL; r++) s[r] = __builtin_nontemporal_load(&ip[16 * r]);
+      p[NPK] = __builtin_nontemporal_load(&a.flagw[(size_t)e * 16 + t]);
+      p[0] = __builtin_nontemporal_load(&ic[kIdxPattern]);
+      return;
+    }
 #pragma unroll
     for (int r = 0; r < NPL; r++) s[r] = (int)__builtin_nontemporal_load(&ic[r]);
     s[NPL] = (int)__builtin_nontemporal_load(&ic[kIdxStart0 + t]);
@@ -161,7 +176,26 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, MINW) void nd_hex_stream_kerne
   };
   // decodes the index of the batch in place (s[r] becomes dof | kEssBit | kExclBit, negative: -(1 + word), flipped) and
   // requests the raw x of the entries (essential entries are zeroed when staged).  stab: 20 ints of LDS of this element.
+  // COMPACT: s[r] is the signed index already and stays as it is (the pad entries of a partial last slice hold dof 0); the flags are
+  // read from the flag word where they are used.
   auto gather = [&](int (&s)[NPL + 2], unsigned (&p)[NPK + 1], double (&xv)[NPL], int *stab, const int t) {
+    if (COMPACT) {
+      // A basic-block boundary, for the rounding and nothing else (never taken: bend > b >= 0).  The general form's decode ends the
+      // block here with its `if (t < 4)`.  Products that two transposed components share (T_z CV[2] of components 0 and 1 in the
+      // curl-curl kernels: 16 at p = 3) are multiplied once in the first and ADDED in the second because the compiler contracts a
+      // product with a sum only inside one block; without the boundary it contracts those 16 and y moves in the last bits.
+      // (GPOS = 2, the kernels with a mass term: components 1 and 2 share no product, the same arithmetic with and without.)
+      if (GPOS == 1 && bend < 0) return;
+      const uint32_t *sl = a.slots + (size_t)p[0] * (NPK * 16) + t;
+#pragma unroll
+      for (int k = 0; k < NPK; k++) p[k] = sl[16 * k];
+#pragma unroll
+      for (int r = 0; r < NPL; r++) {
+        const int dof = s[r] >= 0 ? s[r] : -1 - s[r];
+        xv[r] = SPLIT ? (dof < a.nsplit ? xsel : xgh)[dof] : xsel[dof];
+      }
+      return;
+    }
     stab[t] = s[NPL];
     if (t < 4) stab[16 + t] = s[NPL + 1];
     wave_sync();
@@ -278,13 +312,15 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, MINW) void nd_hex_stream_kerne
     for (int r = 0; r < NPL; r++) {
       if (16 * r + 15 < PP || t + 16 * r < PP) {
         const int sv = sA[r], df = sv >= 0 ? sv : -1 - sv;
-        const double v = (df & kEssBit) ? 0.0 : xv[r];
+        const double v = (COMPACT ? (pA[NPK] >> (18 + r)) & 1u : df & kEssBit) ? 0.0 : xv[r];
         sm[(pA[r >> 2] >> (8 * (r & 3))) & 255u] = sv >= 0 ? v : -v;
-        side[t + 16 * r] = sv;
+        if (!COMPACT) side[t + 16 * r] = sv;
       }
     }
+    if (!COMPACT) {
 #pragma unroll
-    for (int k = 0; k <= NPK; k++) side[2 * ((PP + 1) / 2) + 16 * k + t] = (int)pA[k];
+      for (int k = 0; k <= NPK; k++) side[2 * ((PP + 1) / 2) + 16 * k + t] = (int)pA[k];
+    }
     wave_sync();
     double uin[3][NC];
 #pragma unroll
@@ -564,9 +600,25 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, MINW) void nd_hex_stream_kerne
 #pragma unroll
     for (int r = 0; r < NPL; r++) {
       const int m = (16 * r + 15 < PP) ? t + 16 * r : min(t + 16 * r, PP - 1), mt = m & 15, mr = m >> 4;
-      const unsigned fl = (unsigned)side[2 * ((PP + 1) / 2) + 16 * NPK + mt] >> (2 * mr);
-      const double v = sm[((unsigned)side[2 * ((PP + 1) / 2) + 16 * (mr >> 2) + mt] >> (8 * (mr & 3))) & 255u];
-      const int sv = side[m], df = sv >= 0 ? sv : -1 - sv, d = df & (kExclBit - 1);
+      unsigned wf, ws;  // the flag word, the slot word and the index word of entry m
+      int sv;
+      if (COMPACT) {
+        // from this lane's registers; a partial last slice: the lanes past the last entry take the words of the lane that holds it
+        // (mr = r there: the last entry lies in the last slice)
+        wf = pA[NPK], ws = pA[r >> 2], sv = sA[r];
+        if (!(16 * r + 15 < PP)) {
+          const int src = (lo & ~15) | ((PP - 1) & 15);
+          const unsigned of = __shfl(wf, src, 64), os = __shfl(ws, src, 64);
+          const int ov = __shfl(sv, src, 64);
+          if (t + 16 * r >= PP) wf = of, ws = os, sv = ov;
+        }
+      } else {
+        wf = (unsigned)side[2 * ((PP + 1) / 2) + 16 * NPK + mt], ws = (unsigned)side[2 * ((PP + 1) / 2) + 16 * (mr >> 2) + mt];
+        sv = side[m];
+      }
+      const unsigned fl = wf >> (2 * mr);
+      const double v = sm[(ws >> (8 * (mr & 3))) & 255u];
+      const int df = sv >= 0 ? sv : -1 - sv, d = df & (kExclBit - 1);
       double *yd = (CPLX && (sub & 1)) ? a.y1 : a.y;
       if (SPLIT) yd = d < a.nsplit ? a.y : a.yg;
       double *dst = (fl & 2u) ? yd + d : ((CPLX && (sub & 1)) ? a.ye1 : a.ye) + ((size_t)e * PP + m);
@@ -953,6 +1005,11 @@ void build_stream(SubOp &so) {
   }
   so.h_perm_s = pp;
   so.d_idxc = dev_upload(ic.data(), ic.size());
+  if (so.q1d == 4 && lane16_curl && so.qd->all_compact) {  // the compact-only form reads its index ready-made (nd_hex_stream_compact)
+    std::vector<int32_t> ip;
+    streamhost::pack_index_plain(ne, P, so.h_sidx.data(), ip);
+    so.d_idxp = dev_upload(ip.data(), ip.size());
+  }
   if (so.qd->metric || (so.iso && so.qf == PA_QF_HDIV_33 && so.geom->d_xnodes)) stream_element_coefficients(so);
   StreamTables &t = so.stream[kStreamPlain];
   t.d_flags = upload_flags(so, pp);
@@ -984,7 +1041,7 @@ static void launch_gpos(const SubOp &so, NDStreamArgs<P1> &a, hipStream_t s) {
   constexpr int PP = 3 * P1 * (P1 + 1) * (P1 + 1);
   constexpr int NPK = ((PP + 15) / 16 + 3) / 4;
   const size_t lds = sizeof(double) * (size_t)(kWavesPerBlock * 4) *
-                     stream_lds_elem(L::ELEM_PAD + (PP + 1) / 2 + (NPK + 1) * 8 + 12 + (GEOMN ? 82 : 0));
+                     stream_lds_elem(L::ELEM_PAD + (COMPACT ? 0 : (PP + 1) / 2 + (NPK + 1) * 8 + 12) + (GEOMN ? 82 : 0));  // (as in the kernel)
   // resident workgroups per CU: what the registers (MINW waves per SIMD) and the LDS (160 KB) admit, at most 8, and not more than
   // the occupancy query says -- with a fixed stride a workgroup that had to queue would run after the others and double the time
   static const int wg_env = stream_env_int("PALACE_AMD_STREAM_WG");
@@ -1027,7 +1084,7 @@ static void launch_variant(const SubOp &so, NDStreamArgs<P1> &a, hipStream_t s) 
 // a column batch (QData::all_compact) and PALACE_AMD_STREAM_COMPACT is not 0 (read at every launch: A / B runs in one process),
 // the general form otherwise.
 bool nd_hex_stream_compact(const SubOp &so) {
-  if (!so.qd || !so.qd->all_compact || so.fe_type != PA_FE_HCURL || so.q1d != 4 || !so.d_idxc) return false;
+  if (!so.qd || !so.qd->all_compact || so.fe_type != PA_FE_HCURL || so.q1d != 4 || !so.d_idxc || !so.d_idxp) return false;
   const char *e = getenv("PALACE_AMD_STREAM_COMPACT");
   return !(e && atoi(e) == 0);
 }
@@ -1042,7 +1099,7 @@ static void launch_p(const SubOp &so, const double *x, double *y, StreamForm for
   NDStreamArgs<P1> a{};  // (every field the chosen form does not use: zero)
   stream_set_split(a, split, so.lsize);
   a.ne = so.ne, a.nbatch = 0;
-  a.idxc = so.d_idxc;
+  a.idxc = so.d_idxc, a.idxp = so.d_idxp;
   a.flagw = so.stream[form].d_flags;
   a.slots = so.d_slots;
   a.qdata = so.qd->d;

@@ -110,6 +110,20 @@ inline bool pack_index(int ne, int P, int lsize, const int32_t *sidx, const uint
   return true;
 }
 
+// Plain element -> dof index of the compact-only four-point H(curl) kernel (pa_nd_hex_stream.hip, COMPACT): one word per entry,
+//   ip [nep][npl 16]   entry m = 16 r + t of element e is make_sub's signed sorted index itself: dof, or -1 - dof when flipped
+// 576 / 256 / 64 B per element at p = 3 / 2 / 1 against the 128 B of the compressed block, for no decode on the device.  Only the
+// sign moves into the table: the only-copy and essential flags stay in the flag words of pp, which differ between the plain, the
+// masked and the `all` form while this table serves all three.  The pad entries of a partial last slice and the pad elements read
+// dof 0, unflipped (their results: as for pack_index).
+inline void pack_index_plain(int ne, int P, const int32_t *sidx, std::vector<int32_t> &ip) {
+  const int nep = (ne + 3) & ~3, row = (P + 15) / 16 * 16;
+  ip.assign((size_t)nep * row, 0);
+  for (int e = 0; e < ne; e++)
+    for (int m = 0; m < P; m++) ip[(size_t)e * row + m] = sidx[(size_t)e * P + m];
+}
+inline int index_dof_plain(const int32_t *ip, int m) { return dof_of(ip[m]); }  // host model of the device's read (ip: the element's row)
+
 // ---- wide form: one element per 32 lanes (five points per direction, pa_nd_hex_stream5.hip) ----------------------------
 // The same idea with 32-entry slices, for elements of up to 320 entries (p = 4: P = 300).  Index block of an element,
 // kWideWords = 48 words, fetched by its 32 lanes with two loads and decoded from LDS:
