@@ -144,6 +144,13 @@ enum pa_conform_flags {
 };
 int pa_conform_restrict(pa_context *ctx, pa_conform *c, const double *ly, double *y_true, int flags, double a,
                         const uint8_t *ess_mask, const double *x_ess);
+/* The two products for both parts of a complex field in one launch each: C, the inverted index and the mask are read once.
+ * Either part is bit-identical to the one-vector call on it (same lanes, same summation order).  The outputs must not overlap
+ * each other or the inputs; y0 / y1 may be x_ess0 / x_ess1. */
+int pa_conform_prolongate2(pa_context *ctx, pa_conform *c, const double *x0, const double *x1, double *lx0, double *lx1,
+                           const uint8_t *ess_mask);
+int pa_conform_restrict2(pa_context *ctx, pa_conform *c, const double *ly0, const double *ly1, double *y0, double *y1, int flags,
+                         double a, const uint8_t *ess_mask, const double *x_ess0, const double *x_ess1);
 /* lanes that share one row of C (which = 0) or of C^T (1): a power of two sized from the longest row */
 int pa_conform_lanes(const pa_conform *c, int which);
 /* pa_par_op_create / pa_par_sum_op_create / pa_complex_par_op_create / pa_interp_create / pa_gradient_create with a conforming
@@ -466,6 +473,12 @@ int pa_gradient_create_conforming(pa_context *ctx, const pa_restriction_desc *h1
 int pa_curl_create(pa_context *ctx, const pa_restriction_desc *nd_restr, const pa_basis_desc *nd_basis,
                    const pa_restriction_desc *rt_restr, const pa_basis_desc *rt_basis, const double *Dg, pa_halo *nd_halo,
                    int n_true_nd, int n_true_rt, pa_interp **C);
+/* The discrete curl between constrained spaces on a mesh with hanging nodes: Mult = R_rt C_loc P_nd (the first n_true_rt rows of
+ * the local result: a constrained flux dof is its master's trace, which the curl of a conforming field reproduces),
+ * MultTranspose = P_nd^T C_loc^T R_rt^T with a zero-filled tail.  nd_conf is the Nedelec space's conforming prolongation. */
+int pa_curl_create_conforming(pa_context *ctx, const pa_restriction_desc *nd_restr, const pa_basis_desc *nd_basis,
+                              const pa_restriction_desc *rt_restr, const pa_basis_desc *rt_basis, const double *Dg,
+                              pa_conform *nd_conf, int n_true_nd, int n_true_rt, pa_interp **C);
 /* The same two operators for non-tensor elements (tetrahedra, ...): the element projection matrix
  * M [P_range][P_domain] (row-major) MFEM's GetTransferMatrix / discrete-gradient interpolator gives
  * (basis.cpp:132-150), with the native restrictions of both spaces.  When the range space has a dof

@@ -108,6 +108,16 @@ void require_one_rank(const FiniteElementSpaceHierarchy &fespaces) {
     PA_REQUIRE(!fespaces.GetFESpaceAtLevel(l).GetHalo(),
                "the multigrid (use_mg) flux projector runs on one rank: a level of the smooth space has a halo (use_mg = false "
                "takes spaces with halos)");
+  // (the RT / ND p-prolongation between spaces that both carry hanging-node constraints is not built)
+  for (std::size_t l = 0; l < fespaces.GetNumLevels(); l++)
+    PA_REQUIRE(!fespaces.GetFESpaceAtLevel(l).GetConforming(),
+               "the multigrid (use_mg) flux projector does not take a smooth space with hanging-node constraints: pass use_mg = false "
+               "(PCG + Jacobi on P^T M P)");
+}
+
+// true-dof vector -> L-vector through the hanging-node constraints: lv = P x
+void conform_to_lvector(const Context &ctx, const Conforming &c, const Vector &x, Vector &lv) {
+  c.Prolongate(x.Data(), lv.Data(), nullptr, ctx.stream);
 }
 
 }  // namespace
@@ -159,7 +169,7 @@ void FluxProjector::Init(const MaterialPropertyCoefficient &coeff, const FiniteE
     add_mass_integrator(m, scalar_flux);
     mass_ = m.PartialAssemble();
     M_ = std::make_unique<ParOperator>(*ctx_, *mass_, smooth_fespace.GetTrueVSize(), nullptr, 0,
-                                       ParOperator::DiagonalPolicy::DIAG_ONE, smooth_fespace.GetHalo());
+                                       ParOperator::DiagonalPolicy::DIAG_ONE, smooth_fespace.GetHalo(), smooth_fespace.GetConforming());
   } else {  // :136-147: one mass per level
     require_one_rank(*smooth_fespaces);
     BilinearForm m(smooth_fespace);
@@ -206,23 +216,32 @@ void FluxProjector::Init(const MaterialPropertyCoefficient &coeff, const FiniteE
   }
   pcg_->SetPreconditioner(*pc_);
   rhs_.SetSize(smooth_fespace.GetTrueVSize());
-  if (rhs_fespace.GetHalo()) lx_.SetSize(rhs_fespace.GetVSize());
-  if (smooth_fespace.GetHalo()) ly_.SetSize(smooth_fespace.GetVSize());
+  if (rhs_fespace.GetHalo() || rhs_fespace.GetConforming()) lx_.SetSize(rhs_fespace.GetVSize());
+  if (smooth_fespace.GetHalo() || smooth_fespace.GetConforming()) ly_.SetSize(smooth_fespace.GetVSize());
 }
 
 void FluxProjector::Mult(const Vector &x, Vector &y) const {
   PhaseRange range("Estimation / Solve");  // errorestimator.cpp:172
   PA_REQUIRE(x.Size() == rhs_space_->GetTrueVSize() && y.Size() == rhs_.Size(), "Invalid vector dimensions for FluxProjector::Mult!");
   // Flux as a ParOperator between two spaces (rap.cpp:207-220 without essential dofs): P_test^T A P_trial
+  // (on a mesh with hanging nodes P is the conforming prolongation of either space: the right-hand side is P_smooth^T Flux P_rhs x,
+  // the system matrix P^T M P with the Jacobi diagonal |P|^T diag, rap.cpp:163-175)
   const Halo *hx = rhs_space_->GetHalo(), *hy = smooth_->GetHalo();
+  const Conforming *cx = rhs_space_->GetConforming(), *cy = smooth_->GetConforming();
   const Vector *in = &x;
   if (hx) {
     Vector t(lx_.Data(), x.Size());
     linalg::Copy(*ctx_, x, t);
     hx->Prolongate(lx_.Data(), ctx_->stream);
     in = &lx_;
+  } else if (cx) {
+    conform_to_lvector(*ctx_, *cx, x, lx_);
+    in = &lx_;
   }
-  if (hy) {
+  if (cy) {
+    flux_->Mult(*in, ly_);
+    cy->Restrict(ly_.Data(), rhs_.Data(), 0, 1.0, nullptr, nullptr, ctx_->stream);
+  } else if (hy) {
     flux_->Mult(*in, ly_);
     hy->RestrictAdd(ly_.Data(), ctx_->stream);
     Vector t(ly_.Data(), rhs_.Size());
@@ -299,7 +318,9 @@ void FluxErrorEstimatorBase::AddErrorEstimates(const Vector &F, Vector &estimate
              "Invalid vector dimensions for the error estimate!");
   projector_.Mult(F, G_);
   // grid functions = L-vectors (GetProlongationMatrix()->Mult, :202-214): ghosts filled through the halos
+  // ... or, on a mesh with hanging nodes, the constrained dofs through the conforming prolongation
   const Halo *hf = fespace_.GetHalo(), *hg = smooth_fespace_.GetHalo();
+  const Conforming *cf = fespace_.GetConforming(), *cg = smooth_fespace_.GetConforming();
   Vector F_gf, G_gf;
   const double *pf = F.Data(), *pg = G_.Data();
   if (hf) {
@@ -308,6 +329,10 @@ void FluxErrorEstimatorBase::AddErrorEstimates(const Vector &F, Vector &estimate
     linalg::Copy(*ctx_, F, t);
     hf->Prolongate(F_gf.Data(), ctx_->stream);
     pf = F_gf.Data();
+  } else if (cf) {
+    F_gf.SetSize(fespace_.GetVSize());
+    conform_to_lvector(*ctx_, *cf, F, F_gf);
+    pf = F_gf.Data();
   }
   if (hg) {
     G_gf.SetSize(smooth_fespace_.GetVSize());
@@ -315,9 +340,13 @@ void FluxErrorEstimatorBase::AddErrorEstimates(const Vector &F, Vector &estimate
     linalg::Copy(*ctx_, G_, t);
     hg->Prolongate(G_gf.Data(), ctx_->stream);
     pg = G_gf.Data();
+  } else if (cg) {
+    G_gf.SetSize(smooth_fespace_.GetVSize());
+    conform_to_lvector(*ctx_, *cg, G_, G_gf);
+    pg = G_gf.Data();
   }
   check(pa_error_op_apply_add(integ_op_, pf, pg, estimates.Data(), ctx_->stream));
-  if (hf || hg) PA_HIP(hipStreamSynchronize(ctx_->stream));  // the temporaries go out of scope
+  if (hf || hg || cf || cg) PA_HIP(hipStreamSynchronize(ctx_->stream));  // the temporaries go out of scope
 }
 
 void FluxErrorEstimatorBase::AddErrorIndicator(const Vector &F, double Et, ErrorIndicator &indicator) const {
@@ -395,7 +424,8 @@ void ComplexFluxProjector::Init(const MaterialPropertyCoefficient &coeff, const 
     add_mass_integrator(m, scalar_flux);
     mass_ = m.PartialAssemble();
     // BuildLevelParOperator<ComplexOperator> (:50-65): the real mass matrix as the real part, no imaginary part
-    M_ = std::make_unique<ComplexParOperator>(*ctx_, mass_.get(), nullptr, smooth_fespace.GetTrueVSize(), smooth_fespace.GetHalo());
+    M_ = std::make_unique<ComplexParOperator>(*ctx_, mass_.get(), nullptr, smooth_fespace.GetTrueVSize(), smooth_fespace.GetHalo(),
+                                              smooth_fespace.GetConforming());
     finest_mass = mass_.get(), finest_M = M_.get();
   } else {  // :136-147
     require_one_rank(*smooth_fespaces);
@@ -421,7 +451,8 @@ void ComplexFluxProjector::Init(const MaterialPropertyCoefficient &coeff, const 
   pcg_->SetTol(tol);
   pcg_->SetAbsTol(std::numeric_limits<double>::epsilon());
   pcg_->SetMaxIter(max_it);
-  Mboth_ = std::make_unique<ComplexMassOperator>(*finest_mass, *finest_M, smooth_fespace.GetHalo() != nullptr);
+  Mboth_ = std::make_unique<ComplexMassOperator>(*ctx_, *finest_mass, *finest_M, smooth_fespace.GetHalo() != nullptr,
+                                                 smooth_fespaces ? nullptr : smooth_fespace.GetConforming());
   pcg_->SetOperator(*Mboth_);
   if (!smooth_fespaces) {
     pc_ = std::make_unique<ComplexJacobiSmoother>(*ctx_);
@@ -443,21 +474,33 @@ void ComplexFluxProjector::Init(const MaterialPropertyCoefficient &coeff, const 
   }
   pcg_->SetPreconditioner(*pc_);
   rhs_.SetSize(smooth_fespace.GetTrueVSize());
-  if (rhs_fespace.GetHalo()) lx_.SetSize(rhs_fespace.GetVSize());
-  if (smooth_fespace.GetHalo()) ly_.SetSize(smooth_fespace.GetVSize());
+  if (rhs_fespace.GetHalo() || rhs_fespace.GetConforming()) lx_.SetSize(rhs_fespace.GetVSize());
+  if (smooth_fespace.GetHalo() || smooth_fespace.GetConforming()) ly_.SetSize(smooth_fespace.GetVSize());
 }
 
 bool ComplexFluxProjector::FluxTwoRhs() const { return pa_op_two_rhs(flux_->Handle()) != 0; }
 
-ComplexMassOperator::ComplexMassOperator(const ceed::Operator &mass, const ComplexParOperator &par, bool has_halo)
-    : ComplexOperator(par.Height(), par.Width()), mass_(&mass), par_(&par), has_halo_(has_halo) {}
+ComplexMassOperator::ComplexMassOperator(const Context &ctx, const ceed::Operator &mass, const ComplexParOperator &par, bool has_halo,
+                                         const Conforming *conf)
+    : ComplexOperator(par.Height(), par.Width()), ctx_(&ctx), mass_(&mass), par_(&par), has_halo_(has_halo), conf_(conf) {
+  PA_REQUIRE(!conf || (conf->NumTrue() == par.Height() && conf->NumLocal() == mass.Height()),
+             "the conforming prolongation does not match the mass operator");
+  if (conf) lx_.SetSize(conf->NumLocal()), ly_.SetSize(conf->NumLocal());
+}
 
 // (with a streaming form two separate applies are the faster choice, as in ParOperator::Mult2)
 bool ComplexMassOperator::OnePass() const { return !has_halo_ && pa_op_two_rhs(mass_->Handle()) != 0 && !mass_->Streams(); }
 
 void ComplexMassOperator::Mult(const ComplexVector &x, ComplexVector &y) const {
   if (!OnePass()) return par_->Mult(x, y);
-  mass_->Mult2(x.Real(), x.Imag(), y.Real(), y.Imag());  // no essential dofs, no imaginary part: yr = M xr, yi = M xi
+  if (conf_) {  // P^T M P on both parts: three launches where the two real ParOperators take six
+    conf_->Prolongate2(x.Real().Data(), x.Imag().Data(), lx_.Real().Data(), lx_.Imag().Data(), nullptr, ctx_->stream);
+    mass_->Mult2(lx_.Real(), lx_.Imag(), ly_.Real(), ly_.Imag());
+    conf_->Restrict2(ly_.Real().Data(), ly_.Imag().Data(), y.Real().Data(), y.Imag().Data(), 0, 1.0, nullptr, nullptr, nullptr,
+                     ctx_->stream);
+  } else {
+    mass_->Mult2(x.Real(), x.Imag(), y.Real(), y.Imag());  // no essential dofs, no imaginary part: yr = M xr, yi = M xi
+  }
   one_pass_applies_++;
 }
 
@@ -466,13 +509,21 @@ void ComplexFluxProjector::Mult(const ComplexVector &x, ComplexVector &y) const 
   PA_REQUIRE(x.Size() == rhs_space_->GetTrueVSize() && y.Size() == rhs_.Size(),
              "Invalid vector dimensions for ComplexFluxProjector::Mult!");
   const Halo *hx = rhs_space_->GetHalo(), *hy = smooth_->GetHalo();
+  const Conforming *cx = rhs_space_->GetConforming(), *cy = smooth_->GetConforming();
   const Vector *in_r = &x.Real(), *in_i = &x.Imag();
   if (hx) {
     to_lvector(*ctx_, *hx, x.Real(), lx_.Real());
     to_lvector(*ctx_, *hx, x.Imag(), lx_.Imag());
     in_r = &lx_.Real(), in_i = &lx_.Imag();
+  } else if (cx) {  // both parts through P in one launch
+    cx->Prolongate2(x.Real().Data(), x.Imag().Data(), lx_.Real().Data(), lx_.Imag().Data(), nullptr, ctx_->stream);
+    in_r = &lx_.Real(), in_i = &lx_.Imag();
   }
-  if (hy) {
+  if (cy) {  // P_smooth^T Flux P_rhs x
+    flux_->Mult2(*in_r, *in_i, ly_.Real(), ly_.Imag());
+    cy->Restrict2(ly_.Real().Data(), ly_.Imag().Data(), rhs_.Real().Data(), rhs_.Imag().Data(), 0, 1.0, nullptr, nullptr, nullptr,
+                  ctx_->stream);
+  } else if (hy) {
     flux_->Mult2(*in_r, *in_i, ly_.Real(), ly_.Imag());
     for (Vector *part : {&ly_.Real(), &ly_.Imag()}) hy->RestrictAdd(part->Data(), ctx_->stream);
     Vector tr(ly_.Real().Data(), rhs_.Size()), ti(ly_.Imag().Data(), rhs_.Size());
@@ -514,6 +565,7 @@ void ComplexFluxErrorEstimatorBase::AddErrorEstimates(const ComplexVector &F, Ve
   projector_.Mult(F, G_);
   // both parts of F and G as L-vectors (:202-214), then one error integrator call for the two parts (:249-261)
   const Halo *hf = fespace_.GetHalo(), *hg = smooth_fespace_.GetHalo();
+  const Conforming *cf = fespace_.GetConforming(), *cg = smooth_fespace_.GetConforming();
   ComplexVector F_gf, G_gf;
   const double *pf[2] = {F.Real().Data(), F.Imag().Data()}, *pg[2] = {G_.Real().Data(), G_.Imag().Data()};
   if (hf) {
@@ -521,15 +573,23 @@ void ComplexFluxErrorEstimatorBase::AddErrorEstimates(const ComplexVector &F, Ve
     to_lvector(*ctx_, *hf, F.Real(), F_gf.Real());
     to_lvector(*ctx_, *hf, F.Imag(), F_gf.Imag());
     pf[0] = F_gf.Real().Data(), pf[1] = F_gf.Imag().Data();
+  } else if (cf) {
+    F_gf.SetSize(fespace_.GetVSize());
+    cf->Prolongate2(pf[0], pf[1], F_gf.Real().Data(), F_gf.Imag().Data(), nullptr, ctx_->stream);
+    pf[0] = F_gf.Real().Data(), pf[1] = F_gf.Imag().Data();
   }
   if (hg) {
     G_gf.SetSize(smooth_fespace_.GetVSize());
     to_lvector(*ctx_, *hg, G_.Real(), G_gf.Real());
     to_lvector(*ctx_, *hg, G_.Imag(), G_gf.Imag());
     pg[0] = G_gf.Real().Data(), pg[1] = G_gf.Imag().Data();
+  } else if (cg) {
+    G_gf.SetSize(smooth_fespace_.GetVSize());
+    cg->Prolongate2(pg[0], pg[1], G_gf.Real().Data(), G_gf.Imag().Data(), nullptr, ctx_->stream);
+    pg[0] = G_gf.Real().Data(), pg[1] = G_gf.Imag().Data();
   }
   check(pa_error_op_apply_add2(integ_op_, pf[0], pg[0], pf[1], pg[1], estimates.Data(), ctx_->stream));
-  if (hf || hg) PA_HIP(hipStreamSynchronize(ctx_->stream));  // the temporaries go out of scope
+  if (hf || hg || cf || cg) PA_HIP(hipStreamSynchronize(ctx_->stream));  // the temporaries go out of scope
 }
 
 void ComplexFluxErrorEstimatorBase::AddErrorIndicator(const ComplexVector &F, double Et, ErrorIndicator &indicator) const {

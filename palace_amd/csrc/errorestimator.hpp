@@ -78,6 +78,9 @@ struct MaterialTensors {
 // is the MultigridOperator of the levels' masses, the cycle one pre and one post step of 4th-kind Chebyshev of order 2 and one
 // native AMG cycle (strength threshold 0.8) on the fully assembled coarsest level; a one-level hierarchy gets the AMG alone.
 // One rank.
+// On a mesh with hanging nodes either space may carry a Conforming prolongation P (fem.hpp: SetConformingProlongation): the
+// right-hand side is then P_smooth^T Flux P_rhs x, M the ParOperator P^T M P, Jacobi its |P|^T diag (rap.cpp:163-175), and the
+// estimators prolongate F and G through P before the element integrator.  use_mg with a constrained smooth space is refused.
 
 // BoomerAmgSolver(1, 1, true, 0) with SetStrengthThresh(0.8) as the projectors' coarse solve (:81-82): one cycle of the native
 // AMG on the assembled matrix of the level it is given (a ParOperator or FespaceParOperator without a halo)
@@ -171,14 +174,20 @@ public:
 // part without essential dofs as two one-part applies; here, on one rank and where the mass operator has a two-vector kernel and
 // no streaming form (pa_op_two_rhs, pa_op_streams), both parts go through one ceed::Operator::Mult2.  Everything else, and the
 // diagonal, is the ComplexParOperator's.
+// On a smooth space with hanging-node constraints (conf) the one-pass route is P2, Mult2, P^T2 (Conforming::Prolongate2 /
+// Restrict2): three launches where the two real ParOperators of the ComplexParOperator take six.
 class ComplexMassOperator : public ComplexOperator {
+  const Context *ctx_;
   const ceed::Operator *mass_;
   const ComplexParOperator *par_;
   bool has_halo_;
+  const Conforming *conf_;
+  mutable ComplexVector lx_, ly_;
   mutable long one_pass_applies_ = 0;
 
 public:
-  ComplexMassOperator(const ceed::Operator &mass, const ComplexParOperator &par, bool has_halo);
+  ComplexMassOperator(const Context &ctx, const ceed::Operator &mass, const ComplexParOperator &par, bool has_halo,
+                      const Conforming *conf = nullptr);
   const Operator *Real() const override { return par_->Real(); }
   void AssembleDiagonal(ComplexVector &diag) const override { par_->AssembleDiagonal(diag); }
   void Mult(const ComplexVector &x, ComplexVector &y) const override;

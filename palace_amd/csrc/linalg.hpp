@@ -423,6 +423,11 @@ public:
   // value is x_ess[i] (FIX_ONE) or 0 (FIX_ZERO) instead.  y may be x_ess; y must not overlap ly.
   void Restrict(const double *ly, double *y, int flags, double a, const uint8_t *ess_mask, const double *x_ess,
                 hipStream_t stream) const;
+  // The same for the two parts of a complex field in one launch each: the index arrays, the values and the mask are read once;
+  // either part is bit-identical to the one-vector call on it.  The outputs must not overlap each other or the inputs.
+  void Prolongate2(const double *x0, const double *x1, double *lx0, double *lx1, const uint8_t *ess_mask, hipStream_t stream) const;
+  void Restrict2(const double *ly0, const double *ly1, double *y0, double *y1, int flags, double a, const uint8_t *ess_mask,
+                 const double *x_ess0, const double *x_ess1, hipStream_t stream) const;
 };
 
 // Sparse triple product with conforming prolongations on the device (pa_rap_conform.hip): T = L B P_trial with B a local CSR matrix

@@ -134,6 +134,137 @@ __global__ __launch_bounds__(kBlock) void k_conform_restrict(const int n_true, c
   }
 }
 
+// ---- both parts of a complex field in one launch ---------------------------------------------------------------------------
+// The same mapping (head blocks copy, one lane group per row, the butterfly of group_sum) with the index arrays, the values,
+// `touched` and the mask read once for two vectors.  Either part goes through the operations of the one-vector kernel in the
+// same order, so it is bit-identical to a one-vector launch on that part.
+template <bool VEC>
+__device__ __forceinline__ double2 load2(const double *p, const int i) {
+  if (VEC) return *reinterpret_cast<const double2 *>(p + i);
+  double2 v;
+  v.x = p[i], v.y = p[i + 1];
+  return v;
+}
+
+template <bool VEC>
+__device__ __forceinline__ void store2(double *p, const int i, const double2 v) {
+  if (VEC) {
+    *reinterpret_cast<double2 *>(p + i) = v;
+  } else {
+    p[i] = v.x, p[i + 1] = v.y;
+  }
+}
+
+template <int L, bool VEC>
+__global__ __launch_bounds__(kBlock) void k_conform_prolongate2(const int n_true, const int n_con, const int head_blocks,
+                                                                 const int *__restrict__ row_ptr, const int32_t *__restrict__ col,
+                                                                 const double *__restrict__ val, const double *__restrict__ x0,
+                                                                 const double *__restrict__ x1, const uint8_t *__restrict__ mask,
+                                                                 double *__restrict__ lx0, double *__restrict__ lx1) {
+  if ((int)blockIdx.x < head_blocks) {
+    const int i = 2 * ((int)blockIdx.x * kBlock + (int)threadIdx.x);
+    if (i + 1 < n_true) {
+      double2 v0 = load2<VEC>(x0, i), v1 = load2<VEC>(x1, i);
+      if (mask) {
+        if (mask[i] & 1) v0.x = 0.0, v1.x = 0.0;
+        if (mask[i + 1] & 1) v0.y = 0.0, v1.y = 0.0;
+      }
+      store2<VEC>(lx0, i, v0);
+      store2<VEC>(lx1, i, v1);
+    } else if (i < n_true) {
+      const bool m = mask && (mask[i] & 1);
+      lx0[i] = m ? 0.0 : x0[i];
+      lx1[i] = m ? 0.0 : x1[i];
+    }
+    return;
+  }
+  const int lane = (int)threadIdx.x % L;
+  const int r = ((int)blockIdx.x - head_blocks) * (kBlock / L) + (int)threadIdx.x / L;
+  double s0 = 0.0, s1 = 0.0;
+  if (r < n_con) {
+    const int e = row_ptr[r + 1];
+    for (int k = row_ptr[r] + lane; k < e; k += L) {
+      const int j = col[k];
+      const bool m = mask && (mask[j] & 1);
+      const double v = val[k];
+      const double xj0 = m ? 0.0 : x0[j];
+      const double xj1 = m ? 0.0 : x1[j];
+      s0 += v * xj0;
+      s1 += v * xj1;
+    }
+  }
+  s0 = group_sum<L>(s0);
+  s1 = group_sum<L>(s1);
+  if (r < n_con && lane == 0) lx0[n_true + r] = s0, lx1[n_true + r] = s1;
+}
+
+template <int L, bool VEC>
+__global__ __launch_bounds__(kBlock) void k_conform_restrict2(const int n_true, const int n_touched, const int head_blocks,
+                                                               const int *__restrict__ t_ptr, const int32_t *__restrict__ t_dof,
+                                                               const int32_t *__restrict__ t_slave, const double *__restrict__ t_val,
+                                                               const uint8_t *__restrict__ touched, const double *__restrict__ ly0,
+                                                               const double *__restrict__ ly1, const int flags, const double a,
+                                                               const uint8_t *__restrict__ mask, const double *x_ess0,
+                                                               const double *x_ess1, double *y0, double *y1) {
+  if ((int)blockIdx.x < head_blocks) {
+    const int i = 2 * ((int)blockIdx.x * kBlock + (int)threadIdx.x);
+    if (i + 1 < n_true) {
+      double2 v0 = load2<VEC>(ly0, i), v1 = load2<VEC>(ly1, i);
+      const bool t0 = touched[i] != 0, t1 = touched[i + 1] != 0;
+      if (!t0) {
+        v0.x = restrict_value(v0.x, i, flags, a, mask, x_ess0, y0);
+        v1.x = restrict_value(v1.x, i, flags, a, mask, x_ess1, y1);
+      }
+      if (!t1) {
+        v0.y = restrict_value(v0.y, i + 1, flags, a, mask, x_ess0, y0);
+        v1.y = restrict_value(v1.y, i + 1, flags, a, mask, x_ess1, y1);
+      }
+      if (VEC && !t0 && !t1) {
+        store2<true>(y0, i, v0);
+        store2<true>(y1, i, v1);
+      } else {
+        if (!t0) y0[i] = v0.x, y1[i] = v1.x;
+        if (!t1) y0[i + 1] = v0.y, y1[i + 1] = v1.y;
+      }
+    } else if (i < n_true) {
+      if (!touched[i]) {
+        y0[i] = restrict_value(ly0[i], i, flags, a, mask, x_ess0, y0);
+        y1[i] = restrict_value(ly1[i], i, flags, a, mask, x_ess1, y1);
+      }
+    }
+    return;
+  }
+  const int lane = (int)threadIdx.x % L;
+  const int t = ((int)blockIdx.x - head_blocks) * (kBlock / L) + (int)threadIdx.x / L;
+  double s0 = 0.0, s1 = 0.0;
+  if (t < n_touched) {
+    const int e = t_ptr[t + 1];
+    const double *tail0 = ly0 + n_true, *tail1 = ly1 + n_true;
+    if (flags & Conforming::ABS) {
+      for (int k = t_ptr[t] + lane; k < e; k += L) {
+        const double v = fabs(t_val[k]);
+        const int sl = t_slave[k];
+        s0 += v * tail0[sl];
+        s1 += v * tail1[sl];
+      }
+    } else {
+      for (int k = t_ptr[t] + lane; k < e; k += L) {
+        const double v = t_val[k];
+        const int sl = t_slave[k];
+        s0 += v * tail0[sl];
+        s1 += v * tail1[sl];
+      }
+    }
+  }
+  s0 = group_sum<L>(s0);
+  s1 = group_sum<L>(s1);
+  if (t < n_touched && lane == 0) {
+    const int i = t_dof[t];
+    y0[i] = restrict_value(ly0[i] + s0, i, flags, a, mask, x_ess0, y0);
+    y1[i] = restrict_value(ly1[i] + s1, i, flags, a, mask, x_ess1, y1);
+  }
+}
+
 int lanes_for(int longest) {
   int l = 1;
   while (l < longest && l < 32) l *= 2;
@@ -141,6 +272,9 @@ int lanes_for(int longest) {
 }
 
 bool aligned16(const void *a, const void *b) { return (((uintptr_t)a | (uintptr_t)b) & 15) == 0; }
+
+// true when [a, a + na) and [b, b + nb) share an element
+bool overlap(const double *a, size_t na, const double *b, size_t nb) { return a && b && a < b + nb && b < a + na; }
 
 }  // namespace
 
@@ -244,6 +378,74 @@ void Conforming::Restrict(const double *ly, double *y, int flags, double a, cons
 #define PA_CONFORM_CASE(L)                                                     \
   case L:                                                                      \
     vec ? launch(k_conform_restrict<L, true>, L) : launch(k_conform_restrict<L, false>, L); \
+    break;
+  switch (tr_lanes_) {
+    PA_CONFORM_CASE(1)
+    PA_CONFORM_CASE(2)
+    PA_CONFORM_CASE(4)
+    PA_CONFORM_CASE(8)
+    PA_CONFORM_CASE(16)
+    PA_CONFORM_CASE(32)
+    default: throw pa::Error("conforming restriction: bad lane count");
+  }
+#undef PA_CONFORM_CASE
+  PA_HIP(hipGetLastError());
+}
+
+void Conforming::Prolongate2(const double *x0, const double *x1, double *lx0, double *lx1, const uint8_t *ess_mask,
+                             hipStream_t stream) const {
+  if (n_true_ + n_con_ == 0) return;
+  const size_t nt = (size_t)n_true_, nl = nt + n_con_;
+  PA_REQUIRE(!overlap(lx0, nl, lx1, nl) && !overlap(lx0, nl, x0, nt) && !overlap(lx0, nl, x1, nt) && !overlap(lx1, nl, x0, nt) &&
+                 !overlap(lx1, nl, x1, nt),
+             "conforming prolongation of two vectors: the outputs must not overlap each other or the inputs");
+  const int head = ((n_true_ + 1) / 2 + kBlock - 1) / kBlock;
+  const bool vec = aligned16(x0, lx0) && aligned16(x1, lx1);
+  auto launch = [&](auto kernel, int lanes) {
+    const int rows_per_block = kBlock / lanes;
+    const int grid = head + (n_con_ + rows_per_block - 1) / rows_per_block;
+    if (grid == 0) return;
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), 0, stream, n_true_, n_con_, head, d_row_ptr_, d_col_, d_val_, x0, x1, ess_mask,
+                       lx0, lx1);
+  };
+#define PA_CONFORM_CASE(L)                                                           \
+  case L:                                                                            \
+    vec ? launch(k_conform_prolongate2<L, true>, L) : launch(k_conform_prolongate2<L, false>, L); \
+    break;
+  switch (fwd_lanes_) {
+    PA_CONFORM_CASE(1)
+    PA_CONFORM_CASE(2)
+    PA_CONFORM_CASE(4)
+    PA_CONFORM_CASE(8)
+    PA_CONFORM_CASE(16)
+    PA_CONFORM_CASE(32)
+    default: throw pa::Error("conforming prolongation: bad lane count");
+  }
+#undef PA_CONFORM_CASE
+  PA_HIP(hipGetLastError());
+}
+
+void Conforming::Restrict2(const double *ly0, const double *ly1, double *y0, double *y1, int flags, double a, const uint8_t *ess_mask,
+                           const double *x_ess0, const double *x_ess1, hipStream_t stream) const {
+  if (n_true_ == 0) return;
+  PA_REQUIRE(!((flags & FIX_ONE) && ess_mask) || (x_ess0 && x_ess1),
+             "conforming restriction: FIX_ONE needs the vectors the essential rows copy");
+  PA_REQUIRE(!((flags & FIX_ONE) && (flags & FIX_ZERO)), "conforming restriction: one policy for the essential rows");
+  const size_t nt = (size_t)n_true_, nl = nt + n_con_;
+  PA_REQUIRE(!overlap(y0, nt, y1, nt) && !overlap(y0, nt, ly0, nl) && !overlap(y0, nt, ly1, nl) && !overlap(y1, nt, ly0, nl) &&
+                 !overlap(y1, nt, ly1, nl),
+             "conforming restriction of two vectors: the outputs must not overlap each other or the inputs");
+  const int head = ((n_true_ + 1) / 2 + kBlock - 1) / kBlock;
+  const bool vec = aligned16(ly0, y0) && aligned16(ly1, y1);
+  auto launch = [&](auto kernel, int lanes) {
+    const int rows_per_block = kBlock / lanes;
+    const int grid = head + (n_touched_ + rows_per_block - 1) / rows_per_block;
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), 0, stream, n_true_, n_touched_, head, d_t_ptr_, d_t_dof_, d_t_slave_, d_t_val_,
+                       d_touched_, ly0, ly1, flags, a, ess_mask, x_ess0, x_ess1, y0, y1);
+  };
+#define PA_CONFORM_CASE(L)                                                       \
+  case L:                                                                        \
+    vec ? launch(k_conform_restrict2<L, true>, L) : launch(k_conform_restrict2<L, false>, L); \
     break;
   switch (tr_lanes_) {
     PA_CONFORM_CASE(1)

@@ -1185,6 +1185,21 @@ int pa_conform_restrict(pa_context *ctx, pa_conform *c, const double *ly, double
     c->conf->Restrict(ly, y, flags, a, ess_mask, x_ess, ctx->ctx.stream);
   });
 }
+int pa_conform_prolongate2(pa_context *ctx, pa_conform *c, const double *x0, const double *x1, double *lx0, double *lx1,
+                           const uint8_t *ess_mask) {
+  return guarded([&] {
+    PA_REQUIRE(ctx && c && x0 && x1 && lx0 && lx1, "null argument");
+    c->conf->Prolongate2(x0, x1, lx0, lx1, ess_mask, ctx->ctx.stream);
+  });
+}
+int pa_conform_restrict2(pa_context *ctx, pa_conform *c, const double *ly0, const double *ly1, double *y0, double *y1, int flags,
+                         double a, const uint8_t *ess_mask, const double *x_ess0, const double *x_ess1) {
+  return guarded([&] {
+    PA_REQUIRE(ctx && c && ly0 && ly1 && y0 && y1, "null argument");
+    PA_REQUIRE((flags & ~(PA_CONFORM_ADD | PA_CONFORM_ABS | PA_CONFORM_FIX_ONE | PA_CONFORM_FIX_ZERO)) == 0, "unknown flag");
+    c->conf->Restrict2(ly0, ly1, y0, y1, flags, a, ess_mask, x_ess0, x_ess1, ctx->ctx.stream);
+  });
+}
 int pa_conform_lanes(const pa_conform *c, int which) {
   return c ? (which ? c->conf->TransposeLanes() : c->conf->ForwardLanes()) : 0;
 }
@@ -1284,6 +1299,16 @@ int pa_gradient_create_conforming(pa_context *ctx, const pa_restriction_desc *rh
     p->ctx = ctx;
     p->op.reset(make_conforming_interp_operator(ctx->ctx, *rh, *bh, *rn, *bn, I.data(), Dg, h1_conf->conf.get(), nt_h1, nt_nd, 1));
     *G = p.release();
+  });
+}
+int pa_curl_create_conforming(pa_context *ctx, const pa_restriction_desc *rn, const pa_basis_desc *bn, const pa_restriction_desc *rr,
+                              const pa_basis_desc *br, const double *Dg, pa_conform *nd_conf, int nt_nd, int nt_rt, pa_interp **Cu) {
+  return guarded([&] {
+    PA_REQUIRE(ctx && rn && bn && rr && br && Dg && nd_conf && Cu, "null argument");
+    auto p = std::make_unique<pa_interp>();
+    p->ctx = ctx;
+    p->op.reset(make_conforming_interp_operator(ctx->ctx, *rn, *bn, *rr, *br, nullptr, Dg, nd_conf->conf.get(), nt_nd, nt_rt, 2));
+    *Cu = p.release();
   });
 }
 int pa_curl_create(pa_context *ctx, const pa_restriction_desc *rn, const pa_basis_desc *bn, const pa_restriction_desc *rr,

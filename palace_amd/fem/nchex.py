@@ -1,5 +1,5 @@
-"""Nonconforming (hanging-node) hexahedral meshes and their constrained H(curl) / H1 spaces: the host stand-in for what the
-reference gets from MFEM's NCMesh when `Refinement.Nonconformal` is on (utils/geodata.cpp:174-186: tensor elements are only
+"""Nonconforming (hanging-node) hexahedral meshes and their constrained H(curl) / H1 / H(div) spaces: the host stand-in for what
+the reference gets from MFEM's NCMesh when `Refinement.Nonconformal` is on (utils/geodata.cpp:174-186: tensor elements are only
 ever refined this way; `MaxNCLevels = 1`, utils/configfile.hpp:111-116) -- local refinement of hex27 elements, the
 master / slave faces and edges of the one-irregular result, the conforming prolongation P = [I; C] of an NDHexSpace or
 H1HexSpace on it (every ParOperator of the reference is then P^T A P, linalg/rap.cpp:65, :212-216) and the Doerfler marking of
@@ -14,6 +14,9 @@ master element's trace evaluated at the slave's node.  On the shared entity the 
 an affine map with factor 1/2 that is read off the node ids (a slave's corners are lattice nodes of the master element), so no
 face-frame class has to be enumerated: along the tangent of a covariant dof the open basis on the half interval scaled by
 1/2, along every other direction the closed basis on the half interval -- the 1-D matrices of htransfer.hex_child_matrices.
+A Raviart-Thomas space (RTHexSpace) has dofs on faces and interiors only, so just the p^2 normal-flux dofs of a slave face are
+constrained: the master's normal flux density at the slave node (closed basis along the master's normal, open along the two
+tangents) times the determinant +-1/4 of the map between the two reference faces, the contravariant Piola factor.
 """
 from __future__ import annotations
 
@@ -25,6 +28,7 @@ from .basis1d import gauss_legendre, gauss_lobatto
 from .fespace import _VERT_IJK, H1HexSpace, NDHexSpace
 from .htransfer import hex_child_matrices
 from .mesh import _CORNER_LATTICE, HEX_EDGES, HEX_FACE_AXES, HEX_FACES_UV, HexMesh, _merge_points, _q2_1d
+from .rthex import RTHexSpace
 
 # lattice index of the mid node of every local edge / face, and of the four edge mid nodes of every local face in the order
 # (u at v = 0, u at v = 1, v at u = 0, v at u = 1) of its (c00, c10, c01, c11) corners
@@ -241,8 +245,8 @@ def _lagrange(nodes, x):
 
 
 class _NCSpaceMixin:
-    """An NDHexSpace / H1HexSpace on an NCHexMesh, renumbered so that its true dofs come first and its constrained dofs last
-    (the layout of pa_halo_create: true dofs [0, n_true), then the rest), with the conforming prolongation P = [I; C].
+    """An NDHexSpace / H1HexSpace / RTHexSpace on an NCHexMesh, renumbered so that its true dofs come first and its constrained
+    dofs last (the layout of pa_halo_create: true dofs [0, n_true), then the rest), with the conforming prolongation P = [I; C].
 
     elem_dof_lex (and elem_sign_lex), ndofs = n_local, n_true, C [n_local - n_true, n_true] (scipy CSR), ess_dofs() as true-dof
     indices on the corrected boundary mask, broken_perm [n_local]: the wrapped space's dof d is dof broken_perm[d] here."""
@@ -251,16 +255,16 @@ class _NCSpaceMixin:
         import scipy.sparse as sp
 
         mesh, p = self.mesh, self.p
-        hcurl = isinstance(self, NDHexSpace)
+        hcurl, hdiv = isinstance(self, NDHexSpace), isinstance(self, RTHexSpace)
         nc = mesh._nc() if isinstance(mesh, NCHexMesh) else None
         cp = gauss_lobatto(p + 1)
-        op = gauss_legendre(p)[0] if hcurl else None
+        op = gauss_legendre(p)[0] if hcurl or hdiv else None
         # reference position and direction of every local dof
-        if hcurl:
+        if hcurl or hdiv:
             xi, comp = [], []
             for c in range(3):
-                nodes = [cp, cp, cp]
-                nodes[c] = op
+                nodes = [op, op, op] if hdiv else [cp, cp, cp]
+                nodes[c] = cp if hdiv else op
                 K, J, I = np.meshgrid(np.arange(nodes[2].size), np.arange(nodes[1].size), np.arange(nodes[0].size), indexing="ij")
                 xi.append(np.stack([nodes[0][I.ravel()], nodes[1][J.ravel()], nodes[2][K.ravel()]], axis=1))
                 comp.append(np.full(I.size, c))
@@ -268,7 +272,7 @@ class _NCSpaceMixin:
         else:
             K, J, I = np.meshgrid(np.arange(p + 1), np.arange(p + 1), np.arange(p + 1), indexing="ij")
             xi, comp = np.stack([cp[I.ravel()], cp[J.ravel()], cp[K.ravel()]], axis=1), None
-        sign = self.elem_sign_lex.astype(np.float64) if hcurl else None
+        sign = self.elem_sign_lex.astype(np.float64) if hcurl or hdiv else None
         rows = {}  # constrained (broken) dof -> (columns, values)
 
         def trace_rows(M, S, axes, origin, ldofs):
@@ -296,6 +300,20 @@ class _NCSpaceMixin:
                     f = [Bo[d] if d == c else Bc[d] for d in range(3)]
                     blocks.append(tan[:, c, None] * np.einsum("nk,nj,ni->nkji", f[2], f[1], f[0]).reshape(len(ldofs), -1))
                 R = np.concatenate(blocks, axis=1) * sign[M][None, :] * sign[S, ldofs][:, None]
+            elif hdiv:
+                # normal flux density of M's field on the face: block mn of M (closed along its normal mn, open along the
+                # two tangents) times the contravariant Piola factor det(A_face) = +-1/4 between the two reference faces,
+                # both taken with ascending-axis tangents, and the sign e_u x e_v = eps e_n of either reference normal
+                uax, vax = axes
+                tm = [d for d in range(3) if np.any(A[d] != 0.0)]
+                mn = 3 - sum(tm)
+                det = np.linalg.det(A[np.ix_(tm, [uax, vax])]) * (-1.0 if uax > vax else 1.0)
+                eps = (-1.0 if mn == 1 else 1.0) * (-1.0 if 3 - uax - vax == 1 else 1.0)
+                f = [Bc[d] if d == mn else _lagrange(op, xm[:, d]) for d in range(3)]
+                R = np.zeros((len(ldofs), self.P))
+                nblk = p * p * (p + 1)
+                R[:, mn * nblk:(mn + 1) * nblk] = eps * det * np.einsum("nk,nj,ni->nkji", f[2], f[1], f[0]).reshape(len(ldofs), -1)
+                R = R * sign[M][None, :] * sign[S, ldofs][:, None]
             else:
                 R = np.einsum("nk,nj,ni->nkji", Bc[2], Bc[1], Bc[0]).reshape(len(ldofs), -1)
             gm = self.elem_dof_lex[M]
@@ -317,11 +335,11 @@ class _NCSpaceMixin:
                 M, _ = nc["mfaces"][int(nc["face_master"][f])]
                 S, lf = nc["face_elem"][f]
                 nax, side, uax, vax = HEX_FACE_AXES[lf]
-                sel = on(nax, side) & ((comp != nax) if hcurl else True)
+                sel = on(nax, side) & ((comp != nax) if hcurl else (comp == nax) if hdiv else True)
                 origin = [0, 0, 0]
                 origin[nax] = 2 * side
                 trace_rows(M, int(S), (uax, vax), origin, np.nonzero(sel)[0])
-            for e in np.nonzero(nc["edge_master"] >= 0)[0]:
+            for e in np.nonzero(nc["edge_master"] >= 0)[0] if not hdiv else ():
                 M, _ = nc["medges"][int(nc["edge_master"][e])]
                 S, le = nc["edge_elem"][e]
                 a, b = HEX_EDGES[le]
@@ -373,11 +391,18 @@ class NCH1HexSpace(_NCSpaceMixin, H1HexSpace):
     pass
 
 
+class NCRTHexSpace(_NCSpaceMixin, RTHexSpace):
+    """Only the p^2 normal-flux dofs of a slave face are constrained; RT has no edge or vertex dofs and no essential dofs."""
+
+    def ess_dofs(self, *args, **kw):
+        return np.zeros(0, dtype=np.int64)
+
+
 def NCSpace(space):
-    """The constrained form of an NDHexSpace or H1HexSpace (orders 1 to 5) built on an NCHexMesh; a conforming mesh gives a
-    space with zero constraints."""
-    cls = NCNDHexSpace if isinstance(space, NDHexSpace) else NCH1HexSpace
-    assert isinstance(space, (NDHexSpace, H1HexSpace)) and not isinstance(space, _NCSpaceMixin)
+    """The constrained form of an NDHexSpace, H1HexSpace or RTHexSpace (orders 1 to 5) built on an NCHexMesh; a conforming
+    mesh gives a space with zero constraints."""
+    cls = NCNDHexSpace if isinstance(space, NDHexSpace) else NCRTHexSpace if isinstance(space, RTHexSpace) else NCH1HexSpace
+    assert isinstance(space, (NDHexSpace, H1HexSpace, RTHexSpace)) and not isinstance(space, _NCSpaceMixin)
     out = cls.__new__(cls)
     out.__dict__.update(space.__dict__)
     out.broken = space

@@ -434,6 +434,8 @@ class Conforming:
         L.pa_conform_prolongate.argtypes = [C.c_void_p] * 5
         L.pa_conform_restrict.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_void_p]
         L.pa_conform_lanes.argtypes = [C.c_void_p, C.c_int]
+        L.pa_conform_prolongate2.argtypes = [C.c_void_p] * 7
+        L.pa_conform_restrict2.argtypes = [C.c_void_p] * 6 + [C.c_int, C.c_double] + [C.c_void_p] * 3
         _lib.check(L.pa_conform_create(ctx.handle, self.n_true, self.n_local, _ptr(rp), _ptr(col), _ptr(val), C.byref(self.handle)))
 
     ADD, ABS, FIX_ONE, FIX_ZERO = 1, 2, 4, 8
@@ -457,6 +459,26 @@ class Conforming:
                                             C.c_void_p(ess_mask.data_ptr()) if ess_mask is not None else None,
                                             C.c_void_p(x_ess.data_ptr()) if x_ess is not None else None))
         return y
+
+    def prolongate2(self, x0, x1, lx0, lx1, ess_mask=None):
+        """(lx0, lx1) = (P x0, P x1), both parts of a complex field in one launch; each bit-identical to prolongate."""
+        assert all(x.numel() == self.n_true for x in (x0, x1)) and all(lx.numel() == self.n_local for lx in (lx0, lx1))
+        assert ess_mask is None or ess_mask.numel() == self.n_true
+        _lib.check(_L().pa_conform_prolongate2(self.ctx.handle, self.handle, C.c_void_p(x0.data_ptr()), C.c_void_p(x1.data_ptr()),
+                                               C.c_void_p(lx0.data_ptr()), C.c_void_p(lx1.data_ptr()),
+                                               C.c_void_p(ess_mask.data_ptr()) if ess_mask is not None else None))
+        return lx0, lx1
+
+    def restrict2(self, ly0, ly1, y0, y1, flags=0, a=1.0, ess_mask=None, x_ess0=None, x_ess1=None):
+        """(y0, y1) = (P^T ly0, P^T ly1) with the flags of restrict, in one launch; each bit-identical to restrict."""
+        assert all(ly.numel() == self.n_local for ly in (ly0, ly1)) and all(y.numel() == self.n_true for y in (y0, y1))
+        assert ess_mask is None or ess_mask.numel() == self.n_true
+        assert all(x is None or x.numel() == self.n_true for x in (x_ess0, x_ess1))
+        opt = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+        _lib.check(_L().pa_conform_restrict2(self.ctx.handle, self.handle, C.c_void_p(ly0.data_ptr()), C.c_void_p(ly1.data_ptr()),
+                                             C.c_void_p(y0.data_ptr()), C.c_void_p(y1.data_ptr()), int(flags), float(a),
+                                             opt(ess_mask), opt(x_ess0), opt(x_ess1)))
+        return y0, y1
 
     def __del__(self):
         try:
@@ -954,8 +976,10 @@ class Curl(Interp):
     """Discrete curl C : ND(p) -> RT(p) on tensor hexahedra (the flux B = curl A, fem/fespace.cpp:199-206), sum-factorised:
     pa_curl_create.  mult = C, mult_transpose = C^T."""
 
-    def __init__(self, ctx, nd_space, rt_space, nd_halo=None, n_true_nd=None, n_true_rt=None):
-        self.ctx = ctx
+    def __init__(self, ctx, nd_space, rt_space, nd_halo=None, n_true_nd=None, n_true_rt=None, conforming=None):
+        """conforming: the Conforming prolongation of the Nedelec space (hanging nodes: R_rt C P_nd on true-dof vectors)."""
+        _one_of(nd_halo, conforming)
+        self.ctx, self.conforming = ctx, conforming
         p = rt_space.p
         _, Dg = lagrange_eval(gauss_lobatto(p + 1), gauss_legendre(p)[0])  # [p][p+1]
         Dg = np.ascontiguousarray(Dg)
@@ -964,6 +988,13 @@ class Curl(Interp):
         bn, k3 = _basis_desc(nd_space, p + 1)
         br, k4 = _basis_desc(rt_space, p + 1)
         self.handle = C.c_void_p()
+        if conforming is not None:
+            _lib.check(_L().pa_curl_create_conforming(ctx.handle, C.byref(rn), C.byref(bn), C.byref(rr), C.byref(br), _ptr(Dg),
+                                                      conforming.handle,
+                                                      _default_true(nd_space) if n_true_nd is None else n_true_nd,
+                                                      _default_true(rt_space) if n_true_rt is None else n_true_rt,
+                                                      C.byref(self.handle)))
+            return
         _lib.check(_L().pa_curl_create(ctx.handle, C.byref(rn), C.byref(bn), C.byref(rr), C.byref(br), _ptr(Dg),
                                        nd_halo.handle if nd_halo else None,
                                        nd_space.ndofs if n_true_nd is None else n_true_nd,
