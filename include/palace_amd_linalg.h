@@ -120,17 +120,40 @@ int pa_par_op_add_mult(pa_par_op *A, const double *x, double *y, double a);
 int pa_par_op_eliminate_rhs(pa_par_op *A, const double *x, double *b);
 int pa_par_op_assemble_diagonal(pa_par_op *A, double *diag);
 
-/* --- conforming prolongation with hanging-entity constraints (one rank) ------------------------
+/* --- conforming prolongation with hanging-entity constraints -----------------------------------
  * After a nonconforming refinement of tensor elements (utils/geodata.cpp:174-186) the reference's conforming prolongation is a
  * sparse operator, and every ParOperator is P^T A P with it (linalg/rap.cpp:65, :212-216).  Local vector layout as for a
  * halo: true dofs [0, n_true), then the constrained dofs; P = [I; C].
  *   row_ptr [n_local - n_true + 1], col, val   C in CSR (host arrays); every column must be a true dof (one-irregular meshes
  *                                              have no chains of constraints)
  * The transposed product gathers through an inverted index built here (per touched true dof its (slave, value) pairs in
- * ascending slave order): no atomics, bitwise reproducible.  A halo and a conforming prolongation together are not supported. */
+ * ascending slave order): no atomics, bitwise reproducible.  The operators never take a halo and a conforming prolongation
+ * side by side: across ranks the pa_conform itself carries the halo (pa_conform_create_dist). */
 typedef struct pa_conform pa_conform;
 int pa_conform_create(pa_context *ctx, int n_true, int n_local, const int *row_ptr, const int32_t *col, const double *val,
                       pa_conform **c);
+/* Several ranks: the object owns the composition P = [I; C] P_halo (the reference's one parallel matrix, rap.cpp:195-234).
+ * Rank-local vector:  [0, n_true) owned true dofs (the T-vector; dots and sums count these)
+ *                     [n_true, n_shared) ghost true dofs, grouped by owner (the halo's L-vector is the prefix [0, n_shared))
+ *                     [n_shared, n_local) constrained dofs, C [n_local - n_shared, n_shared]: columns may be owned or ghost
+ * Constrained dofs are never communicated: every rank that holds one evaluates it from its own copies of the masters.  P is a
+ * masked copy, the halo's P on the prefix and the rows of C in place; P^T folds the constrained rows into the prefix (a scratch
+ * vector of the object), lets the halo sum ghosts into owners and writes the owned part with the flags below.  `halo` covers
+ * the prefix of length n_shared and must outlive the object; NULL is allowed when n_shared == n_true.  The result is a
+ * pa_conform like any other with n_true true and n_local local dofs: every _conforming creator below takes it unchanged, the
+ * products can be recorded wherever the halo's exchange can, and with an empty halo they are bit-identical to
+ * pa_conform_create's.  pa_csr_rap_conforming and pa_par_op_parallel_assemble refuse it (an assembled level across ranks is
+ * not built). */
+int pa_conform_create_dist(pa_context *ctx, int n_true, int n_shared, int n_local, const int *row_ptr, const int32_t *col,
+                           const double *val, pa_halo *halo, pa_conform **c);
+/* length of the communicated prefix (= n_true for pa_conform_create) */
+int pa_conform_num_shared(const pa_conform *c);
+/* Measurement of a pa_conform_create_dist object (collective; waits for the device): microseconds per call of the pieces of P
+ * (us[0] masked copy, us[1] halo exchange, us[2] rows of C) and of P^T (us[3] fold, us[4] halo exchange, us[5] epilogue with
+ * FIX_ONE where ess_mask is given), each repeated `reps` times on its own after a warm-up.  The exchange pieces include the wait
+ * for the neighbours.  x, y [n_true]; lx, ly [n_local]; device pointers. */
+int pa_conform_time_pieces(pa_context *ctx, pa_conform *c, const double *x, double *lx, const double *ly, double *y,
+                           const uint8_t *ess_mask, int reps, double *us);
 void pa_conform_destroy(pa_conform *c);
 /* lx[0, n_true) = x (0 where ess_mask, one byte per true dof, is set; ess_mask may be NULL), lx[n_true + r] = sum_j C[r, j] x[j]
  * with x masked the same way.  One launch; device pointers. */

@@ -177,7 +177,8 @@ class ComplexParOperator : public ComplexOperator {
   const Context *ctx_;
   const Operator *Ar_, *Ai_;
   const Halo *halo_;
-  const Conforming *conf_ = nullptr;  // hanging-node constraints (one rank): every product goes through the two real ParOperators
+  // hanging-node constraints (across ranks the object carries the halo): every product goes through the two real ParOperators
+  const Conforming *conf_ = nullptr;
   int n_true_, n_local_;
   std::unique_ptr<ComplexWrapperOperator> A_;  // local (L-vector) operator
   std::unique_ptr<ParOperator> RAPr_, RAPi_;

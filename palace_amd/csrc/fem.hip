@@ -530,6 +530,19 @@ void FiniteElementSpace::SetConformingProlongation(int n_true,const int *row_ptr
   true_vsize_ = n_true;
 }
 
+void FiniteElementSpace::SetConformingProlongation(int n_true, int n_shared, const int *row_ptr, const int32_t *col,
+                                                   const double *val) {
+  PA_REQUIRE(!conf_, "this space has a conforming prolongation already");
+  PA_REQUIRE(n_true == true_vsize_, "distributed conforming prolongation: n_true is not the space's true-dof count");
+  PA_REQUIRE(n_shared >= n_true && n_shared <= vsize_, "distributed conforming prolongation: n_true <= n_shared <= local dofs");
+  PA_REQUIRE(halo_ || n_shared == n_true, "distributed conforming prolongation: ghost true dofs need the space's halo plan");
+  StreamGraph::Invalidate();
+  G_.clear();
+  conf_ = std::make_unique<Conforming>(*ctx_, n_true, n_shared, vsize_, row_ptr, col, val, halo_);
+  // the Conforming owns the composition from here on: operators and transfers see a constrained space without a halo of its own
+  halo_ = nullptr;
+}
+
 const Operator &FiniteElementSpaceHierarchy::BuildProlongationAtLevel(std::size_t l) const {
   // p-prolongation on one mesh (fespace.cpp:188-203 + bilinearform.cpp:203-282): Kronecker products of the 1-D nodal
   // interpolation matrices between the closed / open point sets of the two orders

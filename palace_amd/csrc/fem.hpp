@@ -186,12 +186,19 @@ public:
     return offsets_[(size_t)e * elem_size_ + j];
   }
   const Halo *GetHalo() const { return halo_; }
-  // Hanging-node constraints of a space on a nonconforming mesh (one rank; what mfem::FiniteElementSpace::
+  // Hanging-node constraints of a space on a nonconforming mesh (one rank, see below for several; what mfem::FiniteElementSpace::
   // GetConformingProlongation() is after a nonconformal refinement): the local vector holds the n_true true dofs first, then
   // the constrained ones, and P = [I; C] with C [GetVSize() - n_true][n_true] in CSR (host arrays; every column a true dof).
   // Every ParOperator and transfer built from this space (BilinearForm::Assemble -> FespaceParOperator, the hierarchy's
-  // prolongations, the discrete interpolators) then applies P and P^T.  Not together with a halo.
+  // prolongations, the discrete interpolators) then applies P and P^T.  Not on a space with a halo (that is the form below).
   void SetConformingProlongation(int n_true, const int *row_ptr, const int32_t *col, const double *val);
+  // Across ranks: the space was built with its true-dof count and the halo plan over the prefix [0, n_shared) of the local
+  // vector (owned true dofs, then ghost true dofs grouped by owner), the constrained dofs follow, and C is
+  // [GetVSize() - n_shared][n_shared] with owned or ghost columns.  The space then builds the Conforming that carries the halo
+  // (linalg.hpp: P = [I; C] P_halo) and hands the plan over to it: GetHalo() is null afterwards, GetConforming() is the whole of
+  // P, and every FespaceParOperator, prolongation and discrete gradient built from the space follows.  The halo may be null
+  // when n_shared == n_true.  BOOMER_AMG / AMS on such a level are refused (KspSolver: JACOBI_PCG at level 0).
+  void SetConformingProlongation(int n_true, int n_shared, const int *row_ptr, const int32_t *col, const double *val);
   const Conforming *GetConforming() const { return conf_.get(); }
   pa_restriction_desc GetCeedElemRestriction() const;
   pa_basis_desc GetCeedBasis() const;

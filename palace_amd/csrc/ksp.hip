@@ -46,6 +46,9 @@ amg::HostCsr AssembledLevelMatrix(const Operator &op, std::vector<char> &ess_fla
   PA_REQUIRE(par, "the algebraic coarse solvers need a ParOperator (the level operator of the multigrid hierarchy)");
   PA_REQUIRE(!par->GetHalo(), "the native AMG / AMS coarse solvers run on one rank (multi-rank: JACOBI_PCG or "
                               "CHEBYSHEV_JACOBI)");
+  PA_REQUIRE(!(par->GetConforming() && par->GetConforming()->IsDistributed()),
+             "BOOMER_AMG / AMS on a level with hanging-node constraints across ranks (its conforming prolongation carries a halo) "
+             "are not built: the assembled P^T A P exists on one rank only.  Use JACOBI_PCG, CHEBYSHEV_JACOBI or JACOBI at level 0.");
   const auto &ess = par->GetEssentialTrueDofsHost();
   if (par->GetConforming()) {
     // hanging nodes: the assembled P^T A P through the device triple product -- for a level that WAS assembled (a CsrOperator,

@@ -1369,6 +1369,9 @@ void ParOperator::AssembleDiagonal(Vector &diag) const {
 std::unique_ptr<pa_csr> ParOperator::ParallelAssemble(bool skip_zeros) const {
   StreamGraph::RequireNotRecording("ParOperator::ParallelAssemble");
   PA_REQUIRE(!halo_, "ParallelAssemble: this operator has a halo (several ranks); the assembled P^T A P is built on one rank only");
+  PA_REQUIRE(!(conf_ && conf_->IsDistributed()),
+             "ParallelAssemble: this operator's conforming prolongation carries a halo (several ranks); the assembled P^T A P is built on "
+             "one rank only");
   const Context &c = *ctx_;
   std::unique_ptr<pa_csr> local;  // the assembled local operator where this call makes it
   const pa_csr *B = nullptr;

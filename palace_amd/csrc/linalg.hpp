@@ -380,12 +380,23 @@ public:
   void MultResidualValues(const double *d_vals, const Vector &y, const Vector &b, Vector *res, const Vector *dinv, double c0, Vector *d0) const;
 };
 
-// Conforming prolongation of a space with hanging-entity constraints on one rank (nonconforming refinement of tensor elements,
-// utils/geodata.cpp:174-186: the reference's P is then a sparse matrix, not only a halo; linalg/rap.cpp:65, :212-216).  Local
-// vector layout as for a halo: true dofs [0, n_true), then the constrained dofs; P = [I; C] with C [n_local - n_true, n_true] in
-// CSR.  Both products are one launch each (pa_conform.hip), allocate nothing and never synchronise, so they can be recorded
+// Conforming prolongation of a space with hanging-entity constraints (nonconforming refinement of tensor elements,
+// utils/geodata.cpp:174-186: the reference's P is then a sparse matrix, not only a halo; linalg/rap.cpp:65, :212-216).  On one
+// rank the local vector holds the true dofs [0, n_true), then the constrained dofs; P = [I; C] with C [n_local - n_true, n_true]
+// in CSR.  Both products are one launch each (pa_conform.hip), allocate nothing and never synchronise, so they can be recorded
 // into the solvers' graphs; the transposed product gathers through an inverted index in a fixed order (no atomics: bitwise
 // reproducible).
+//
+// Across ranks the object owns the whole composition P = [I; C] P_halo (the reference's one parallel matrix, rap.cpp:195-234):
+//   [0, n_true) owned true dofs | [n_true, n_shared) ghost true dofs, grouped by owner | [n_shared, n_local) constrained dofs
+// with C [n_local - n_shared, n_shared] (columns owned or ghost) and the halo plan over the prefix of length n_shared.
+// Constrained dofs are never communicated: every rank that holds one evaluates it from its own copies of the masters.
+//   Prolongate: masked copy x -> lx[0, n_true), the halo's P on the prefix, the rows of C in place (prefix -> tail)
+//   Restrict:   t = prefix of ly + C^T tail (|C|^T with ABS) into the object's scratch, the halo's P^T on t, the epilogue
+//               (ADD, FIX_ONE / FIX_ZERO) on the owned part
+// The kernels keep the conventions above (lane groups, fixed order, no atomics); the products can be recorded wherever the
+// halo's exchange can.  The four methods keep their meaning, so ParOperator, ComplexParOperator and the transfers take a
+// distributed object as they take a one-rank one; the assembled triple product refuses it.
 class Conforming {
   int n_true_, n_con_;
   int fwd_lanes_ = 1, tr_lanes_ = 1;  // lanes that share one row (powers of two, from the longest row)
@@ -395,6 +406,17 @@ class Conforming {
   pa::DevBuf<double> d_val_, d_t_val_;
   pa::DevBuf<uint8_t> d_touched_;  // one byte per true dof: its row of C^T is not empty (the copy part of Restrict leaves it alone)
   pa::DevBuf<int32_t> d_t_slot_;   // per true dof its row of the inverted index, -1: none (the triple product, pa_rap_conform.hip)
+  // across ranks (see above): the index arrays then span the n_shared columns of the prefix
+  bool dist_ = false;
+  int n_shared_ = 0;                // = n_true_ on one rank
+  const Halo *halo_ = nullptr;      // plan over the prefix [0, n_shared_); nullptr: no ghosts
+  mutable pa::DevBuf<double> d_t_;  // [2][n_shared_ rounded up to even] the folded prefix of Restrict (second half: Restrict2)
+  void BuildIndex(const Context &ctx, int n_cols, const int *row_ptr, const int32_t *col, const double *val);
+  // pieces: bit 0 the masked copy / the fold, bit 1 the halo's exchange, bit 2 the rows of C / the epilogue (TimePieces)
+  void ProlongateDist(const double *x0, const double *x1, double *lx0, double *lx1, const uint8_t *ess_mask, hipStream_t stream,
+                      int pieces = 7) const;
+  void RestrictDist(const double *ly0, const double *ly1, double *y0, double *y1, int flags, double a, const uint8_t *ess_mask,
+                    const double *x_ess0, const double *x_ess1, hipStream_t stream, int pieces = 7) const;
 
 public:
   enum : int { ADD = 1, ABS = 2, FIX_ONE = 4, FIX_ZERO = 8 };
@@ -410,11 +432,16 @@ public:
   };
   DeviceView View() const { return {n_true_, n_con_, d_row_ptr_, d_col_, d_val_, d_t_ptr_, d_t_slot_, d_t_slave_, d_t_val_}; }
   Conforming(const Context &ctx, int n_true, int n_local, const int *row_ptr, const int32_t *col, const double *val);
+  // the distributed form; halo may be nullptr when n_shared == n_true (it is validated against [n_true, n_shared))
+  Conforming(const Context &ctx, int n_true, int n_shared, int n_local, const int *row_ptr, const int32_t *col, const double *val,
+             const Halo *halo);
   ~Conforming();
   Conforming(const Conforming &) = delete;
   Conforming &operator=(const Conforming &) = delete;
   int NumTrue() const { return n_true_; }
-  int NumLocal() const { return n_true_ + n_con_; }
+  int NumShared() const { return n_shared_; }
+  int NumLocal() const { return n_shared_ + n_con_; }
+  bool IsDistributed() const { return dist_; }
   int ForwardLanes() const { return fwd_lanes_; }
   int TransposeLanes() const { return tr_lanes_; }
   // lx = P tx, tx = x with the entries flagged in ess_mask (one byte per true dof, bit 1; may be nullptr) read as zero
@@ -423,6 +450,11 @@ public:
   // value is x_ess[i] (FIX_ONE) or 0 (FIX_ZERO) instead.  y may be x_ess; y must not overlap ly.
   void Restrict(const double *ly, double *y, int flags, double a, const uint8_t *ess_mask, const double *x_ess,
                 hipStream_t stream) const;
+  // Measurement (distributed form; collective, waits for the device): microseconds per call of the three pieces of P (masked
+  // copy, exchange, rows) and of P^T (fold, exchange, epilogue with the essential rows), each repeated `reps` times on its own
+  // after a warm-up; us [6].  The exchange pieces include the wait for the neighbours.
+  void TimePieces(const double *x, double *lx, const double *ly, double *y, const uint8_t *ess_mask, int reps, double *us,
+                  hipStream_t stream) const;
   // The same for the two parts of a complex field in one launch each: the index arrays, the values and the mask are read once;
   // either part is bit-identical to the one-vector call on it.  The outputs must not overlap each other or the inputs.
   void Prolongate2(const double *x0, const double *x1, double *lx0, double *lx1, const uint8_t *ess_mask, hipStream_t stream) const;
@@ -443,9 +475,9 @@ std::unique_ptr<pa_csr> RapConforming(const Context &ctx, const pa_csr &B, const
 
 // ParOperator (rap.cpp:154-234): y = P^T A P x with essential-dof handling.  True dofs of this
 // rank are the first n_true entries of the local (L-) vector; shared dofs owned elsewhere follow
-// (see comm.hpp); with one rank P is the identity, or the Conforming prolongation of a space with
-// hanging nodes (then Mult is three launches -- masked P, the local apply, P^T with the essential rows --
-// and the fused and split forms are not available: smoothers and PCG take their plain paths).
+// (see comm.hpp); with one rank P is the identity.  With the Conforming prolongation of a space with
+// hanging nodes (one rank, or across ranks with the halo inside the Conforming) Mult is masked P, the local apply, P^T with the
+// essential rows, and the fused and split forms are not available: smoothers and PCG take their plain paths.
 class ParOperator : public Operator {
 public:
   enum class DiagonalPolicy { DIAG_ZERO = 0, DIAG_ONE = 1 };
@@ -461,7 +493,7 @@ private:
   const CsrOperator *A_csr_ = nullptr;       // single rank, assembled local operator: BCs eliminated in the matrix values
   pa::DevBuf<double> d_csr_bc_;              // ... this wrapper's copy of them (CsrOperator::EliminatedValuesBuf)
   const Halo *halo_;
-  const Conforming *conf_ = nullptr;  // hanging-node constraints (one rank; never together with a halo)
+  const Conforming *conf_ = nullptr;  // hanging-node constraints (never together with a halo: across ranks the Conforming owns its own)
   int n_true_, n_local_;
   pa::DevBuf<int32_t> d_ess_;
   int n_ess_ = 0;

@@ -13,10 +13,15 @@
 //               into y, takes |C| (the diagonal: the reference uses AbsMultTranspose for an AMR mesh, rap.cpp:163-175, because
 //               the signed product does not give a convergent diagonal) and sets the essential rows of ParOperator::Mult.
 //               The copy part leaves the touched dofs to the gather part, so every entry of y is written by one thread.
+//
+// Across ranks the object owns P = [I; C] P_halo (the reference's one parallel matrix, rap.cpp:195-234): the products come apart
+// around the halo's exchange -- masked copy / exchange / rows in place, fold into a scratch prefix / exchange / epilogue -- with
+// the same lane groups and the same order of operations (the second half of this file).
 #include <algorithm>
 #include <cmath>
 #include <vector>
 
+#include "comm.hpp"
 #include "linalg.hpp"
 
 namespace palace {
@@ -265,6 +270,148 @@ __global__ __launch_bounds__(kBlock) void k_conform_restrict2(const int n_true, 
   }
 }
 
+// ---- across ranks: P = [I; C] P_halo in pieces around the halo's exchange ---------------------------------------------------
+// Local vector: owned true dofs [0, n_true), ghost true dofs [n_true, n_shared), constrained dofs [n_shared, n_local); C has
+// n_shared columns.  The pieces keep the arithmetic of the one-launch kernels above (the same lane groups, the same order of
+// products and sums), so with an empty halo they reproduce them bit for bit.  TWO: the second vector of a complex field rides in
+// the same launch and goes through the same operations as a one-vector launch on it.
+
+// masked copy x -> lx[0, n_true): the head blocks of k_conform_prolongate as a launch of their own (the halo runs behind it)
+template <bool VEC, bool TWO>
+__global__ __launch_bounds__(kBlock) void k_conform_copy_masked(const int n_true, const double *__restrict__ x0,
+                                                                 const double *__restrict__ x1, const uint8_t *__restrict__ mask,
+                                                                 double *__restrict__ lx0, double *__restrict__ lx1) {
+  const int i = 2 * ((int)blockIdx.x * kBlock + (int)threadIdx.x);
+  if (i + 1 < n_true) {
+    double2 v0 = load2<VEC>(x0, i), v1 = v0;
+    if (TWO) v1 = load2<VEC>(x1, i);
+    if (mask) {
+      if (mask[i] & 1) v0.x = 0.0, v1.x = 0.0;
+      if (mask[i + 1] & 1) v0.y = 0.0, v1.y = 0.0;
+    }
+    store2<VEC>(lx0, i, v0);
+    if (TWO) store2<VEC>(lx1, i, v1);
+  } else if (i < n_true) {
+    const bool m = mask && (mask[i] & 1);
+    lx0[i] = m ? 0.0 : x0[i];
+    if (TWO) lx1[i] = m ? 0.0 : x1[i];
+  }
+}
+
+// in-place rows: lx[n_shared + r] = sum_j C[r, j] lx[j]; reads the prefix only, writes the tail only (no copy, no mask: the
+// prefix was masked before the exchange, so the ghost copies of essential dofs are zero too)
+template <int L, bool TWO>
+__global__ __launch_bounds__(kBlock) void k_conform_rows(const int n_shared, const int n_con, const int *__restrict__ row_ptr,
+                                                          const int32_t *__restrict__ col, const double *__restrict__ val,
+                                                          double *lx0, double *lx1) {
+  const int lane = (int)threadIdx.x % L;
+  const int r = (int)blockIdx.x * (kBlock / L) + (int)threadIdx.x / L;
+  double s0 = 0.0, s1 = 0.0;
+  if (r < n_con) {  // (whole groups share r: the butterfly below runs with every lane of the group)
+    const int e = row_ptr[r + 1];
+    for (int k = row_ptr[r] + lane; k < e; k += L) {
+      const int j = col[k];  // < n_shared (checked at set-up)
+      const double v = val[k];
+      s0 += v * lx0[j];
+      if (TWO) s1 += v * lx1[j];
+    }
+  }
+  s0 = group_sum<L>(s0);
+  if (TWO) s1 = group_sum<L>(s1);
+  if (r < n_con && lane == 0) {
+    lx0[n_shared + r] = s0;
+    if (TWO) lx1[n_shared + r] = s1;
+  }
+}
+
+// fold into the prefix: t[j] = ly[j] + sum_r C[r, j] ly[n_shared + r] for every j < n_shared, ghost columns included (their
+// sums travel to the owners with the halo's P^T); head blocks copy the columns nothing hangs on, one lane group per touched one
+template <int L, bool VEC, bool TWO>
+__global__ __launch_bounds__(kBlock) void k_conform_fold(const int n_shared, const int n_touched, const int head_blocks,
+                                                          const int *__restrict__ t_ptr, const int32_t *__restrict__ t_dof,
+                                                          const int32_t *__restrict__ t_slave, const double *__restrict__ t_val,
+                                                          const uint8_t *__restrict__ touched, const double *__restrict__ ly0,
+                                                          const double *__restrict__ ly1, const int abs_values,
+                                                          double *__restrict__ t0, double *__restrict__ t1) {
+  if ((int)blockIdx.x < head_blocks) {
+    const int i = 2 * ((int)blockIdx.x * kBlock + (int)threadIdx.x);
+    if (i + 1 < n_shared) {
+      double2 v0 = load2<VEC>(ly0, i), v1 = v0;
+      if (TWO) v1 = load2<VEC>(ly1, i);
+      const bool c0 = touched[i] == 0, c1 = touched[i + 1] == 0;
+      if (VEC && c0 && c1) {
+        store2<true>(t0, i, v0);
+        if (TWO) store2<true>(t1, i, v1);
+      } else {
+        if (c0) t0[i] = v0.x;
+        if (c1) t0[i + 1] = v0.y;
+        if (TWO && c0) t1[i] = v1.x;
+        if (TWO && c1) t1[i + 1] = v1.y;
+      }
+    } else if (i < n_shared) {
+      if (!touched[i]) {
+        t0[i] = ly0[i];
+        if (TWO) t1[i] = ly1[i];
+      }
+    }
+    return;
+  }
+  const int lane = (int)threadIdx.x % L;
+  const int t = ((int)blockIdx.x - head_blocks) * (kBlock / L) + (int)threadIdx.x / L;
+  double s0 = 0.0, s1 = 0.0;
+  if (t < n_touched) {
+    const int e = t_ptr[t + 1];
+    const double *tail0 = ly0 + n_shared, *tail1 = TWO ? ly1 + n_shared : nullptr;
+    if (abs_values) {
+      for (int k = t_ptr[t] + lane; k < e; k += L) {
+        const double v = fabs(t_val[k]);
+        const int sl = t_slave[k];
+        s0 += v * tail0[sl];
+        if (TWO) s1 += v * tail1[sl];
+      }
+    } else {
+      for (int k = t_ptr[t] + lane; k < e; k += L) {
+        const double v = t_val[k];
+        const int sl = t_slave[k];
+        s0 += v * tail0[sl];
+        if (TWO) s1 += v * tail1[sl];
+      }
+    }
+  }
+  s0 = group_sum<L>(s0);
+  if (TWO) s1 = group_sum<L>(s1);
+  if (t < n_touched && lane == 0) {
+    const int i = t_dof[t];
+    t0[i] = ly0[i] + s0;
+    if (TWO) t1[i] = ly1[i] + s1;
+  }
+}
+
+// epilogue on the owned part: y[i] = t[i] with ADD and the essential rows (restrict_value: the tail of k_conform_restrict).
+// y may be x_ess: every thread reads x_ess[i] and y[i] before it writes y[i], and no other thread touches entry i.
+template <bool VEC, bool TWO>
+__global__ __launch_bounds__(kBlock) void k_conform_epilogue(const int n_true, const double *__restrict__ t0,
+                                                              const double *__restrict__ t1, const int flags, const double a,
+                                                              const uint8_t *__restrict__ mask, const double *x_ess0,
+                                                              const double *x_ess1, double *y0, double *y1) {
+  const int i = 2 * ((int)blockIdx.x * kBlock + (int)threadIdx.x);
+  if (i + 1 < n_true) {
+    double2 v0 = load2<VEC>(t0, i), v1 = v0;
+    if (TWO) v1 = load2<VEC>(t1, i);
+    v0.x = restrict_value(v0.x, i, flags, a, mask, x_ess0, y0);
+    v0.y = restrict_value(v0.y, i + 1, flags, a, mask, x_ess0, y0);
+    if (TWO) {
+      v1.x = restrict_value(v1.x, i, flags, a, mask, x_ess1, y1);
+      v1.y = restrict_value(v1.y, i + 1, flags, a, mask, x_ess1, y1);
+    }
+    store2<VEC>(y0, i, v0);
+    if (TWO) store2<VEC>(y1, i, v1);
+  } else if (i < n_true) {
+    y0[i] = restrict_value(t0[i], i, flags, a, mask, x_ess0, y0);
+    if (TWO) y1[i] = restrict_value(t1[i], i, flags, a, mask, x_ess1, y1);
+  }
+}
+
 int lanes_for(int longest) {
   int l = 1;
   while (l < longest && l < 32) l *= 2;
@@ -279,20 +426,35 @@ bool overlap(const double *a, size_t na, const double *b, size_t nb) { return a 
 }  // namespace
 
 Conforming::Conforming(const Context &ctx, int n_true, int n_local, const int *row_ptr, const int32_t *col, const double *val)
-    : n_true_(n_true), n_con_(n_local - n_true) {
+    : n_true_(n_true), n_con_(n_local - n_true), n_shared_(n_true) {
   PA_REQUIRE(n_true >= 0 && n_local >= n_true, "conforming prolongation: bad sizes");
-  PA_REQUIRE(n_local < (1 << 30), "conforming prolongation: too many dofs for the 32-bit index arithmetic of the kernels");
+  BuildIndex(ctx, n_true, row_ptr, col, val);
+}
+
+Conforming::Conforming(const Context &ctx, int n_true, int n_shared, int n_local, const int *row_ptr, const int32_t *col,
+                       const double *val, const Halo *halo)
+    : n_true_(n_true), n_con_(n_local - n_shared), dist_(true), n_shared_(n_shared), halo_(halo) {
+  PA_REQUIRE(n_true >= 0 && n_shared >= n_true && n_local >= n_shared, "distributed conforming prolongation: bad sizes");
+  PA_REQUIRE(halo || n_shared == n_true, "distributed conforming prolongation: ghost true dofs need a halo plan");
+  if (halo) halo->Validate(n_true, n_shared);  // the plan covers the prefix: constrained dofs are never communicated
+  BuildIndex(ctx, n_shared, row_ptr, col, val);
+  d_t_ = pa::dev_alloc<double>(2 * (((size_t)n_shared + 1) & ~(size_t)1));
+}
+
+// C by rows and C^T as an inverted index over its n_cols columns (the true dofs; across ranks the owned and the ghost ones)
+void Conforming::BuildIndex(const Context &ctx, int n_cols, const int *row_ptr, const int32_t *col, const double *val) {
+  PA_REQUIRE(n_cols + n_con_ < (1 << 30), "conforming prolongation: too many dofs for the 32-bit index arithmetic of the kernels");
   PA_REQUIRE(n_con_ == 0 || (row_ptr && row_ptr[0] == 0), "conforming prolongation: the row pointer must start at 0");
   const int nnz = n_con_ ? row_ptr[n_con_] : 0;
   PA_REQUIRE(nnz == 0 || (col && val), "conforming prolongation: null arrays");
   int longest = 0;
-  std::vector<int> count((size_t)n_true + 1, 0);
+  std::vector<int> count((size_t)n_cols + 1, 0);
   for (int r = 0; r < n_con_; r++) {
     PA_REQUIRE(row_ptr[r + 1] >= row_ptr[r] && row_ptr[r + 1] <= nnz, "conforming prolongation: the row pointer must not decrease");
     longest = std::max(longest, row_ptr[r + 1] - row_ptr[r]);
     for (int k = row_ptr[r]; k < row_ptr[r + 1]; k++) {
       // one-irregular meshes: every column is a true dof (no chains of constraints)
-      PA_REQUIRE(col[k] >= 0 && col[k] < n_true, "conforming prolongation: a constraint refers to a dof that is not a true dof");
+      PA_REQUIRE(col[k] >= 0 && col[k] < n_cols, "conforming prolongation: a constraint refers to a dof that is not a true dof");
       count[col[k] + 1]++;
     }
   }
@@ -300,10 +462,10 @@ Conforming::Conforming(const Context &ctx, int n_true, int n_local, const int *r
   // C^T as an inverted index over the touched true dofs; rows of C are visited in ascending order, so every list is in
   // ascending slave order
   std::vector<int32_t> t_dof;
-  std::vector<int> t_ptr{0}, slot((size_t)n_true, -1);
-  std::vector<uint8_t> touched((size_t)n_true, 0);
+  std::vector<int> t_ptr{0}, slot((size_t)n_cols, -1);
+  std::vector<uint8_t> touched((size_t)n_cols, 0);
   int longest_t = 0;
-  for (int i = 0; i < n_true; i++) {
+  for (int i = 0; i < n_cols; i++) {
     if (!count[i + 1]) continue;
     slot[i] = (int)t_dof.size();
     t_dof.push_back(i);
@@ -336,6 +498,7 @@ Conforming::Conforming(const Context &ctx, int n_true, int n_local, const int *r
 Conforming::~Conforming() = default;
 
 void Conforming::Prolongate(const double *x, double *lx, const uint8_t *ess_mask, hipStream_t stream) const {
+  if (dist_) return ProlongateDist(x, nullptr, lx, nullptr, ess_mask, stream);
   if (n_true_ + n_con_ == 0) return;
   const int head = ((n_true_ + 1) / 2 + kBlock - 1) / kBlock;
   const bool vec = aligned16(x, lx);
@@ -364,6 +527,10 @@ void Conforming::Prolongate(const double *x, double *lx, const uint8_t *ess_mask
 
 void Conforming::Restrict(const double *ly, double *y, int flags, double a, const uint8_t *ess_mask, const double *x_ess,
                           hipStream_t stream) const {
+  if (dist_) {
+    PA_REQUIRE(!((flags & FIX_ONE) && ess_mask) || x_ess, "conforming restriction: FIX_ONE needs the vector the essential rows copy");
+    return RestrictDist(ly, nullptr, y, nullptr, flags, a, ess_mask, x_ess, nullptr, stream);
+  }
   if (n_true_ == 0) return;
   PA_REQUIRE(!((flags & FIX_ONE) && ess_mask) || x_ess, "conforming restriction: FIX_ONE needs the vector the essential rows copy");
   PA_REQUIRE(!((flags & FIX_ONE) && (flags & FIX_ZERO)), "conforming restriction: one policy for the essential rows");
@@ -394,11 +561,12 @@ void Conforming::Restrict(const double *ly, double *y, int flags, double a, cons
 
 void Conforming::Prolongate2(const double *x0, const double *x1, double *lx0, double *lx1, const uint8_t *ess_mask,
                              hipStream_t stream) const {
-  if (n_true_ + n_con_ == 0) return;
-  const size_t nt = (size_t)n_true_, nl = nt + n_con_;
+  if (n_shared_ + n_con_ == 0 && !dist_) return;  // (a distributed object stays collective: ProlongateDist decides)
+  const size_t nt = (size_t)n_true_, nl = (size_t)n_shared_ + n_con_;
   PA_REQUIRE(!overlap(lx0, nl, lx1, nl) && !overlap(lx0, nl, x0, nt) && !overlap(lx0, nl, x1, nt) && !overlap(lx1, nl, x0, nt) &&
                  !overlap(lx1, nl, x1, nt),
              "conforming prolongation of two vectors: the outputs must not overlap each other or the inputs");
+  if (dist_) return ProlongateDist(x0, x1, lx0, lx1, ess_mask, stream);
   const int head = ((n_true_ + 1) / 2 + kBlock - 1) / kBlock;
   const bool vec = aligned16(x0, lx0) && aligned16(x1, lx1);
   auto launch = [&](auto kernel, int lanes) {
@@ -427,14 +595,15 @@ void Conforming::Prolongate2(const double *x0, const double *x1, double *lx0, do
 
 void Conforming::Restrict2(const double *ly0, const double *ly1, double *y0, double *y1, int flags, double a, const uint8_t *ess_mask,
                            const double *x_ess0, const double *x_ess1, hipStream_t stream) const {
-  if (n_true_ == 0) return;
+  if (n_true_ == 0 && !dist_) return;
   PA_REQUIRE(!((flags & FIX_ONE) && ess_mask) || (x_ess0 && x_ess1),
              "conforming restriction: FIX_ONE needs the vectors the essential rows copy");
   PA_REQUIRE(!((flags & FIX_ONE) && (flags & FIX_ZERO)), "conforming restriction: one policy for the essential rows");
-  const size_t nt = (size_t)n_true_, nl = nt + n_con_;
+  const size_t nt = (size_t)n_true_, nl = (size_t)n_shared_ + n_con_;
   PA_REQUIRE(!overlap(y0, nt, y1, nt) && !overlap(y0, nt, ly0, nl) && !overlap(y0, nt, ly1, nl) && !overlap(y1, nt, ly0, nl) &&
                  !overlap(y1, nt, ly1, nl),
              "conforming restriction of two vectors: the outputs must not overlap each other or the inputs");
+  if (dist_) return RestrictDist(ly0, ly1, y0, y1, flags, a, ess_mask, x_ess0, x_ess1, stream);
   const int head = ((n_true_ + 1) / 2 + kBlock - 1) / kBlock;
   const bool vec = aligned16(ly0, y0) && aligned16(ly1, y1);
   auto launch = [&](auto kernel, int lanes) {
@@ -458,6 +627,134 @@ void Conforming::Restrict2(const double *ly0, const double *ly1, double *y0, dou
   }
 #undef PA_CONFORM_CASE
   PA_HIP(hipGetLastError());
+}
+
+// P = [I; C] P_halo: masked copy, the halo's exchange on the prefix, the rows of C in place.  x1 == nullptr: one vector.
+void Conforming::ProlongateDist(const double *x0, const double *x1, double *lx0, double *lx1, const uint8_t *ess_mask,
+                                hipStream_t stream, int pieces) const {
+  if (n_shared_ + n_con_ == 0 && !halo_) return;
+  const bool two = x1 != nullptr;
+  if (n_true_ && (pieces & 1)) {
+    const int head = ((n_true_ + 1) / 2 + kBlock - 1) / kBlock;
+    const bool vec = aligned16(x0, lx0) && (!two || aligned16(x1, lx1));
+    auto launch = [&](auto kernel) {
+      hipLaunchKernelGGL(kernel, dim3(head), dim3(kBlock), 0, stream, n_true_, x0, x1, ess_mask, lx0, lx1);
+    };
+    if (two)
+      vec ? launch(k_conform_copy_masked<true, true>) : launch(k_conform_copy_masked<false, true>);
+    else
+      vec ? launch(k_conform_copy_masked<true, false>) : launch(k_conform_copy_masked<false, false>);
+  }
+  if (halo_ && (pieces & 2)) {  // (every rank of the plan comes here, with or without dofs of its own: the exchange is collective)
+    halo_->Prolongate(lx0, stream);
+    if (two) halo_->Prolongate(lx1, stream);
+  }
+  if (n_con_ && (pieces & 4)) {
+    auto launch = [&](auto kernel, int lanes) {
+      const int rows_per_block = kBlock / lanes;
+      hipLaunchKernelGGL(kernel, dim3((n_con_ + rows_per_block - 1) / rows_per_block), dim3(kBlock), 0, stream, n_shared_, n_con_,
+                         d_row_ptr_, d_col_, d_val_, lx0, lx1);
+    };
+#define PA_CONFORM_CASE(L)                                                                   \
+  case L:                                                                                    \
+    two ? launch(k_conform_rows<L, true>, L) : launch(k_conform_rows<L, false>, L);          \
+    break;
+    switch (fwd_lanes_) {
+      PA_CONFORM_CASE(1)
+      PA_CONFORM_CASE(2)
+      PA_CONFORM_CASE(4)
+      PA_CONFORM_CASE(8)
+      PA_CONFORM_CASE(16)
+      PA_CONFORM_CASE(32)
+      default: throw pa::Error("conforming prolongation: bad lane count");
+    }
+#undef PA_CONFORM_CASE
+  }
+  PA_HIP(hipGetLastError());
+}
+
+// P^T = P_halo^T [I C^T]: fold the tail into the prefix (scratch t, the caller's ly stays const), the halo sums the ghosts of t
+// into their owners, the epilogue writes the owned part.  ly1 == nullptr: one vector.
+void Conforming::RestrictDist(const double *ly0, const double *ly1, double *y0, double *y1, int flags, double a,
+                              const uint8_t *ess_mask, const double *x_ess0, const double *x_ess1, hipStream_t stream,
+                              int pieces) const {
+  PA_REQUIRE(!((flags & FIX_ONE) && (flags & FIX_ZERO)), "conforming restriction: one policy for the essential rows");
+  if (n_shared_ == 0 && !halo_) return;
+  const bool two = ly1 != nullptr;
+  double *t0 = d_t_, *t1 = two ? d_t_ + (((size_t)n_shared_ + 1) & ~(size_t)1) : nullptr;
+  if (n_shared_ && (pieces & 1)) {
+    const int head = ((n_shared_ + 1) / 2 + kBlock - 1) / kBlock;
+    const bool vec = aligned16(ly0, t0) && (!two || aligned16(ly1, t1));
+    const int abs_values = (flags & ABS) ? 1 : 0;
+    auto launch = [&](auto kernel, int lanes) {
+      const int rows_per_block = kBlock / lanes;
+      const int grid = head + (n_touched_ + rows_per_block - 1) / rows_per_block;
+      hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), 0, stream, n_shared_, n_touched_, head, d_t_ptr_, d_t_dof_, d_t_slave_,
+                         d_t_val_, d_touched_, ly0, ly1, abs_values, t0, t1);
+    };
+#define PA_CONFORM_CASE(L)                                                                                         \
+  case L:                                                                                                          \
+    if (two)                                                                                                       \
+      vec ? launch(k_conform_fold<L, true, true>, L) : launch(k_conform_fold<L, false, true>, L);                  \
+    else                                                                                                           \
+      vec ? launch(k_conform_fold<L, true, false>, L) : launch(k_conform_fold<L, false, false>, L);                \
+    break;
+    switch (tr_lanes_) {
+      PA_CONFORM_CASE(1)
+      PA_CONFORM_CASE(2)
+      PA_CONFORM_CASE(4)
+      PA_CONFORM_CASE(8)
+      PA_CONFORM_CASE(16)
+      PA_CONFORM_CASE(32)
+      default: throw pa::Error("conforming restriction: bad lane count");
+    }
+#undef PA_CONFORM_CASE
+  }
+  if (halo_ && (pieces & 2)) {
+    halo_->RestrictAdd(t0, stream);
+    if (two) halo_->RestrictAdd(t1, stream);
+  }
+  if (n_true_ && (pieces & 4)) {
+    const int head = ((n_true_ + 1) / 2 + kBlock - 1) / kBlock;
+    const bool vec = aligned16(t0, y0) && (!two || aligned16(t1, y1));
+    auto launch = [&](auto kernel) {
+      hipLaunchKernelGGL(kernel, dim3(head), dim3(kBlock), 0, stream, n_true_, t0, t1, flags, a, ess_mask, x_ess0, x_ess1, y0, y1);
+    };
+    if (two)
+      vec ? launch(k_conform_epilogue<true, true>) : launch(k_conform_epilogue<false, true>);
+    else
+      vec ? launch(k_conform_epilogue<true, false>) : launch(k_conform_epilogue<false, false>);
+  }
+  PA_HIP(hipGetLastError());
+}
+
+void Conforming::TimePieces(const double *x, double *lx, const double *ly, double *y, const uint8_t *ess_mask, int reps, double *us,
+                            hipStream_t stream) const {
+  StreamGraph::RequireNotRecording("timing the pieces of a conforming prolongation");
+  PA_REQUIRE(dist_ && reps > 0 && us, "the pieces are those of a conforming prolongation that carries a halo");
+  hipEvent_t e0, e1;
+  PA_HIP(hipEventCreate(&e0));
+  PA_HIP(hipEventCreate(&e1));
+  const int fix = ess_mask ? FIX_ONE : 0;
+  for (int k = 0; k < 6; k++) {
+    const int piece = 1 << (k % 3);
+    auto run = [&] {
+      if (k < 3)
+        ProlongateDist(x, nullptr, lx, nullptr, ess_mask, stream, piece);
+      else
+        RestrictDist(ly, nullptr, y, nullptr, fix, 1.0, ess_mask, x, nullptr, stream, piece);
+    };
+    for (int i = 0; i < 5; i++) run();
+    PA_HIP(hipEventRecord(e0, stream));
+    for (int i = 0; i < reps; i++) run();
+    PA_HIP(hipEventRecord(e1, stream));
+    PA_HIP(hipEventSynchronize(e1));
+    float ms = 0.0f;
+    PA_HIP(hipEventElapsedTime(&ms, e0, e1));
+    us[k] = 1e3 * (double)ms / reps;
+  }
+  PA_HIP(hipEventDestroy(e0));
+  PA_HIP(hipEventDestroy(e1));
 }
 
 }  // namespace palace

@@ -1172,11 +1172,14 @@ public:
     }
     lc_.SetSize(nl_c_), lf_.SetSize(nl_f_);
   }
+  // nothing to exchange and nothing to stage (a Conforming that carries a halo is collective even on a rank whose own local
+  // vector has neither ghosts nor constrained dofs: the other ranks wait for it in the exchange)
+  bool OneRank() const { return !halo_c_ && !(conf_c_ && conf_c_->IsDistributed()) && nt_c_ == nl_c_ && nt_f_ == nl_f_; }
   // y_f = R_f D^-1 E_f^T I E_c P_c x_c
   void Mult(const Vector &x, Vector &y) const override {
     const Context &c = *ctx_;
     PA_REQUIRE(x.Size() == nt_c_ && y.Size() == nt_f_, "size mismatch in prolongation");
-    if (!halo_c_ && nt_c_ == nl_c_ && nt_f_ == nl_f_) {  // one rank: no staging copies
+    if (OneRank()) {  // no staging copies
       launch<false>(x.Data(), y.Data());
       return;
     }
@@ -1194,7 +1197,7 @@ public:
   void MultTranspose(const Vector &x, Vector &y) const override {
     const Context &c = *ctx_;
     PA_REQUIRE(x.Size() == nt_f_ && y.Size() == nt_c_, "size mismatch in restriction");
-    if (!halo_c_ && nt_c_ == nl_c_ && nt_f_ == nl_f_) {
+    if (OneRank()) {
       launch<true>(x.Data(), nullptr);
       launch_k_gather(nl_c_, d_tptr_c_, d_tent_c_, d_ye_c_, y.Data(), c.stream);
       PA_HIP(hipGetLastError());

@@ -1170,6 +1170,23 @@ int pa_conform_create(pa_context *ctx, int n_true, int n_local, const int *row_p
     *c = hold.release();
   });
 }
+int pa_conform_create_dist(pa_context *ctx, int n_true, int n_shared, int n_local, const int *row_ptr, const int32_t *col,
+                           const double *val, pa_halo *halo, pa_conform **c) {
+  return guarded([&] {
+    PA_REQUIRE(ctx && c, "null argument");
+    auto hold = std::make_unique<pa_conform>();
+    hold->conf = std::make_unique<Conforming>(ctx->ctx, n_true, n_shared, n_local, row_ptr, col, val, halo ? halo->halo.get() : nullptr);
+    *c = hold.release();
+  });
+}
+int pa_conform_num_shared(const pa_conform *c) { return c ? c->conf->NumShared() : 0; }
+int pa_conform_time_pieces(pa_context *ctx, pa_conform *c, const double *x, double *lx, const double *ly, double *y,
+                           const uint8_t *ess_mask, int reps, double *us) {
+  return guarded([&] {
+    PA_REQUIRE(ctx && c && x && lx && ly && y && us, "null argument");
+    c->conf->TimePieces(x, lx, ly, y, ess_mask, reps, us, ctx->ctx.stream);
+  });
+}
 void pa_conform_destroy(pa_conform *c) { delete c; }
 int pa_conform_prolongate(pa_context *ctx, pa_conform *c, const double *x, double *lx, const uint8_t *ess_mask) {
   return guarded([&] {

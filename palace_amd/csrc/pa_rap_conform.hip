@@ -286,6 +286,8 @@ void launch_rows(const RapArgs &base, const int *lists, int n_out, const int n_l
 std::unique_ptr<pa_csr> RapConforming(const Context &ctx, const pa_csr &B, const Conforming *test, const Conforming *trial,
                                       RapLeft left, double *phase_ms) {
   StreamGraph::RequireNotRecording("the assembled triple product with conforming prolongations");
+  PA_REQUIRE(!(test && test->IsDistributed()) && !(trial && trial->IsDistributed()),
+             "triple product: a conforming prolongation that carries a halo (several ranks); the assembled P^T A P is built on one rank only");
   hipStream_t s = ctx.stream;
   const int b_rows = B.nrows, b_cols = B.ncols ? B.ncols : B.nrows;
   PA_REQUIRE(!test || test->NumLocal() == b_rows, "triple product: the test side's conforming prolongation does not match the rows of B");

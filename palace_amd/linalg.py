@@ -415,20 +415,34 @@ class Halo:
 
 
 class Conforming:
-    """Conforming prolongation P = [I; C] of a space with hanging-entity constraints on one rank (pa_conform_create): `C` a
-    scipy CSR matrix [n_local - n_true, n_true] whose columns are all true dofs (fem/nchex.py: NCSpace.C), or an NCSpace."""
+    """Conforming prolongation P = [I; C] of a space with hanging-entity constraints (pa_conform_create): `C` a scipy CSR
+    matrix [n_local - n_true, n_true] whose columns are all true dofs (fem/nchex.py: NCSpace.C), or an NCSpace.
 
-    def __init__(self, ctx: Context, C_or_space, n_true=None, n_local=None):
-        self.ctx = ctx
+    Across ranks (pa_conform_create_dist, chosen when a `halo` or an `n_shared` is given) the object owns the composition
+    P = [I; C] P_halo: the local vector is owned true dofs [0, n_true), ghost true dofs [n_true, n_shared), constrained dofs
+    [n_shared, n_local), `C` is [n_local - n_shared, n_shared] and `halo` the plan over the prefix (None: no ghosts, n_shared ==
+    n_true).  A fem/ncpart.py view supplies C, n_true and n_shared.  Every operator takes the object through `conforming=`."""
+
+    def __init__(self, ctx: Context, C_or_space, n_true=None, n_local=None, halo=None, n_shared=None):
+        self.ctx, self.halo = ctx, halo
         Cm = getattr(C_or_space, "C", C_or_space).tocsr()
-        self.n_true = Cm.shape[1] if n_true is None else n_true
-        self.n_local = self.n_true + Cm.shape[0] if n_local is None else n_local
+        dist = halo is not None or n_shared is not None
+        if dist:
+            self.n_shared = int(Cm.shape[1] if n_shared is None else n_shared)
+            self.n_true = int(getattr(C_or_space, "n_true", self.n_shared) if n_true is None else n_true)
+            self.n_local = self.n_shared + Cm.shape[0] if n_local is None else n_local
+        else:
+            self.n_true = Cm.shape[1] if n_true is None else n_true
+            self.n_shared = self.n_true
+            self.n_local = self.n_true + Cm.shape[0] if n_local is None else n_local
         rp = np.ascontiguousarray(Cm.indptr, dtype=np.int32)
         col = np.ascontiguousarray(Cm.indices, dtype=np.int32)
         val = np.ascontiguousarray(Cm.data, dtype=np.float64)
         self.handle = C.c_void_p()
         L = _L()
         L.pa_conform_create.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.pa_conform_create_dist.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 5
+        L.pa_conform_num_shared.argtypes = [C.c_void_p]
         L.pa_conform_destroy.restype = None
         L.pa_conform_destroy.argtypes = [C.c_void_p]
         L.pa_conform_prolongate.argtypes = [C.c_void_p] * 5
@@ -436,12 +450,29 @@ class Conforming:
         L.pa_conform_lanes.argtypes = [C.c_void_p, C.c_int]
         L.pa_conform_prolongate2.argtypes = [C.c_void_p] * 7
         L.pa_conform_restrict2.argtypes = [C.c_void_p] * 6 + [C.c_int, C.c_double] + [C.c_void_p] * 3
-        _lib.check(L.pa_conform_create(ctx.handle, self.n_true, self.n_local, _ptr(rp), _ptr(col), _ptr(val), C.byref(self.handle)))
+        if dist:
+            _lib.check(L.pa_conform_create_dist(ctx.handle, self.n_true, self.n_shared, self.n_local, _ptr(rp), _ptr(col), _ptr(val),
+                                                halo.handle if halo is not None else None, C.byref(self.handle)))
+            assert int(L.pa_conform_num_shared(self.handle)) == self.n_shared
+        else:
+            _lib.check(L.pa_conform_create(ctx.handle, self.n_true, self.n_local, _ptr(rp), _ptr(col), _ptr(val), C.byref(self.handle)))
 
     ADD, ABS, FIX_ONE, FIX_ZERO = 1, 2, 4, 8
 
     def lanes(self, transpose=False):
         return int(_L().pa_conform_lanes(self.handle, int(transpose)))
+
+    def time_pieces(self, x, lx, ly, y, ess_mask=None, reps=100):
+        """Microseconds per call of the pieces of P (masked copy, exchange, rows) and of P^T (fold, exchange, epilogue) of a
+        distributed object (pa_conform_time_pieces; collective)."""
+        assert x.numel() == y.numel() == self.n_true and lx.numel() == ly.numel() == self.n_local
+        L = _L()
+        L.pa_conform_time_pieces.argtypes = [C.c_void_p] * 7 + [C.c_int, C.c_void_p]
+        us = (C.c_double * 6)()
+        _lib.check(L.pa_conform_time_pieces(self.ctx.handle, self.handle, C.c_void_p(x.data_ptr()), C.c_void_p(lx.data_ptr()),
+                                            C.c_void_p(ly.data_ptr()), C.c_void_p(y.data_ptr()),
+                                            C.c_void_p(ess_mask.data_ptr()) if ess_mask is not None else None, int(reps), us))
+        return dict(zip(("copy_masked", "halo_prolongate", "rows", "fold", "halo_restrict_add", "epilogue"), [float(v) for v in us]))
 
     def prolongate(self, x, lx, ess_mask=None):
         """lx = P x (entries flagged in the uint8 tensor ess_mask read as zero): one launch."""
