@@ -394,8 +394,9 @@ public:
 //   Prolongate: masked copy x -> lx[0, n_true), the halo's P on the prefix, the rows of C in place (prefix -> tail)
 //   Restrict:   t = prefix of ly + C^T tail (|C|^T with ABS) into the object's scratch, the halo's P^T on t, the epilogue
 //               (ADD, FIX_ONE / FIX_ZERO) on the owned part
-// The kernels keep the conventions above (lane groups, fixed order, no atomics); the products can be recorded wherever the
-// halo's exchange can.  The four methods keep their meaning, so ParOperator, ComplexParOperator and the transfers take a
+// The pieces are the parts of the one-launch kernels as launches of their own (one set of device functions in pa_conform.hip:
+// lane groups, fixed order, no atomics), so with an empty halo they give the same bits; the products can be recorded wherever
+// the halo's exchange can.  The four methods keep their meaning, so ParOperator, ComplexParOperator and the transfers take a
 // distributed object as they take a one-rank one; the assembled triple product refuses it.
 class Conforming {
   int n_true_, n_con_;
@@ -412,6 +413,11 @@ class Conforming {
   const Halo *halo_ = nullptr;      // plan over the prefix [0, n_shared_); nullptr: no ghosts
   mutable pa::DevBuf<double> d_t_;  // [2][n_shared_ rounded up to even] the folded prefix of Restrict (second half: Restrict2)
   void BuildIndex(const Context &ctx, int n_cols, const int *row_ptr, const int32_t *col, const double *val);
+  // what the four public products go through: the argument checks, then the one-rank launch or the pieces below; a null
+  // second input (x1, ly1) means one vector
+  void ProlongateParts(const double *x0, const double *x1, double *lx0, double *lx1, const uint8_t *ess_mask, hipStream_t stream) const;
+  void RestrictParts(const double *ly0, const double *ly1, double *y0, double *y1, int flags, double a, const uint8_t *ess_mask,
+                     const double *x_ess0, const double *x_ess1, hipStream_t stream) const;
   // pieces: bit 0 the masked copy / the fold, bit 1 the halo's exchange, bit 2 the rows of C / the epilogue (TimePieces)
   void ProlongateDist(const double *x0, const double *x1, double *lx0, double *lx1, const uint8_t *ess_mask, hipStream_t stream,
                       int pieces = 7) const;
@@ -455,8 +461,9 @@ public:
   // after a warm-up; us [6].  The exchange pieces include the wait for the neighbours.
   void TimePieces(const double *x, double *lx, const double *ly, double *y, const uint8_t *ess_mask, int reps, double *us,
                   hipStream_t stream) const;
-  // The same for the two parts of a complex field in one launch each: the index arrays, the values and the mask are read once;
-  // either part is bit-identical to the one-vector call on it.  The outputs must not overlap each other or the inputs.
+  // The same for the two parts of a complex field in one launch each (the same kernels with the second vector riding along):
+  // the index arrays, the values and the mask are read once; either part is bit-identical to the one-vector call on it.  The
+  // outputs must not overlap each other or the inputs.
   void Prolongate2(const double *x0, const double *x1, double *lx0, double *lx1, const uint8_t *ess_mask, hipStream_t stream) const;
   void Restrict2(const double *ly0, const double *ly1, double *y0, double *y1, int flags, double a, const uint8_t *ess_mask,
                  const double *x_ess0, const double *x_ess1, hipStream_t stream) const;

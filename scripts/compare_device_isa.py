@@ -7,7 +7,8 @@ For every named file of palace_amd/csrc the base revision (checked out into a te
 compiled to assembly with `--cuda-device-only -S` and the flags the Makefile of that tree gives the file's object (taken from
 `make -n`, so per-file flags are included).  Required per file:
   * the same set of kernel symbols,
-  * for every kernel the same text from its label to `.end_amdhsa_kernel` (code and kernel descriptor),
+  * for every kernel the same text from its label to `.end_amdhsa_kernel` (code and kernel descriptor; the function's position
+    in the file is taken out of its local labels),
   * for every kernel the same entry in the `amdhsa.kernels` metadata (registers, spills, scratch, LDS, kernarg size).
 Text is compared for equality only; the names of the kernels that differ are printed.  Exit status 1 on any difference.
 """
@@ -58,7 +59,9 @@ def kernels(asm):
         j = start[n]
         while not lines[j].strip().startswith(".end_amdhsa_kernel"):
             j += 1
-        text[n] = "\n".join(lines[start[n]:j + 1])
+        # local labels carry the function's position in the file (.LBB<function>_<block>): drop it, so that adding or removing
+        # another kernel does not make every kernel after it differ
+        text[n] = re.sub(r"\.(LBB|Lfunc_end)\d+", r".\1", "\n".join(lines[start[n]:j + 1]))
     # metadata: the items of the amdhsa.kernels list
     meta, i = {}, lines.index("amdhsa.kernels:") + 1
     item = []

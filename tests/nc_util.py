@@ -74,6 +74,15 @@ def nc_space(name, kind, p):
     return _cache[key]
 
 
+def shifted(a, off):
+    """A device copy of `a` that starts `off` doubles past a fresh allocation (off = 1: not on a 16-byte boundary)."""
+    import torch
+
+    buf = torch.zeros(a.size + off, dtype=torch.float64, device="cuda")
+    buf[off:] = torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    return buf[off:]
+
+
 def rel(a, b):
     return np.max(np.abs(a - b)) / max(np.max(np.abs(b)), 1e-300)
 

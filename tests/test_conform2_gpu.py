@@ -1,6 +1,7 @@
-"""The two-vector kernels of the conforming prolongation (pa_conform.hip: Prolongate2 / Restrict2, both parts of a complex field in
-one launch) against the one-vector kernels, part by part and bit for bit: same lane assignment, same summation order.  Every
-flag combination of test_conform_gpu.py, aligned and misaligned pointers, the identity object and repeats."""
+"""The two-vector form of the conforming prolongation (pa_conform.hip: Prolongate2 / Restrict2, both parts of a complex field in
+one launch: the kernels' TWO = true instantiations) against the one-vector form of the same kernels, part by part and bit for
+bit: same lane assignment, same summation order.  Every flag combination of test_conform_gpu.py, aligned and misaligned
+pointers, the identity object and repeats."""
 import numpy as np
 import pytest
 
@@ -11,6 +12,7 @@ from palace_amd import linalg  # noqa: E402
 from palace_amd.fem import nchex, rthex  # noqa: E402
 from tests import nc_util as nu  # noqa: E402
 from tests import rt_nc_util as rn  # noqa: E402
+from tests.nc_util import shifted as _shifted  # noqa: E402
 
 CASES = [("A", "nd", 2), ("A", "rt", 1), ("A", "rt", 3), ("C", "rt", 2)]
 
@@ -33,13 +35,6 @@ def _setup(ctx, name, kind, p):
         ess = np.nonzero(rng.uniform(0, 1, s.n_true) < 0.1)[0]
     mask[ess] = 1
     return s, linalg.Conforming(ctx, s), rng, mask
-
-
-def _shifted(a, off):
-    """A device copy of `a` that starts `off` doubles past a fresh allocation (off = 1: not on a 16-byte boundary)."""
-    buf = torch.zeros(a.size + off, dtype=torch.float64, device="cuda")
-    buf[off:] = _dev(a)
-    return buf[off:]
 
 
 @pytest.mark.parametrize("name,kind,p", CASES)

@@ -1,6 +1,7 @@
-"""The two kernels of the conforming prolongation with hanging-entity constraints (palace_amd/csrc/pa_conform.hip) against
-scipy: lx = P x and y = P^T ly with P = [I; C], masked and unmasked, overwrite and add, the |C|^T form of the diagonal and both
-essential-row policies.  Tolerance: the 1e-12 relative-to-max of the apply tests."""
+"""The conforming prolongation with hanging-entity constraints (palace_amd/csrc/pa_conform.hip: k_conform_prolongate and
+k_conform_restrict, one launch each, here in their one-vector form) against scipy: lx = P x and y = P^T ly with P = [I; C],
+masked and unmasked, overwrite and add, the |C|^T form of the diagonal and both essential-row policies.  Tolerance: the 1e-12
+relative-to-max of the apply tests.  (Every lane count, on synthetic matrices: test_conform_lanes_gpu.py.)"""
 import numpy as np
 import pytest
 
