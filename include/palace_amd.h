@@ -463,6 +463,13 @@ int pa_op_dense_gather_form(const pa_op *op, int32_t out[2]);
  * simplices), so the pre-assembled D of a quadrature point is the D of the first point times w_q / w_0 and the kernel reads 6
  * values per field and element instead of 6 Q (PALACE_AMD_DENSE_AFFINE=0 at creation time keeps the general form) */
 int pa_op_dense_affine(const pa_op *op);
+/* Which kernel dense sub-operator `sub` (0-based among the dense ones, in the order they were added) runs at an apply:
+ * out[0] PT (16 PT = the padded dof count of an element), out[1] the mode (the DenseMode number of pa_dense.hip: 0..5 the 3-D forms,
+ * 6..10 the plane / boundary forms, 11..13 the line forms), out[2] 1 the LDS-resident form, 0 the staged one, out[3] the geometry
+ * form of the resident kernel: 0 curved (q-data of every point), 1 every block affine, 2 two launches on the lists of the affine and
+ * of the other blocks, out[4] / out[5] the lengths of those two lists, out[6] 1 if an accumulating apply adds through the list of
+ * the rows the block touches, out[7] 1 if the block has a split-vector form. */
+int pa_op_dense_kernel(const pa_op *op, int32_t sub, int32_t out[8]);
 /* Fused form of what ParOperator::Mult does around the local apply for square operators
  * (linalg/rap.cpp:207-220: tx = x; tx[ess] = 0; ly = A P tx): after pa_op_set_essential(list of
  * essential L-dofs), pa_op_mult_essential computes y = A (x with the listed entries read as zero)

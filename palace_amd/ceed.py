@@ -561,6 +561,14 @@ class Operator:
         _lib.check(_lib.load().pa_op_dense_gather_form(self.handle, out))
         return bool(out[0]), int(out[1])
 
+    def dense_kernel(self, sub=0):
+        """Which kernel dense-table block `sub` runs (pa_op_dense_kernel): dict(PT, mode, resident, geometry = 0 curved | 1 affine |
+        2 block lists, lists = (affine blocks, other blocks), rows = adds through its row list, split = has a split-vector form)."""
+        out = (C.c_int32 * 8)()
+        _lib.check(_lib.load().pa_op_dense_kernel(self.handle, C.c_int32(sub), out))
+        return dict(PT=int(out[0]), mode=int(out[1]), resident=bool(out[2]), geometry=int(out[3]), lists=(int(out[4]), int(out[5])),
+                    rows=bool(out[6]), split=bool(out[7]))
+
     def add_mult(self, x, y, a=1.0):
         if a != 1.0:  # operator.cpp:194
             raise _lib.PalaceAmdError("ceed::Operator::AddMult only supports coefficient = 1.0!")

@@ -1507,6 +1507,18 @@ int pa_op_dense_gather_form(const pa_op *op, int32_t out[2]) {
     if (!op->dsubs.empty()) out[0] = op->dsubs[0]->ye_rows ? 1 : 0, out[1] = dense_gather_group(*op->dsubs[0]);
   });
 }
+int pa_op_dense_kernel(const pa_op *op, int32_t sub, int32_t out[8]) {
+  return guarded([&] {
+    PA_REQUIRE(op && out, "null argument");
+    PA_REQUIRE(sub >= 0 && (size_t)sub < op->dsubs.size(), "no such dense sub-operator");
+    const DenseSub &ds = *op->dsubs[(size_t)sub];
+    out[0] = ds.PT, out[1] = ds.mode, out[2] = ds.d_L ? 1 : 0;
+    // (launch_resident_pt: the affine kernels exist for PT <= 3; make_dense_sub sets d_affine for those only)
+    out[3] = !ds.d_L ? 0 : (ds.d_blist[0] ? 2 : (ds.d_affine && ds.PT <= 3 ? 1 : 0));
+    out[4] = ds.n_blist[0], out[5] = ds.n_blist[1];
+    out[6] = ds.d_rows ? 1 : 0, out[7] = dense_split_ok(ds) ? 1 : 0;
+  });
+}
 int pa_op_num_sub(const pa_op *op) { return op ? (int)(op->subs.size() + op->dsubs.size() + op->msubs.size()) : -1; }
 int pa_op_destroy_assembly_data(const pa_op *op) {
   return guarded([&] { PA_REQUIRE(op, "null operator"); });

@@ -1709,7 +1709,9 @@ std::unique_ptr<DenseSub> make_dense_sub(pa_geom *geom, const pa_restriction_des
     const size_t lds = sizeof(double) * ((size_t)rows * S + (r.curl_orients ? (size_t)8 * 4 * PT * 64 : 0));
     const char *force = getenv("PALACE_AMD_DENSE");
     const bool staged = force && std::string(force) == "staged";
-    if (!staged && lds <= 150 * 1024 && is_sym(ds->c0) && (ds->c1.mat.empty() || is_sym(ds->c1))) {
+    // (PT <= 6: the resident kernel is not instantiated for 144 padded dofs -- a block of 97 to 144 dofs whose tables would fit,
+    // a one-component mode with few points, was given the resident form here and then refused at its first apply)
+    if (!staged && PT <= 6 && lds <= 150 * 1024 && is_sym(ds->c0) && (ds->c1.mat.empty() || is_sym(ds->c1))) {
       const int nf = (nci > 0 ? 1 : 0) + (ncd > 0 ? 1 : 0);
       std::vector<double> L((size_t)rows * S, 0.0);
       for (int c = 0; c < nch; c++)

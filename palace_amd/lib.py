@@ -66,6 +66,7 @@ def load():
     lib.pa_device_buffers_live.argtypes = []
     lib.pa_op_algorithmic_bytes.restype = C.c_double
     lib.pa_op_algorithmic_bytes.argtypes = [C.c_void_p]
+    lib.pa_op_dense_kernel.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
     for name in ("pa_geom_destroy", "pa_op_destroy", "pa_error_op_destroy"):
         getattr(lib, name).restype = None
         getattr(lib, name).argtypes = [C.c_void_p]

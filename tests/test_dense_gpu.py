@@ -161,10 +161,11 @@ def test_dense_matches_tensor_kernel(cylinder_mesh):
     assert float((y1 - y2).abs().max() / y2.abs().max()) < REL
 
 
-@pytest.mark.parametrize("p", [1, 2, 3])
+@pytest.mark.parametrize("p", [1, 2, 3, 4, 5])
 def test_hex_boundary_mass(cylinder_mesh, p):
     """Surface Nedelec mass (f_apply_hcurl_32) on the boundary quadrilaterals of a hexahedral space, alone and as a
-    second sub-operator next to the sum-factorised volume operator (impedance-type boundary term)."""
+    second sub-operator next to the sum-factorised volume operator (impedance-type boundary term).  Orders 4 and 5 (40 and 60
+    dofs a face) are the natural elements that run the 2-D mode with three and four tiles of 16 dofs."""
     import torch
 
     from palace_amd import ceed
@@ -182,6 +183,8 @@ def test_hex_boundary_mass(cylinder_mesh, p):
     c3, b3 = util.make_ctx("aniso", 2)
     block = ceed.DenseBlock(ceed.FE_HCURL, nd.ndofs, blk.offsets, interp, None, orients=blk.orients)
     bop = ceed.Operator(nd.ndofs, nd.ndofs).add_dense_integrator(bgeom, block, ceed.QF_HCURL_32, b3, ceed.EVAL_INTERP).finalize()
+    k = bop.dense_kernel()  # MODE_VMASS2 in the resident form, every point's D (the faces of the cylinder are not parallelograms)
+    assert (k["PT"], k["mode"], k["resident"], k["geometry"]) == ((1, 1, 2, 3, 4)[p - 1], 7, True, 0), k
     orc = po.CeedOperatorOracle(nd.ndofs, blk.offsets, blk.orients, interp, np.zeros((1, len(w), blk.P)), og,
                                 po.QF_HCURL_32, c3)
     x = np.random.default_rng(p).uniform(-1, 1, nd.ndofs)
