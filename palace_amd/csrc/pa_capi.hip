@@ -1512,9 +1512,8 @@ int pa_op_dense_kernel(const pa_op *op, int32_t sub, int32_t out[8]) {
     PA_REQUIRE(op && out, "null argument");
     PA_REQUIRE(sub >= 0 && (size_t)sub < op->dsubs.size(), "no such dense sub-operator");
     const DenseSub &ds = *op->dsubs[(size_t)sub];
-    out[0] = ds.PT, out[1] = ds.mode, out[2] = ds.d_L ? 1 : 0;
-    // (launch_resident_pt: the affine kernels exist for PT <= 3; make_dense_sub sets d_affine for those only)
-    out[3] = !ds.d_L ? 0 : (ds.d_blist[0] ? 2 : (ds.d_affine && ds.PT <= 3 ? 1 : 0));
+    const DenseCell cell = dense_kernel_cell(ds);  // (what the launchers select through)
+    out[0] = cell.PT, out[1] = ds.mode, out[2] = cell.resident ? 1 : 0, out[3] = cell.geo;
     out[4] = ds.n_blist[0], out[5] = ds.n_blist[1];
     out[6] = ds.d_rows ? 1 : 0, out[7] = dense_split_ok(ds) ? 1 : 0;
   });

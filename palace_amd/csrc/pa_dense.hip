@@ -28,101 +28,26 @@
 #include <cstring>
 #include <type_traits>
 
+#include "pa_dense_host.hpp"
 #include "pa_device.hpp"
 #include "pa_internal.hpp"
 
 namespace pa {
 
+using namespace densehost;  // modes, plan and table builders: pa_dense_host.hpp
+
 namespace {
 
 typedef double double4_t __attribute__((ext_vector_type(4)));
 
-constexpr int kEB = 16;  // elements per block (N of the MFMA tile)
-
-enum DenseMode {
-  MODE_CURL = 0,      // ND curl-curl              f_apply_hdiv_33 on curl u
-  MODE_VMASS = 1,     // ND mass                   f_apply_hcurl_33 on u
-  MODE_CURLMASS = 2,  // ND curl-curl + mass       f_apply_hdivmass_33
-  MODE_DIFF = 3,      // H1 diffusion              f_apply_hcurl_33 on grad u
-  MODE_DIFFMASS = 4,  // H1 diffusion + mass       f_apply_hcurlmass_33
-  MODE_MASS = 5,      // H1 mass                   f_apply_h1_1
-  // 2-D (fast path only: tables resident in LDS + packed D)
-  MODE_CURL2 = 6,     // 2-D ND curl-curl          f_apply_l2_1 on the scalar curl (q_w input)
-  MODE_VMASS2 = 7,    // 2-D ND mass               f_apply_hcurl_22
-  MODE_CURLMASS2 = 8, // 2-D ND curl-curl + mass   f_apply_hdivmass_22 / _32
-  MODE_DIFF2 = 9,     // 2-D H1 diffusion          f_apply_hcurl_22 / _32 on grad u
-  MODE_DIFFMASS2 = 10, // 2-D H1 diffusion + mass   f_apply_hcurlmass_22 / _32
-  // (MODE_MASS serves the 2-D and 1-D H1 mass too: f_apply_h1_1 only reads w detJ)
-  // line elements (boundaries of plane problems, curves in space): every D is a scalar per point
-  MODE_VMASS1 = 11,    // ND mass on a line         f_apply_hcurl_21 / _31
-  MODE_DIFF1 = 12,     // H1 diffusion on a line    f_apply_hcurl_21 / _31 on du/dxi
-  MODE_DIFFMASS1 = 13  // H1 diffusion + mass       f_apply_hcurlmass_21 / _31
-};
-
 template <int MODE>
 struct ModeTraits {
-  static constexpr int NCI = (MODE == MODE_VMASS || MODE == MODE_CURLMASS) ? 3
-                             : (MODE == MODE_VMASS2 || MODE == MODE_CURLMASS2) ? 2
-                             : (MODE == MODE_DIFFMASS || MODE == MODE_MASS || MODE == MODE_DIFFMASS2 || MODE == MODE_VMASS1 ||
-                                MODE == MODE_DIFFMASS1) ? 1 : 0;
-  static constexpr int NCD = (MODE == MODE_VMASS || MODE == MODE_MASS || MODE == MODE_VMASS2 || MODE == MODE_VMASS1) ? 0
-                             : (MODE == MODE_CURL2 || MODE == MODE_CURLMASS2 || MODE == MODE_DIFF1 || MODE == MODE_DIFFMASS1) ? 1
-                             : (MODE == MODE_DIFF2 || MODE == MODE_DIFFMASS2) ? 2 : 3;
-  static constexpr int NCT = NCI + NCD;
+  static constexpr int NCI = kModeComps[MODE].nci, NCD = kModeComps[MODE].ncd, NCT = NCI + NCD;
 };
 
-int mode_of(int fe_type, int qf, int dim, int sdim) {
-  if (dim == 1) {  // line elements in the plane (21) or in space (31)
-    const int q_vec = sdim == 3 ? PA_QF_HCURL_31 : PA_QF_HCURL_21, q_pair = sdim == 3 ? PA_QF_HCURLMASS_31 : PA_QF_HCURLMASS_21;
-    if (fe_type == PA_FE_HCURL && qf == q_vec) return MODE_VMASS1;
-    if (fe_type == PA_FE_H1 && qf == PA_QF_H1_1) return MODE_MASS;
-    if (fe_type == PA_FE_H1 && qf == q_vec) return MODE_DIFF1;
-    if (fe_type == PA_FE_H1 && qf == q_pair) return MODE_DIFFMASS1;
-    throw Error("QFunction does not match a line element");
-  }
-  if (dim == 2) {  // the same applies for plane elements and for boundary elements in 3-D: only D differs (3x2 geometry)
-    const bool bdr = sdim == 3;
-    if (fe_type == PA_FE_HCURL) {
-      if (qf == PA_QF_L2_1) return MODE_CURL2;
-      if (qf == (bdr ? PA_QF_HCURL_32 : PA_QF_HCURL_22)) return MODE_VMASS2;
-      if (qf == (bdr ? PA_QF_HDIVMASS_32 : PA_QF_HDIVMASS_22)) return MODE_CURLMASS2;
-      throw Error(bdr ? "QFunction does not match an H(curl) boundary element" : "QFunction does not match a 2-D H(curl) element");
-    }
-    if (qf == PA_QF_H1_1) return MODE_MASS;
-    if (qf == (bdr ? PA_QF_HCURL_32 : PA_QF_HCURL_22)) return MODE_DIFF2;
-    if (qf == (bdr ? PA_QF_HCURLMASS_32 : PA_QF_HCURLMASS_22)) return MODE_DIFFMASS2;
-    throw Error(bdr ? "QFunction does not match an H1 boundary element" : "QFunction does not match a 2-D H1 element");
-  }
-  if (fe_type == PA_FE_HCURL) {
-    if (qf == PA_QF_L2_1) return MODE_CURL2;  // (reached through the H(div) alias: div-div, a scalar derivative in 3-D)
-    if (qf == PA_QF_HDIV_33) return MODE_CURL;
-    if (qf == PA_QF_HCURL_33) return MODE_VMASS;
-    if (qf == PA_QF_HDIVMASS_33) return MODE_CURLMASS;
-  } else {
-    if (qf == PA_QF_HCURL_33) return MODE_DIFF;
-    if (qf == PA_QF_HCURLMASS_33) return MODE_DIFFMASS;
-    if (qf == PA_QF_H1_1) return MODE_MASS;
-  }
-  throw Error("QFunction does not match the element type");
-}
-
-void mode_comps(int mode, int &nci, int &ncd) {
-  nci = (mode == MODE_VMASS || mode == MODE_CURLMASS) ? 3
-        : (mode == MODE_VMASS2 || mode == MODE_CURLMASS2) ? 2
-        : (mode == MODE_DIFFMASS || mode == MODE_MASS || mode == MODE_DIFFMASS2 || mode == MODE_VMASS1 || mode == MODE_DIFFMASS1) ? 1
-        : 0;
-  ncd = (mode == MODE_VMASS || mode == MODE_MASS || mode == MODE_VMASS2 || mode == MODE_VMASS1) ? 0
-        : (mode == MODE_CURL2 || mode == MODE_CURLMASS2 || mode == MODE_DIFF1 || mode == MODE_DIFFMASS1) ? 1
-        : (mode == MODE_DIFF2 || mode == MODE_DIFFMASS2) ? 2 : 3;
-}
-
-// position of (dof slot s, lane) of a block's E-vector: lane = kq * 16 + element, dof = 4 s + kq
+// position of (dof slot s, lane) of a block's E-vector: lane = kq * 16 + element, dof = 4 s + kq (block_pos of the host)
 __device__ __forceinline__ int ye_pos(const int rows, const int KP, const int s, const int lane) {
   return rows ? (lane & 15) * (4 * KP) + 4 * s + (lane >> 4) : s * 64 + lane;
-}
-inline size_t ye_pos_host(bool rows, int KP, int e, int d) {  // (element e, local dof d) in the whole E-vector
-  const size_t blk = (size_t)(e / kEB) * 4 * KP * kEB;
-  return rows ? blk + (size_t)(e % kEB) * 4 * KP + d : blk + (size_t)d * kEB + (e % kEB);
 }
 
 struct DenseArgs {
@@ -217,10 +142,7 @@ constexpr int kDenseThreads = 64 * kDenseWaves;
 // curl / gradient part) and the number of components before it.
 template <int MODE, int F>
 struct FieldTraits {
-  using M = ModeTraits<MODE>;
-  static constexpr int NF = (M::NCI > 0 ? 1 : 0) + (M::NCD > 0 ? 1 : 0);
-  static constexpr int NC = (NF == 2) ? (F == 0 ? M::NCI : M::NCD) : M::NCT;
-  static constexpr int CB = (NF == 2 && F == 1) ? M::NCI : 0;
+  static constexpr int NF = kModeComps[MODE].nf(), NC = kModeComps[MODE].nc(F), CB = kModeComps[MODE].cb(F);
 };
 
 // D on the components of one field at one quadrature point (in place).  The paired QFunctions
@@ -439,7 +361,7 @@ __global__ __launch_bounds__(kDenseThreads, (PT <= 4 ? 2 : 1)) void dense_apply_
 // two lanes).  No barrier after the initial load: every wave walks its own element blocks.
 template <int PT>
 struct ResidentStride {
-  static constexpr int S = 16 * PT + ((PT & 1) ? 2 : 18);
+  static constexpr int S = resident_stride(PT);
 };
 
 constexpr int kResWaves = 8;
@@ -1052,33 +974,52 @@ __global__ void dense_diag_qd_kernel(const DenseArgs a, const int32_t *__restric
   diag[gid] = d;  // element diagonal; dense_diag_slot_kernel pushes it through the transposed unsigned restriction
 }
 
+// ---- launches of the resident kernel ------------------------------------------------------------------------------------------
+// One instantiation: its dynamic-LDS attribute (once) and its launch.  A list kernel works on a.blist, the complex form has two
+// units (real and imaginary part) per block.
+template <int PT, int MODE, bool AFFINE, bool CPLX, bool LIST, bool SPLIT>
+void launch_resident_cell(const DenseSub &ds, const DenseArgs &a, hipStream_t s) {
+  constexpr int NW = (AFFINE && !CPLX) ? kAffWaves : kResWaves;  // (the kernel's launch bounds)
+  const int units = (CPLX ? 2 : 1) * (LIST ? a.nblist : ds.nb);
+  if (units == 0) return;
+  const auto kernel = dense_apply_resident_kernel<PT, MODE, AFFINE, CPLX, LIST, SPLIT>;
+  static std::atomic<bool> attr_set{false};  // idempotent set-up; rank threads may race here
+  if (!attr_set) {
+    PA_HIP(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLaunchLimit));
+    attr_set = true;
+  }
+  const int grid = std::min((units + NW - 1) / NW, ds.num_cu);
+  const size_t shm = resident_launch_bytes(a.Q4, ds.L_rows, PT, ds.d_co != nullptr, NW);
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(64 * NW), shm, s, a, ds.L_rows);
+}
+
+// The geometry form of one (PT, MODE), chosen through dense_kernel_cell.  The affine and list kernels exist for PT <= 3 (larger
+// blocks have no registers for the values kept across the block); split-vector applies have no list form (dense_split_ok).
+template <int PT, int MODE, bool CPLX, bool SPLIT>
+void launch_resident_mode(const DenseSub &ds, const DenseArgs &a, hipStream_t s) {
+  constexpr bool SMALL = PT <= 3;
+  const int geo = dense_kernel_cell(ds).geo;
+  if constexpr (!SPLIT) {
+    if (geo == kGeoList) {  // affine and curved blocks: one launch each on its list (they write disjoint E-vector blocks)
+      DenseArgs aa = a, ag = a;
+      aa.blist = ds.d_blist[0], aa.nblist = ds.n_blist[0];
+      ag.blist = ds.d_blist[1], ag.nblist = ds.n_blist[1], ag.affine = nullptr;
+      launch_resident_cell<PT, MODE, SMALL, CPLX, SMALL, SPLIT>(ds, aa, s);
+      launch_resident_cell<PT, MODE, false, CPLX, SMALL, SPLIT>(ds, ag, s);
+      return;
+    }
+  }
+  if (geo == kGeoAffine) launch_resident_cell<PT, MODE, SMALL, CPLX, false, SPLIT>(ds, a, s);
+  else launch_resident_cell<PT, MODE, false, CPLX, false, SPLIT>(ds, a, s);
+}
+
 // split-vector launches: the 3-D forms a multi-rank solve applies (curl-curl, vector mass, both, diffusion), PT <= 3, one kind of block
 static bool resident_split_mode(int mode) { return mode == MODE_CURL || mode == MODE_VMASS || mode == MODE_CURLMASS || mode == MODE_DIFF; }
 template <int PT>
 void launch_resident_split(const DenseSub &ds, const DenseArgs &a, hipStream_t s) {
-  const int rows = ds.L_rows;
-  const bool affine = a.affine != nullptr;
-  const int nw = affine ? kAffWaves : kResWaves;
-  const size_t shm = sizeof(double) * ((size_t)(a.Q4 + 31) / 32 * 32 + (size_t)rows * ResidentStride<PT>::S +
-                                      (ds.d_co ? (size_t)nw * 4 * PT * 64 : 0));
-  if (ds.nb == 0) return;
-  const int grid = std::min((ds.nb + nw - 1) / nw, ds.num_cu);
   switch (ds.mode) {
-#define PA_RES_SPLIT_CASE(MODE)                                                                                          \
-  case MODE: {                                                                                                           \
-    static std::atomic<bool> attr_set{false};                                                                            \
-    if (!attr_set) {                                                                                                     \
-      PA_HIP(hipFuncSetAttribute((const void *)dense_apply_resident_kernel<PT, MODE, false, false, false, true>,         \
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));                               \
-      PA_HIP(hipFuncSetAttribute((const void *)dense_apply_resident_kernel<PT, MODE, true, false, false, true>,          \
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));                               \
-      attr_set = true;                                                                                                   \
-    }                                                                                                                    \
-    if (affine)                                                                                                          \
-      hipLaunchKernelGGL((dense_apply_resident_kernel<PT, MODE, true, false, false, true>), dim3(grid), dim3(64 * nw), shm, s, a, rows); \
-    else                                                                                                                 \
-      hipLaunchKernelGGL((dense_apply_resident_kernel<PT, MODE, false, false, false, true>), dim3(grid), dim3(64 * kResWaves), shm, s, a, rows); \
-  } break;
+#define PA_RES_SPLIT_CASE(MODE) \
+  case MODE: launch_resident_mode<PT, MODE, false, true>(ds, a, s); break;
     PA_RES_SPLIT_CASE(MODE_CURL)
     PA_RES_SPLIT_CASE(MODE_VMASS)
     PA_RES_SPLIT_CASE(MODE_CURLMASS)
@@ -1091,47 +1032,9 @@ void launch_resident_split(const DenseSub &ds, const DenseArgs &a, hipStream_t s
 
 template <int PT>
 void launch_resident_pt(const DenseSub &ds, const DenseArgs &a, hipStream_t s) {
-  const int rows = ds.L_rows;
-  if (ds.d_blist[0] && !a.blist) {  // affine and curved blocks: one launch each on its list (they write disjoint E-vector blocks)
-    DenseArgs aa = a, ag = a;
-    aa.blist = ds.d_blist[0], aa.nblist = ds.n_blist[0];
-    ag.blist = ds.d_blist[1], ag.nblist = ds.n_blist[1], ag.affine = nullptr;
-    launch_resident_pt<PT>(ds, aa, s);
-    launch_resident_pt<PT>(ds, ag, s);
-    return;
-  }
-  const bool affine = a.affine && PT <= 3;  // (make_dense_sub: larger blocks have no registers for the values kept across the block)
-  const int nw = affine ? kAffWaves : kResWaves;
-  const size_t shm = sizeof(double) * ((size_t)(a.Q4 + 31) / 32 * 32 + (size_t)rows * ResidentStride<PT>::S +
-                                      (ds.d_co ? (size_t)nw * 4 * PT * 64 : 0));
-  const int nblocks = a.blist ? a.nblist : ds.nb;
-  if (nblocks == 0) return;
-  int grid = (nblocks + nw - 1) / nw;
-  if (grid > ds.num_cu) grid = ds.num_cu;
   switch (ds.mode) {
-#define PA_RES_CASE(MODE)                                                                                \
-  case MODE: {                                                                                           \
-    static std::atomic<bool> attr_set{false}; /* idempotent set-up; rank threads may race here */ \
-    if (!attr_set) {                                                                                     \
-      PA_HIP(hipFuncSetAttribute((const void *)dense_apply_resident_kernel<PT, MODE, false>,             \
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));               \
-      PA_HIP(hipFuncSetAttribute((const void *)dense_apply_resident_kernel<PT, MODE, (PT <= 3)>,         \
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));               \
-      PA_HIP(hipFuncSetAttribute((const void *)dense_apply_resident_kernel<PT, MODE, false, false, (PT <= 3)>, \
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));               \
-      PA_HIP(hipFuncSetAttribute((const void *)dense_apply_resident_kernel<PT, MODE, (PT <= 3), false, (PT <= 3)>, \
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));               \
-      attr_set = true;                                                                                   \
-    }                                                                                                    \
-    if (a.blist && affine)                                                                               \
-      hipLaunchKernelGGL((dense_apply_resident_kernel<PT, MODE, (PT <= 3), false, (PT <= 3)>), dim3(grid), dim3(64 * nw), shm, s, a, rows); \
-    else if (a.blist)                                                                                    \
-      hipLaunchKernelGGL((dense_apply_resident_kernel<PT, MODE, false, false, (PT <= 3)>), dim3(grid), dim3(64 * kResWaves), shm, s, a, rows); \
-    else if (affine)                                                                                     \
-      hipLaunchKernelGGL((dense_apply_resident_kernel<PT, MODE, (PT <= 3)>), dim3(grid), dim3(64 * nw), shm, s, a, rows); \
-    else                                                                                                 \
-      hipLaunchKernelGGL((dense_apply_resident_kernel<PT, MODE, false>), dim3(grid), dim3(64 * kResWaves), shm, s, a, rows); \
-  } break;
+#define PA_RES_CASE(MODE) \
+  case MODE: launch_resident_mode<PT, MODE, false, false>(ds, a, s); break;
     PA_RES_CASE(MODE_CURL)
     PA_RES_CASE(MODE_VMASS)
     PA_RES_CASE(MODE_CURLMASS)
@@ -1315,6 +1218,7 @@ __global__ void dense_diag_slot_kernel(const int ne, const int P, const int KP, 
     if (j + 1 < P) v += fabs((double)t[3 + 0]) * d[j + 1];
     if (j > 0) v += fabs((double)t[-3 + 2]) * d[j - 1];
   }
+  // (block_pos of the host, written out: through the shared function hipcc orders this kernel's address arithmetic differently)
   const size_t pos = ((size_t)(e / kEB) * 4 * KP + j) * kEB + (e % kEB);  // (the index table keeps the [dof][element] rows)
   const size_t blk = (size_t)(e / kEB) * 4 * KP * kEB;
   ye[ye_rows ? blk + (size_t)(e % kEB) * 4 * KP + j : pos] = idx[pos] < 0 ? -v : v;
@@ -1350,7 +1254,7 @@ DenseArgs make_args(const DenseSub &ds) {
   a.ne = ds.ne, a.nb = ds.nb, a.P = ds.P, a.Q = ds.Q, a.Qpad = ds.Qpad, a.nch = ds.nch, a.KP = ds.KP;
   a.idx = ds.d_idx, a.co = ds.d_co, a.co2 = ds.d_co2, a.geom = ds.geom->d_geom, a.qw = ds.geom->d_qw, a.Tf = ds.d_Tf, a.Tt = ds.d_Tt;
   a.contra = ds.contra ? 1 : 0;
-  a.L = ds.d_L, a.qdata = ds.d_qdata, a.ncq = ds.ncq, a.Q4 = (ds.Q + 3) / 4 * 4;
+  a.L = ds.d_L, a.qdata = ds.d_qdata, a.ncq = ds.ncq, a.Q4 = round_up4(ds.Q);
   a.affine = ds.d_affine, a.wrel = ds.d_wrel;
   a.x1 = nullptr, a.ye1 = nullptr, a.qdata_i = nullptr, a.ncq_i = 0, a.qi_mass = a.qi_curl = -1;
   a.blist = nullptr, a.nblist = 0;
@@ -1388,436 +1292,272 @@ void launch_geom_dense(const pa_mesh_dense_desc &mesh, Geom &g, hipStream_t s) {
   PA_HIP(hipMemsetAsync(g.d_geom, 0, sizeof(double) * count, s));
   const long long n = (long long)ne * Q;
   const int bs = 256;
-  if (dim == 1 && sdim == 3)
-    hipLaunchKernelGGL(geom_dense1_kernel<3>, dim3((unsigned)((n + bs - 1) / bs)), dim3(bs), 0, s, ne, Q, g.Qpad, npe, d_off,
-                       d_nodes, d_attr, d_grad, d_w, g.d_geom.get());
-  else if (dim == 1)
-    hipLaunchKernelGGL(geom_dense1_kernel<2>, dim3((unsigned)((n + bs - 1) / bs)), dim3(bs), 0, s, ne, Q, g.Qpad, npe, d_off,
-                       d_nodes, d_attr, d_grad, d_w, g.d_geom.get());
-  else if (dim == 2 && sdim == 3)
-    hipLaunchKernelGGL(geom_dense32_kernel, dim3((unsigned)((n + bs - 1) / bs)), dim3(bs), 0, s, ne, Q, g.Qpad, npe, d_off,
-                       d_nodes, d_attr, d_grad, d_w, g.d_geom.get());
-  else if (dim == 2)
-    hipLaunchKernelGGL(geom_dense2_kernel, dim3((unsigned)((n + bs - 1) / bs)), dim3(bs), 0, s, ne, Q, g.Qpad, npe, d_off,
-                       d_nodes, d_attr, d_grad, d_w, g.d_geom.get());
-  else
-    hipLaunchKernelGGL(geom_dense_kernel, dim3((unsigned)((n + bs - 1) / bs)), dim3(bs), 0, s, ne, Q, g.Qpad, npe, d_off,
-                       d_nodes, d_attr, d_grad, d_w, g.d_geom.get());
+  const auto kernel = dim == 1   ? (sdim == 3 ? geom_dense1_kernel<3> : geom_dense1_kernel<2>)
+                      : dim == 2 ? (sdim == 3 ? geom_dense32_kernel : geom_dense2_kernel)
+                                 : geom_dense_kernel;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)((n + bs - 1) / bs)), dim3(bs), 0, s, ne, Q, g.Qpad, npe, d_off, d_nodes, d_attr, d_grad,
+                     d_w, g.d_geom.get());
   PA_HIP(hipGetLastError());
   PA_HIP(hipStreamSynchronize(s));
 }
 
-std::unique_ptr<DenseSub> make_dense_sub(pa_geom *geom, const pa_restriction_desc &r, const pa_dense_basis_desc &b, int qf,
-                                         const void *ctx, size_t ctx_size, uint32_t trial_ops, uint32_t test_ops, int height,
-                                         bool contra) {
-  PA_REQUIRE(geom && geom->eb == kEB, "geometry data must come from pa_geom_create_dense");
-  if (b.fe_type == PA_FE_HDIV) {
-    // H(div) elements run on the arithmetic of an existing mode: the tables change places, the D of the values takes the
-    // contravariant map (`contra`: AdjJt of the stored adj(J)^T / detJ, what f_apply_hdiv_* do first).
-    const int d = 10 * geom->sdim + geom->dim;
-    const uint32_t t_ops = trial_ops & ~(uint32_t)PA_EVAL_WEIGHT, s_ops = test_ops & ~(uint32_t)PA_EVAL_WEIGHT;
-    pa_dense_basis_desc alias = b;
-    if (qf == PA_QF_L2_1) {
-      // div-div (fem/integ/divdiv.cpp: Div | Weight, f_apply_l2_1 for single-component elements): the scalar-derivative
-      // arithmetic of the 2-D curl-curl, c qw^2 / (w detJ), with the divergence table [Q][P] in the place of the curl table
-      PA_REQUIRE((d == 33 || d == 22 || d == 32) && t_ops == PA_EVAL_DIV && s_ops == PA_EVAL_DIV && b.deriv,
-                 "H(div) elements: the div-div operator takes the divergence table with Div (| Weight)");
-      alias.fe_type = PA_FE_HCURL, alias.interp = nullptr;
-      return make_dense_sub(geom, r, alias, qf, ctx, ctx_size, PA_EVAL_CURL, PA_EVAL_CURL, height);
-    }
-    const int q_mass = d == 33 ? PA_QF_HDIV_33 : d == 22 ? PA_QF_HDIV_22 : d == 32 ? PA_QF_HDIV_32 : d == 21 ? PA_QF_HDIV_21 : PA_QF_HDIV_31;
-    const int q_pair = d == 33   ? PA_QF_L2MASS_33
-                       : d == 22 ? PA_QF_L2MASS_22
-                       : d == 32 ? PA_QF_L2MASS_32
-                       : d == 21 ? PA_QF_L2MASS_21
-                                 : PA_QF_L2MASS_31;
-    if (qf == q_mass) {
-      PA_REQUIRE(t_ops == PA_EVAL_INTERP && s_ops == PA_EVAL_INTERP && b.interp, "H(div) mass: Interp on the value table");
-      if (d == 33) {
-        // (fem/integ/vecfemass.cpp with an RT space: Interp + f_apply_hdiv_33) the arithmetic of the curl-curl operator with the
-        // value table in the place of the curl table
-        alias.fe_type = PA_FE_HCURL, alias.deriv = b.interp, alias.interp = nullptr;
-        return make_dense_sub(geom, r, alias, qf, ctx, ctx_size, PA_EVAL_CURL, PA_EVAL_CURL, height);
-      }
-      // plane, boundary and line elements (f_apply_hdiv_22 | _32 | _21 | _31): the vector mass of the geometry with the
-      // contravariant map in the place of adjJt
-      alias.fe_type = PA_FE_HCURL;
-      const int q_cov = d == 22 ? PA_QF_HCURL_22 : d == 32 ? PA_QF_HCURL_32 : d == 21 ? PA_QF_HCURL_21 : PA_QF_HCURL_31;
-      return make_dense_sub(geom, r, alias, q_cov, ctx, ctx_size, PA_EVAL_INTERP, PA_EVAL_INTERP, height, true);
-    }
-    PA_REQUIRE(qf == q_pair, "H(div) elements: the mass operator (Interp, hdiv_*), div-div (Div, l2_1) and div-div + mass "
-                             "(Interp | Div, l2mass_*) of the geometry's dimensions are supported");
-    // DivDivMassIntegrator (fem/integ/divdivmass.cpp: Interp | Div | Weight, f_apply_l2mass_*; pair context: mass first)
-    PA_REQUIRE(t_ops == (PA_EVAL_INTERP | PA_EVAL_DIV) && s_ops == t_ops && b.interp && b.deriv,
-               "div-div + mass: value and divergence tables with Interp | Div (| Weight)");
-    if (d == 22 || d == 32) {  // the plane / boundary curl-curl + mass: two values, one scalar derivative
-      alias.fe_type = PA_FE_HCURL;
-      return make_dense_sub(geom, r, alias, d == 22 ? PA_QF_HDIVMASS_22 : PA_QF_HDIVMASS_32, ctx, ctx_size,
-                            PA_EVAL_INTERP | PA_EVAL_CURL, PA_EVAL_INTERP | PA_EVAL_CURL, height, true);
-    }
-    alias.fe_type = PA_FE_H1;
-    if (d == 33) {  // diffusion + mass with the roles exchanged: one "value" (the divergence), three "derivatives" (the values)
-      alias.interp = b.deriv, alias.deriv = b.interp;
-      return make_dense_sub(geom, r, alias, PA_QF_HCURLMASS_33, ctx, ctx_size, PA_EVAL_INTERP | PA_EVAL_GRAD,
-                            PA_EVAL_INTERP | PA_EVAL_GRAD, height, true);
-    }
-    // line elements: one value, one derivative -- the tables stay where they are
-    return make_dense_sub(geom, r, alias, d == 21 ? PA_QF_HCURLMASS_21 : PA_QF_HCURLMASS_31, ctx, ctx_size,
-                          PA_EVAL_INTERP | PA_EVAL_GRAD, PA_EVAL_INTERP | PA_EVAL_GRAD, height, true);
-  }
+// ---- set-up of one block: the stages of make_dense_sub -----------------------------------------------------------------------------
+namespace {
+
+// The block as the alias leaves it against the geometry data, the restriction and the operator; returns its mode.
+int validate_dense(const Geom &geom, const pa_restriction_desc &r, const pa_dense_basis_desc &b, int qf, uint32_t trial_ops,
+                   uint32_t test_ops, int height) {
   PA_REQUIRE(b.fe_type == PA_FE_H1 || b.fe_type == PA_FE_HCURL, "unknown element type");
-  PA_REQUIRE(b.num_dofs > 0 && b.num_qpts == geom->Q, "basis and geometry data disagree on the quadrature rule");
-  PA_REQUIRE(r.num_elem == geom->ne && r.elem_size == b.num_dofs, "restriction does not match mesh / basis");
+  PA_REQUIRE(b.num_dofs > 0 && b.num_qpts == geom.Q, "basis and geometry data disagree on the quadrature rule");
+  PA_REQUIRE(r.num_elem == geom.ne && r.elem_size == b.num_dofs, "restriction does not match mesh / basis");
   PA_REQUIRE(r.lsize == height && r.offsets, "restriction L-vector size does not match the operator");
   PA_REQUIRE(!(r.orients && r.curl_orients), "restriction is either oriented or curl-oriented");
   PA_REQUIRE(r.lsize < (1 << 29), "too many local dofs for the index encoding");
-  const int P = b.num_dofs, Q = b.num_qpts, ne = r.num_elem;
-  const int dim = geom->dim;
-  const int sdim = geom->sdim;
-  const int mode = mode_of(b.fe_type, qf, dim, sdim);
-  int nci, ncd;
-  mode_comps(mode, nci, ncd);
-  const int nct = nci + ncd;
+  const int mode = mode_of(b.fe_type, qf, geom.dim, geom.sdim);
+  const int nci = mode_comps(mode).nci, ncd = mode_comps(mode).ncd;
   PA_REQUIRE(nci == 0 || b.interp, "interp table missing");
   PA_REQUIRE(ncd == 0 || b.deriv, "curl / gradient table missing");
-  {
-    const uint32_t want_i = nci ? PA_EVAL_INTERP : 0u;
-    const uint32_t want_d = ncd ? (b.fe_type == PA_FE_HCURL ? PA_EVAL_CURL : PA_EVAL_GRAD) : 0u;
-    // 2-D curl-curl adds the Weight input (integ/curlcurl.cpp:65-68): accepted, the weights live in the geometry data
-    const uint32_t got = trial_ops & ~(uint32_t)PA_EVAL_WEIGHT;
-    // (the reference adds Weight to the trial side only, integ/curlcurl.cpp:62-68)
-    PA_REQUIRE(got == (want_i | want_d) && (test_ops & ~(uint32_t)PA_EVAL_WEIGHT) == got, "eval modes do not match the QFunction");
-  }
-  static const int kPT[] = {1, 2, 3, 4, 6, 9};
-  int PT = 0;
-  for (int v : kPT)
-    if (P <= 16 * v) {
-      PT = v;
-      break;
-    }
+  const uint32_t want_i = nci ? PA_EVAL_INTERP : 0u;
+  const uint32_t want_d = ncd ? (b.fe_type == PA_FE_HCURL ? PA_EVAL_CURL : PA_EVAL_GRAD) : 0u;
+  // 2-D curl-curl adds the Weight input (integ/curlcurl.cpp:65-68): accepted, the weights live in the geometry data
+  const uint32_t got = trial_ops & ~(uint32_t)PA_EVAL_WEIGHT;
+  // (the reference adds Weight to the trial side only, integ/curlcurl.cpp:62-68)
+  PA_REQUIRE(got == (want_i | want_d) && (test_ops & ~(uint32_t)PA_EVAL_WEIGHT) == got, "eval modes do not match the QFunction");
+  const int PT = dense_pt(b.num_dofs);
   PA_REQUIRE(PT > 0, "element has more than 144 dofs: not instantiated");
+  return mode;
+}
 
+// E: block-transposed index (+ packed tridiagonal rows), the transpose map for the gather form of E^T and the E-vector.
+// Returns the copies of every dof in dof order (build_transpose) for choose_elayout.
+std::vector<int32_t> upload_restriction(DenseSub &ds, const DensePlan &p, const pa_restriction_desc &r) {
+  std::vector<int32_t> idx, tptr, ted;
+  std::vector<uint16_t> co;
+  std::vector<uint32_t> co2;
+  build_index(p, r, idx, co, co2);
+  ds.d_idx = dev_upload(idx.data(), idx.size());
+  if (r.curl_orients) ds.d_co = dev_upload(co.data(), co.size()), ds.d_co2 = dev_upload(co2.data(), co2.size());
+  build_transpose(p, r, tptr, ted);
+  ds.d_tptr = dev_upload(tptr.data(), tptr.size());
+  ds.d_ye = dev_alloc<double>(num_slots(p));
+  // a block that touches few of the dofs (the surface terms of a driven problem: a few thousand boundary faces in a space of
+  // millions) adds its result through the list of the rows it has: its gather was a pass over the whole vector, 58 times per
+  // FGMRES iteration of config 3 (round 5: 3.7 % of that solve's device time)
+  if (few_rows(p, r.lsize)) {
+    const std::vector<int32_t> rows = touched_rows(tptr);
+    ds.n_rows = (int)rows.size();
+    ds.d_rows = dev_upload(rows.data(), std::max<size_t>(rows.size(), 1));
+  }
+  ds.h_co = std::move(co), ds.h_idx = std::move(idx);
+  return ted;
+}
+
+// Which rows the E-vector gets (DenseArgs::ye_rows) is decided by what the GATHER does with them, MEASURED here on blocks large
+// enough for it to matter: a mesh numbered with locality in the [dof] rows (a Kuhn-split cube: consecutive elements share
+// entities at the same local index, and neighbouring waves of the gather re-read each other's rows from L2) keeps them -- there
+// the rows by element only cost the apply kernel its coalesced stores (+3 us of 186) -- an unstructured mesh (config 3's) reads
+// one 64-byte sector per 8-byte entry from the [dof] rows and a third of that from the rows by element (gather of 2.18M order-3
+// dofs: 64 -> 37 us).  The sums do not depend on the choice (same copies, same order): timing noise cannot change a result.
+// `forced`: 1 rows by element, 0 rows by dof (PALACE_AMD_DENSE_ELAYOUT=rows | block), -1 measure.
+void choose_elayout(DenseSub &ds, const DensePlan &p, const pa_restriction_desc &r, const std::vector<int32_t> &ted, int forced,
+                    bool verbose) {
+  std::vector<int32_t> tent;
+  if (forced == 1) ds.ye_rows = true;
+  else if (forced == 0 || r.lsize < (1 << 17)) ds.ye_rows = false;
+  else {
+    PA_HIP(hipMemset(ds.d_ye, 0, num_slots(p) * sizeof(double)));
+    double t[2];
+    for (int rows = 0; rows < 2; rows++) {
+      build_tent(p, r, ted, rows != 0, tent);
+      const DevBuf<int32_t> d_t = dev_upload(tent.data(), tent.size());
+      t[rows] = time_dense_gather(ds, d_t);
+    }
+    ds.ye_rows = t[1] < 0.85 * t[0];
+    if (verbose)
+      std::fprintf(stderr, "[palace_amd] dense block %d elements x %d dofs: gather %.1f us by dof rows, %.1f us by element rows -> %s\n",
+                   p.ne, p.P, 1e3 * t[0], 1e3 * t[1], ds.ye_rows ? "element rows" : "dof rows");
+  }
+  build_tent(p, r, ted, ds.ye_rows, tent);
+  ds.d_tent = dev_upload(tent.data(), tent.size());
+}
+
+// B: MFMA A-operand fragments (see the header comment for the row order), the checksums, plain copies for the diagonal kernel
+void upload_tables(DenseSub &ds, const DensePlan &p, const Tables &T, const pa_restriction_desc &r) {
+  std::vector<double> Tf, Tt;
+  build_fragments(p, T, Tf, Tt);
+  ds.d_Tf = dev_upload(Tf.data(), Tf.size());
+  ds.d_Tt = dev_upload(Tt.data(), Tt.size());
+  const size_t n = (size_t)p.ne * p.P, ni = (size_t)T.m.nci * p.Q * p.P, nd = (size_t)T.m.ncd * p.Q * p.P;
+  ds.chk_interp = table_checksum(T.interp, ni), ds.chk_deriv = table_checksum(T.deriv, nd);
+  if (ni) ds.d_interp = dev_upload(T.interp, ni);
+  if (nd) ds.d_deriv = dev_upload(T.deriv, nd);
+  ds.d_off = dev_upload(r.offsets, n);
+  ds.h_off.assign(r.offsets, r.offsets + n);
+  if (r.curl_orients) ds.d_cor = dev_upload(r.curl_orients, 3 * n);
+}
+
+// D: the coefficient context(s), in the order ctx_layout gives for the block
+void parse_contexts(DenseSub &ds, const void *ctx, size_t ctx_size) {
+  PA_REQUIRE(ctx && ctx_size >= 16 && ctx_size % 8 == 0, "bad coefficient context");
+  ds.ctx_blob.assign((const uint8_t *)ctx, (const uint8_t *)ctx + ctx_size);
+  const CtxLayout l = ctx_layout(ds.mode, ds.contra, ds.geom->sdim);
+  size_t at = 0;
+  for (int k = 0; k < l.n; k++) {
+    CoeffHost &c = l.part[k].slot ? ds.c1 : ds.c0;
+    parse_coeff(ctx, ctx_size, l.part[k].dim, c, at);
+    at += c.slots;
+  }
+}
+
+// packed D of every point: one of 17 kernels by the dimensions of the element and of the space
+void launch_dense_qdata(DenseSub &ds, const DenseArgs &a) {
+  const int dim = ds.geom->dim, sdim = ds.geom->sdim, mode = ds.mode;
+  const long long n = (long long)ds.ne * ds.Q;
+  const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+  if (dim == 1) {
+    switch (mode) {
+#define PA_QD1_CASE(MODE)                                                                         \
+  case MODE:                                                                                      \
+    if (sdim == 3)                                                                                \
+      hipLaunchKernelGGL((dense_qdata1_kernel<MODE, 3>), grid, block, 0, nullptr, a, ds.d_qdata); \
+    else                                                                                          \
+      hipLaunchKernelGGL((dense_qdata1_kernel<MODE, 2>), grid, block, 0, nullptr, a, ds.d_qdata); \
+    break;
+      PA_QD1_CASE(MODE_MASS)
+      PA_QD1_CASE(MODE_VMASS1)
+      PA_QD1_CASE(MODE_DIFF1)
+      PA_QD1_CASE(MODE_DIFFMASS1)
+#undef PA_QD1_CASE
+    }
+  } else if (dim == 3 && mode == MODE_CURL2) {
+    hipLaunchKernelGGL((dense_qdata2_kernel<MODE_CURL2, 11>), grid, block, 0, nullptr, a, ds.d_qdata);
+  } else if (dim == 2) {
+    switch (mode) {
+#define PA_QD2_CASE(MODE)                                                                         \
+  case MODE:                                                                                      \
+    if (sdim == 3)                                                                                \
+      hipLaunchKernelGGL((dense_qdata2_kernel<MODE, 8>), grid, block, 0, nullptr, a, ds.d_qdata); \
+    else                                                                                          \
+      hipLaunchKernelGGL((dense_qdata2_kernel<MODE, 6>), grid, block, 0, nullptr, a, ds.d_qdata); \
+    break;
+      PA_QD2_CASE(MODE_CURL2)
+      PA_QD2_CASE(MODE_VMASS2)
+      PA_QD2_CASE(MODE_CURLMASS2)
+      PA_QD2_CASE(MODE_MASS)
+      PA_QD2_CASE(MODE_DIFF2)
+      PA_QD2_CASE(MODE_DIFFMASS2)
+#undef PA_QD2_CASE
+    }
+  } else {
+    switch (mode) {
+#define PA_QD_CASE(MODE) \
+  case MODE: hipLaunchKernelGGL((dense_qdata_kernel<MODE>), grid, block, 0, nullptr, a, ds.d_qdata); break;
+      PA_QD_CASE(MODE_CURL)
+      PA_QD_CASE(MODE_VMASS)
+      PA_QD_CASE(MODE_CURLMASS)
+      PA_QD_CASE(MODE_DIFF)
+      PA_QD_CASE(MODE_DIFFMASS)
+      PA_QD_CASE(MODE_MASS)
+#undef PA_QD_CASE
+    }
+  }
+  PA_HIP(hipGetLastError());
+  PA_HIP(hipStreamSynchronize(nullptr));
+}
+
+// fast path: tables resident in LDS (one copy, rows in tile order, stride S) + packed D
+void setup_resident(DenseSub &ds, const DensePlan &p, const Tables &T) {
+  std::vector<double> L;
+  build_resident(p, T, L);
+  ds.d_L = dev_upload(L.data(), L.size());
+  ds.L_rows = p.rows, ds.ncq = p.ncq;
+  const size_t nq = (size_t)p.nb * p.ncq * p.Q4 * kEB;
+  ds.d_qdata = dev_alloc<double>(nq);
+  PA_HIP(hipMemset(ds.d_qdata, 0, sizeof(double) * nq));
+  int dev = 0;
+  PA_HIP(hipGetDevice(&dev));
+  PA_HIP(hipDeviceGetAttribute(&ds.num_cu, hipDeviceAttributeMultiprocessorCount, dev));
+  launch_dense_qdata(ds, make_args(ds));
+}
+
+// affine blocks read one point of q-data: flags per block, and the two block lists of a mesh with curved parts
+void detect_affine(DenseSub &ds, const DensePlan &p) {
+  const Geom &geom = *ds.geom;
+  const int nb = p.nb, Q = p.Q;
+  if (!(affine_fits(p, ds.d_co != nullptr, kAffWaves) && (int)geom.wq.size() == Q && geom.wq[0] != 0.0)) return;
+  const DevBuf<unsigned int> d_na = dev_alloc<unsigned int>((size_t)nb);
+  PA_HIP(hipMemset(d_na, 0, sizeof(unsigned int) * nb));
+  hipLaunchKernelGGL(dense_affine_kernel, dim3((unsigned)((nb * kEB + 255) / 256)), dim3(256), 0, nullptr, nb, p.ncq, Q, p.Q4,
+                     ds.d_qdata, geom.d_qw, d_na);
+  PA_HIP(hipGetLastError());
+  std::vector<unsigned int> na((size_t)nb);
+  PA_HIP(hipMemcpy(na.data(), d_na, sizeof(unsigned int) * nb, hipMemcpyDeviceToHost));
+  std::vector<uint8_t> flag((size_t)nb);
+  for (int i = 0; i < nb; i++) flag[i] = na[i] ? 0 : 1, ds.n_affine += flag[i];
+  if (use_block_lists(ds.n_affine, nb)) {
+    std::vector<int32_t> lists[2];
+    for (int i = 0; i < nb; i++) lists[flag[i] ? 0 : 1].push_back(i);
+    for (int k = 0; k < 2; k++) ds.d_blist[k] = dev_upload(lists[k].data(), lists[k].size()), ds.n_blist[k] = (int)lists[k].size();
+  }
+  if (ds.n_affine == nb || ds.d_blist[0]) {
+    std::vector<double> wrel((size_t)p.Q4, 0.0);
+    for (int i = 0; i < Q; i++) wrel[i] = geom.wq[i] / geom.wq[0];
+    ds.d_affine = dev_upload(flag.data(), flag.size());
+    ds.d_wrel = dev_upload(wrel.data(), wrel.size());
+  }
+}
+
+}  // namespace
+
+std::unique_ptr<DenseSub> make_dense_sub(pa_geom *geom, const pa_restriction_desc &r, const pa_dense_basis_desc &given, int qf_given,
+                                         const void *ctx, size_t ctx_size, uint32_t trial_given, uint32_t test_given, int height,
+                                         bool contra_given) {
+  PA_REQUIRE(geom && geom->eb == kEB, "geometry data must come from pa_geom_create_dense");
+  // the environment switches, read at every creation (A / B runs in one process)
+  const char *e_form = getenv("PALACE_AMD_DENSE"), *e_aff = getenv("PALACE_AMD_DENSE_AFFINE"), *e_lay = getenv("PALACE_AMD_DENSE_ELAYOUT");
+  const bool staged = e_form && std::string(e_form) == "staged";  // keeps the general kernel
+  const bool affine_off = e_aff && e_aff[0] == '0';               // every block reads all of its q-data
+  const int elayout = (e_lay && std::string(e_lay) == "rows") ? 1 : (e_lay && std::string(e_lay) == "block") ? 0 : -1;
+  const bool verbose = getenv("PALACE_AMD_DENSE_VERBOSE") != nullptr;
+
+  // 1. an H(div) block becomes the block of another element type whose arithmetic it runs on
+  const DenseAlias al = resolve_alias(given.fe_type, qf_given, 10 * geom->sdim + geom->dim, trial_given, test_given,
+                                      {given.interp != nullptr, given.deriv != nullptr}, contra_given);
+  const double *const tables[3] = {nullptr, given.interp, given.deriv};
+  pa_dense_basis_desc b = given;
+  b.fe_type = al.fe_type, b.interp = tables[al.interp], b.deriv = tables[al.deriv];
+  const bool contra = al.contra;
+  // 2., 3.
+  const int mode = validate_dense(*geom, r, b, al.qf, al.trial_ops, al.test_ops, height), dim = geom->dim;
+  const ModeComps m = mode_comps(mode);
+  const DensePlan p = make_plan(r.num_elem, b.num_dofs, b.num_qpts, geom->Qpad, m);
   auto ds = std::make_unique<DenseSub>();
   ds->geom = Ref<Geom>(geom);
-  ds->fe_type = b.fe_type, ds->P = P, ds->Q = Q, ds->Qpad = geom->Qpad, ds->nch = geom->Qpad / 16;
-  ds->ne = ne, ds->nb = (ne + kEB - 1) / kEB, ds->lsize = r.lsize, ds->KP = 4 * PT, ds->PT = PT;
-  ds->qf = qf, ds->mode = mode, ds->trial_ops = trial_ops, ds->test_ops = test_ops, ds->contra = contra;
-  const int KP = ds->KP, nb = ds->nb, nch = ds->nch;
-
-  // ---- E: block-transposed index (+ packed tridiagonal rows)
-  const size_t nslot = (size_t)nb * KP * 64;
-  std::vector<int32_t> idx(nslot, kEssBit);
-  std::vector<uint16_t> co(r.curl_orients ? nslot : 0, 0u);
-  for (int e = 0; e < ne; e++) {
-    for (int d = 0; d < P; d++) {
-      const int32_t off = r.offsets[(size_t)e * P + d];
-      PA_REQUIRE(off >= 0 && off < r.lsize, "restriction offset out of range");
-      const size_t pos = ((size_t)(e / kEB) * 4 * KP + d) * kEB + (e % kEB);
-      idx[pos] = (r.orients && r.orients[(size_t)e * P + d]) ? -1 - off : off;
-      if (r.curl_orients) {
-        const int8_t *t = r.curl_orients + 3 * ((size_t)e * P + d);
-        const int8_t up = d > 0 ? t[-3 + 2] : 0, dn = d + 1 < P ? t[3 + 0] : 0;  // T[d-1][d], T[d+1][d]
-        // MFEM's ND face transformations only contain -1, 0, 1 (the reference stores them as int8,
-        // restriction.cpp:318-336); two bits per entry
-        for (int8_t v : {t[0], t[1], t[2]}) PA_REQUIRE(v >= -1 && v <= 1, "curl-orientation entries must be -1, 0 or 1");
-        co[pos] = (uint16_t)((t[0] & 3) | ((t[1] & 3) << 2) | ((t[2] & 3) << 4) | ((up & 3) << 6) | ((dn & 3) << 8));
-      }
-    }
-  }
-  ds->d_idx = dev_upload(idx.data(), nslot);
-  if (r.curl_orients) {
-    ds->d_co = dev_upload(co.data(), nslot);
-    // the resident kernel takes the words of slots 2 s, 2 s + 1 of a lane together (half the loads and registers)
-    std::vector<uint32_t> co2(nslot / 2);
-    for (size_t b = 0; b < (size_t)nb; b++)
-      for (int s2 = 0; s2 < KP / 2; s2++)
-        for (int l = 0; l < 64; l++)
-          co2[(b * (KP / 2) + s2) * 64 + l] = (uint32_t)co[(b * KP + 2 * s2) * 64 + l] | ((uint32_t)co[(b * KP + 2 * s2 + 1) * 64 + l] << 16);
-    ds->d_co2 = dev_upload(co2.data(), co2.size());
-  }
-  ds->h_co = co;
-  // transpose map for the gather form of E^T (counting sort by dof, element order preserved)
-  {
-    // Which rows the E-vector gets (DenseArgs::ye_rows) is decided by what the GATHER does with them, MEASURED here on blocks large
-    // enough for it to matter: a mesh numbered with locality in the [dof] rows (a Kuhn-split cube: consecutive elements share
-    // entities at the same local index, and neighbouring waves of the gather re-read each other's rows from L2) keeps them -- there
-    // the rows by element only cost the apply kernel its coalesced stores (+3 us of 186) -- an unstructured mesh (config 3's) reads
-    // one 64-byte sector per 8-byte entry from the [dof] rows and a third of that from the rows by element (gather of 2.18M order-3
-    // dofs: 64 -> 37 us).  The sums do not depend on the choice (same copies, same order): timing noise cannot change a result.
-    // PALACE_AMD_DENSE_ELAYOUT=rows | block overrides (read at every creation: A / B runs in one process).
-    std::vector<int32_t> tptr((size_t)r.lsize + 1, 0), tent((size_t)ne * P), ted((size_t)ne * P);
-    for (size_t k = 0; k < (size_t)ne * P; k++) tptr[(size_t)r.offsets[k] + 1]++;
-    for (int d = 0; d < r.lsize; d++) tptr[d + 1] += tptr[d];
-    {
-      std::vector<int32_t> fill(tptr.begin(), tptr.end() - 1);
-      for (int e = 0; e < ne; e++)
-        for (int d = 0; d < P; d++) ted[fill[r.offsets[(size_t)e * P + d]]++] = e * P + d;
-    }
-    auto fill_tent = [&](bool rows) {
-      for (size_t k = 0; k < (size_t)ne * P; k++) {
-        const int e = ted[k] / P, d = ted[k] % P;
-        const int32_t pos = (int32_t)ye_pos_host(rows, KP, e, d);
-        const bool flip = r.orients && r.orients[(size_t)e * P + d];
-        tent[k] = flip ? -1 - pos : pos;
-      }
-    };
-    ds->d_tptr = dev_upload(tptr.data(), tptr.size());
-    ds->d_ye = dev_alloc<double>(nslot);
-    const char *gl = getenv("PALACE_AMD_DENSE_ELAYOUT");
-    if (gl && std::string(gl) == "rows") ds->ye_rows = true;
-    else if ((gl && std::string(gl) == "block") || r.lsize < (1 << 17)) ds->ye_rows = false;
-    else {
-      PA_HIP(hipMemset(ds->d_ye, 0, nslot * sizeof(double)));
-      double t[2];
-      for (int rows = 0; rows < 2; rows++) {
-        fill_tent(rows != 0);
-        const DevBuf<int32_t> d_t = dev_upload(tent.data(), tent.size());
-        t[rows] = time_dense_gather(*ds, d_t);
-      }
-      ds->ye_rows = t[1] < 0.85 * t[0];
-      if (getenv("PALACE_AMD_DENSE_VERBOSE"))
-        std::fprintf(stderr, "[palace_amd] dense block %d elements x %d dofs: gather %.1f us by dof rows, %.1f us by element rows -> %s\n", ne,
-                     P, 1e3 * t[0], 1e3 * t[1], ds->ye_rows ? "element rows" : "dof rows");
-    }
-    fill_tent(ds->ye_rows);
-    ds->d_tent = dev_upload(tent.data(), tent.size());
-    // a block that touches few of the dofs (the surface terms of a driven problem: a few thousand boundary faces in a space of
-    // millions) adds its result through the list of the rows it has: its gather was a pass over the whole vector, 58 times per
-    // FGMRES iteration of config 3 (round 5: 3.7 % of that solve's device time)
-    if ((size_t)ne * P * 4 < (size_t)r.lsize) {
-      std::vector<int32_t> rows;
-      for (int d = 0; d < r.lsize; d++)
-        if (tptr[d + 1] > tptr[d]) rows.push_back(d);
-      ds->n_rows = (int)rows.size();
-      ds->d_rows = dev_upload(rows.data(), std::max<size_t>(rows.size(), 1));
-    }
-  }
-  ds->h_idx = std::move(idx);
-
-  // ---- B: MFMA A-operand fragments (see the header comment for the row order)
-  auto tab = [&](int cidx, int q, int p) -> double {
-    if (q >= Q || p >= P) return 0.0;
-    return cidx < nci ? b.interp[((size_t)cidx * Q + q) * P + p] : b.deriv[((size_t)(cidx - nci) * Q + q) * P + p];
-  };
-  std::vector<double> Tf((size_t)nch * KP * nct * 64), Tt((size_t)nch * 4 * nct * PT * 64);
-  {
-    const int nf = (nci > 0 ? 1 : 0) + (ncd > 0 ? 1 : 0);
-    size_t of = 0, ot = 0;
-    for (int c = 0; c < nch; c++)
-      for (int f = 0; f < nf; f++) {
-        const int nc = (nf == 2) ? (f == 0 ? nci : ncd) : nct, cb = (nf == 2 && f == 1) ? nci : 0;
-        for (int s = 0; s < KP; s++)
-          for (int t = 0; t < nc; t++)
-            for (int lane = 0; lane < 64; lane++) {
-              const int i = lane & 15, kq = lane >> 4;
-              const int pi = 4 * t + (i >> 2), gl = pi / nc, k = pi % nc;
-              Tf[of++] = tab(cb + k, 16 * c + 4 * gl + (i & 3), 4 * s + kq);
-            }
-        for (int pi = 0; pi < 4 * nc; pi++)
-          for (int pt = 0; pt < PT; pt++)
-            for (int lane = 0; lane < 64; lane++) {
-              const int i = lane & 15, kq = lane >> 4;
-              const int gl = pi / nc, k = pi % nc;
-              Tt[ot++] = tab(cb + k, 16 * c + 4 * gl + kq, 16 * pt + i);
-            }
-      }
-  }
-  ds->d_Tf = dev_upload(Tf.data(), Tf.size());
-  ds->d_Tt = dev_upload(Tt.data(), Tt.size());
-  {  // position-weighted checksums of the two tables (two sub-operators on "the same basis" are compared through them)
-    auto chk = [&](const double *t, int nc) {
-      double c = 0.0;
-      if (t)
-        for (size_t i = 0; i < (size_t)nc * Q * P; i++) c += t[i] * (double)(1 + i % 1021);
-      return c;
-    };
-    ds->chk_interp = chk(b.interp, nci), ds->chk_deriv = chk(b.deriv, ncd);
-  }
-  // plain copies for the diagonal kernel
-  if (nci) ds->d_interp = dev_upload(b.interp, (size_t)nci * Q * P);
-  if (ncd) ds->d_deriv = dev_upload(b.deriv, (size_t)ncd * Q * P);
-  ds->d_off = dev_upload(r.offsets, (size_t)ne * P);
-  ds->h_off.assign(r.offsets, r.offsets + (size_t)ne * P);
-  if (r.curl_orients) ds->d_cor = dev_upload(r.curl_orients, (size_t)3 * ne * P);
-
-  // ---- D: coefficient context(s)
-  PA_REQUIRE(ctx && ctx_size >= 16 && ctx_size % 8 == 0, "bad coefficient context");
-  ds->ctx_blob.assign((const uint8_t *)ctx, (const uint8_t *)ctx + ctx_size);
-  switch (mode) {
-    case MODE_CURL:
-    case MODE_VMASS:
-    case MODE_DIFF:
-      parse_coeff(ctx, ctx_size, 3, ds->c0, 0);
-      break;
-    case MODE_CURLMASS:
-      parse_coeff(ctx, ctx_size, 3, ds->c0, 0);
-      parse_coeff(ctx, ctx_size, 3, ds->c1, ds->c0.slots);
-      break;
-    case MODE_DIFFMASS:
-      if (contra) {  // l2mass_33: the 3 x 3 mass coefficient comes first, then the scalar one of the divergence
-        parse_coeff(ctx, ctx_size, 3, ds->c1, 0);
-        parse_coeff(ctx, ctx_size, 1, ds->c0, ds->c1.slots);
-        break;
-      }
-      parse_coeff(ctx, ctx_size, 1, ds->c0, 0);
-      parse_coeff(ctx, ctx_size, 3, ds->c1, ds->c0.slots);
-      break;
-    case MODE_MASS:
-    case MODE_CURL2:
-      parse_coeff(ctx, ctx_size, 1, ds->c0, 0);
-      break;
-    case MODE_VMASS2:
-    case MODE_DIFF2:
-      parse_coeff(ctx, ctx_size, sdim == 3 ? 3 : 2, ds->c0, 0);  // boundary elements take the 3x3 material
-      break;
-    case MODE_CURLMASS2:
-      parse_coeff(ctx, ctx_size, sdim == 3 ? 3 : 2, ds->c0, 0);
-      parse_coeff(ctx, ctx_size, 1, ds->c1, ds->c0.slots);
-      break;
-    case MODE_DIFFMASS2:
-    case MODE_DIFFMASS1:
-      if (mode == MODE_DIFFMASS1 && contra) {  // l2mass_21 | _31: the mass coefficient matrix first, then the scalar one
-        parse_coeff(ctx, ctx_size, sdim == 3 ? 3 : 2, ds->c0, 0);
-        parse_coeff(ctx, ctx_size, 1, ds->c1, ds->c0.slots);
-        break;
-      }
-      parse_coeff(ctx, ctx_size, 1, ds->c0, 0);
-      parse_coeff(ctx, ctx_size, sdim == 3 ? 3 : 2, ds->c1, ds->c0.slots);
-      break;
-    case MODE_VMASS1:
-    case MODE_DIFF1:
-      parse_coeff(ctx, ctx_size, sdim == 3 ? 3 : 2, ds->c0, 0);
-      break;
-  }
-
-  // ---- fast path: tables resident in LDS (one copy, rows in tile order, stride S) + packed D.
-  // Needs symmetric coefficients and tables that fit; PALACE_AMD_DENSE=staged keeps the general kernel.
-  {
-    auto is_sym = [](const CoeffHost &c) {
-      if (c.dim == 2) {
-        for (size_t k = 0; k + 4 <= c.mat.size(); k += 4)
-          if (c.mat[k + 1] != c.mat[k + 2]) return false;
-        return true;
-      }
-      if (c.dim != 3) return true;
-      for (size_t k = 0; k + 9 <= c.mat.size(); k += 9)
-        if (c.mat[k + 1] != c.mat[k + 3] || c.mat[k + 2] != c.mat[k + 6] || c.mat[k + 5] != c.mat[k + 7]) return false;
-      return true;
-    };
-    const int S = 16 * PT + ((PT & 1) ? 2 : 18);
-    const int rows = nch * nct * 16;
-    const size_t lds = sizeof(double) * ((size_t)rows * S + (r.curl_orients ? (size_t)8 * 4 * PT * 64 : 0));
-    const char *force = getenv("PALACE_AMD_DENSE");
-    const bool staged = force && std::string(force) == "staged";
-    // (PT <= 6: the resident kernel is not instantiated for 144 padded dofs -- a block of 97 to 144 dofs whose tables would fit,
-    // a one-component mode with few points, was given the resident form here and then refused at its first apply)
-    if (!staged && PT <= 6 && lds <= 150 * 1024 && is_sym(ds->c0) && (ds->c1.mat.empty() || is_sym(ds->c1))) {
-      const int nf = (nci > 0 ? 1 : 0) + (ncd > 0 ? 1 : 0);
-      std::vector<double> L((size_t)rows * S, 0.0);
-      for (int c = 0; c < nch; c++)
-        for (int f = 0; f < nf; f++) {
-          const int nc = (nf == 2) ? (f == 0 ? nci : ncd) : nct, cb = (nf == 2 && f == 1) ? nci : 0;
-          for (int row = 0; row < 16 * nc; row++) {
-            const int pi = row >> 2, kqp = row & 3, gl = pi / nc, k = pi % nc;
-            for (int d = 0; d < P; d++)
-              L[((size_t)(c * nct + cb) * 16 + row) * S + d] = tab(cb + k, 16 * c + 4 * gl + kqp, d);
-          }
-        }
-      ds->d_L = dev_upload(L.data(), L.size());
-      ds->L_rows = rows;
-      ds->ncq = (nci == 3 ? 6 : (nci == 2 ? 3 : nci)) + (ncd == 3 ? 6 : (ncd == 2 ? 3 : ncd));
-      const size_t nq = (size_t)nb * ds->ncq * ((Q + 3) / 4 * 4) * kEB;
-      ds->d_qdata = dev_alloc<double>(nq);
-      PA_HIP(hipMemset(ds->d_qdata, 0, sizeof(double) * nq));
-      hipDeviceProp_t prop;
-      int dev = 0;
-      PA_HIP(hipGetDevice(&dev));
-      PA_HIP(hipGetDeviceProperties(&prop, dev));
-      ds->num_cu = prop.multiProcessorCount;
-      DenseArgs a = make_args(*ds);
-      const long long n = (long long)ne * Q;
-      const dim3 grid((unsigned)((n + 255) / 256)), block(256);
-      if (dim == 1) {
-        switch (mode) {
-#define PA_QD1_CASE(MODE)                                                                          \
-  case MODE:                                                                                       \
-    if (sdim == 3)                                                                                 \
-      hipLaunchKernelGGL((dense_qdata1_kernel<MODE, 3>), grid, block, 0, nullptr, a, ds->d_qdata); \
-    else                                                                                           \
-      hipLaunchKernelGGL((dense_qdata1_kernel<MODE, 2>), grid, block, 0, nullptr, a, ds->d_qdata); \
-    break;
-          PA_QD1_CASE(MODE_MASS)
-          PA_QD1_CASE(MODE_VMASS1)
-          PA_QD1_CASE(MODE_DIFF1)
-          PA_QD1_CASE(MODE_DIFFMASS1)
-#undef PA_QD1_CASE
-        }
-      } else if (dim == 3 && mode == MODE_CURL2) {
-        hipLaunchKernelGGL((dense_qdata2_kernel<MODE_CURL2, 11>), grid, block, 0, nullptr, a, ds->d_qdata);
-      } else if (dim == 2) {
-        switch (mode) {
-#define PA_QD2_CASE(MODE)                                                                          \
-  case MODE:                                                                                       \
-    if (sdim == 3)                                                                                 \
-      hipLaunchKernelGGL((dense_qdata2_kernel<MODE, 8>), grid, block, 0, nullptr, a, ds->d_qdata); \
-    else                                                                                           \
-      hipLaunchKernelGGL((dense_qdata2_kernel<MODE, 6>), grid, block, 0, nullptr, a, ds->d_qdata); \
-    break;
-          PA_QD2_CASE(MODE_CURL2)
-          PA_QD2_CASE(MODE_VMASS2)
-          PA_QD2_CASE(MODE_CURLMASS2)
-          PA_QD2_CASE(MODE_MASS)
-          PA_QD2_CASE(MODE_DIFF2)
-          PA_QD2_CASE(MODE_DIFFMASS2)
-#undef PA_QD2_CASE
-        }
-      } else
-      switch (mode) {
-#define PA_QD_CASE(MODE) \
-  case MODE: hipLaunchKernelGGL((dense_qdata_kernel<MODE>), grid, block, 0, nullptr, a, ds->d_qdata); break;
-        PA_QD_CASE(MODE_CURL)
-        PA_QD_CASE(MODE_VMASS)
-        PA_QD_CASE(MODE_CURLMASS)
-        PA_QD_CASE(MODE_DIFF)
-        PA_QD_CASE(MODE_DIFFMASS)
-        PA_QD_CASE(MODE_MASS)
-#undef PA_QD_CASE
-      }
-      PA_HIP(hipGetLastError());
-      PA_HIP(hipStreamSynchronize(nullptr));
-      // affine blocks read one point of q-data (PALACE_AMD_DENSE_AFFINE=0: every block reads all of it)
-      const char *aff_env = getenv("PALACE_AMD_DENSE_AFFINE");
-      const size_t lds_aff = sizeof(double) * ((size_t)((Q + 3) / 4 * 4 + 31) / 32 * 32 + (size_t)rows * S +
-                                               (r.curl_orients ? (size_t)kAffWaves * 4 * PT * 64 : 0));
-      if (!(aff_env && aff_env[0] == '0') && PT <= 3 && lds_aff <= 160 * 1024 && (int)geom->wq.size() == Q && Q > 1 &&
-          geom->wq[0] != 0.0) {
-        const int Q4 = (Q + 3) / 4 * 4;
-        const DevBuf<unsigned int> d_na = dev_alloc<unsigned int>((size_t)nb);
-        PA_HIP(hipMemset(d_na, 0, sizeof(unsigned int) * nb));
-        hipLaunchKernelGGL(dense_affine_kernel, dim3((unsigned)((nb * kEB + 255) / 256)), dim3(256), 0, nullptr, nb, ds->ncq, Q,
-                           Q4, ds->d_qdata, geom->d_qw, d_na);
-        PA_HIP(hipGetLastError());
-        std::vector<unsigned int> na((size_t)nb);
-        PA_HIP(hipMemcpy(na.data(), d_na, sizeof(unsigned int) * nb, hipMemcpyDeviceToHost));
-        std::vector<uint8_t> flag((size_t)nb);
-        for (int i = 0; i < nb; i++) flag[i] = na[i] ? 0 : 1, ds->n_affine += flag[i];
-        if (ds->n_affine < nb && ds->n_affine * 4 >= nb) {  // a mesh with curved parts: the affine blocks get the affine kernel
-          std::vector<int32_t> lists[2];
-          for (int i = 0; i < nb; i++) lists[flag[i] ? 0 : 1].push_back(i);
-          for (int k = 0; k < 2; k++) ds->d_blist[k] = dev_upload(lists[k].data(), lists[k].size()), ds->n_blist[k] = (int)lists[k].size();
-        }
-        if (ds->n_affine == nb || ds->d_blist[0]) {
-          std::vector<double> wrel((size_t)Q4, 0.0);
-          for (int i = 0; i < Q; i++) wrel[i] = geom->wq[i] / geom->wq[0];
-          ds->d_affine = dev_upload(flag.data(), flag.size());
-          ds->d_wrel = dev_upload(wrel.data(), wrel.size());
-        }
-      }
-    }
+  ds->fe_type = b.fe_type, ds->P = p.P, ds->Q = p.Q, ds->Qpad = p.Qpad, ds->nch = p.nch;
+  ds->ne = p.ne, ds->nb = p.nb, ds->lsize = r.lsize, ds->KP = p.KP, ds->PT = p.PT;
+  ds->qf = al.qf, ds->mode = mode, ds->trial_ops = al.trial_ops, ds->test_ops = al.test_ops, ds->contra = contra;
+  // 4. - 7.
+  const std::vector<int32_t> ted = upload_restriction(*ds, p, r);
+  choose_elayout(*ds, p, r, ted, elayout, verbose);
+  const Tables T{b.interp, b.deriv, m, p.P, p.Q};
+  upload_tables(*ds, p, T, r);
+  parse_contexts(*ds, ctx, ctx_size);
+  // 8., 9. the fast path needs symmetric coefficients and tables that fit
+  const bool symmetric = coeff_symmetric(ds->c0.dim, ds->c0.mat) && (ds->c1.mat.empty() || coeff_symmetric(ds->c1.dim, ds->c1.mat));
+  if (!staged && resident_fits(p, r.curl_orients != nullptr, kResWaves) && symmetric) {
+    setup_resident(*ds, p, T);
+    if (!affine_off) detect_affine(*ds, p);
   }
   PA_REQUIRE((dim == 3 && mode < MODE_CURL2 && !contra) || ds->d_L,
              "2-D blocks, div-div and div-div + mass need symmetric coefficients and tables that fit in LDS (fast path only)");
   return ds;
+}
+
+// what ran is what is reported: the launchers select through this, pa_op_dense_kernel answers from it
+DenseCell dense_kernel_cell(const DenseSub &ds) {
+  if (!ds.d_L) return {false, kGeoCurved, ds.PT};
+  const bool small = ds.PT <= 3;  // (the affine and list kernels exist for these; detect_affine finds flags and lists for these only)
+  return {true, small && ds.d_blist[0] ? kGeoList : (small && ds.d_affine ? kGeoAffine : kGeoCurved), ds.PT};
 }
 
 void dense_set_essential(DenseSub &ds, const std::vector<char> &flag) {
@@ -1841,13 +1581,13 @@ bool dense_split_ok(const DenseSub &ds) {
 void launch_dense_apply(const DenseSub &ds, const double *x, bool masked, hipStream_t s, const SplitIO *split) {
   DenseArgs a = make_args(ds);
   a.x = x;
+  if (masked && ds.d_idx_bc) a.idx = ds.d_idx_bc;
   if (split) {
     PA_REQUIRE(split->n_true >= 0 && split->n_true <= ds.lsize, "split point outside the local vector");
     a.nsplit = split->n_true;
     a.xg0 = split->xg0 - split->n_true, a.xg1 = (split->xg1 ? split->xg1 : split->xg0) - split->n_true;
     a.xg_sel = split->sel;
     PA_REQUIRE(dense_split_ok(ds), "no split-vector form of this dense block");
-    if (masked && ds.d_idx_bc) a.idx = ds.d_idx_bc;
     switch (ds.PT) {
       case 1: launch_resident_split<1>(ds, a, s); break;
       case 2: launch_resident_split<2>(ds, a, s); break;
@@ -1855,8 +1595,7 @@ void launch_dense_apply(const DenseSub &ds, const double *x, bool masked, hipStr
     }
     return;
   }
-  if (masked && ds.d_idx_bc) a.idx = ds.d_idx_bc;
-  if (ds.d_L) {
+  if (dense_kernel_cell(ds).resident) {
     switch (ds.PT) {
       case 1: launch_resident_pt<1>(ds, a, s); break;
       case 2: launch_resident_pt<2>(ds, a, s); break;
@@ -1905,45 +1644,6 @@ bool dense_complex_ok(const DenseSub &dr, const DenseSub &di) {
   return dr.h_idx == di.h_idx && dr.h_co == di.h_co;  // same restriction (host compare; the callers cache the answer)
 }
 
-template <int PT>
-static void launch_resident_complex_pt(const DenseSub &dr, const DenseArgs &a, hipStream_t s) {
-  const int rows = dr.L_rows;
-  const size_t shm = sizeof(double) * ((size_t)(a.Q4 + 31) / 32 * 32 + (size_t)rows * ResidentStride<PT>::S +
-                                      (dr.d_co ? (size_t)kResWaves * 4 * PT * 64 : 0));
-  if (dr.d_blist[0] && !a.blist) {  // affine and curved blocks: one launch each on its list (they write disjoint E-vector blocks)
-    DenseArgs aa = a, ag = a;
-    aa.blist = dr.d_blist[0], aa.nblist = dr.n_blist[0];
-    ag.blist = dr.d_blist[1], ag.nblist = dr.n_blist[1], ag.affine = nullptr;
-    launch_resident_complex_pt<PT>(dr, aa, s);
-    launch_resident_complex_pt<PT>(dr, ag, s);
-    return;
-  }
-  const int nblocks = a.blist ? a.nblist : dr.nb;
-  if (nblocks == 0) return;
-  int grid = (2 * nblocks + kResWaves - 1) / kResWaves;
-  if (grid > dr.num_cu) grid = dr.num_cu;
-  static std::atomic<bool> attr_set{false};  // idempotent set-up, may race between rank threads
-  if (!attr_set) {
-    PA_HIP(hipFuncSetAttribute((const void *)dense_apply_resident_kernel<PT, MODE_CURLMASS, true, true>,
-                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    PA_HIP(hipFuncSetAttribute((const void *)dense_apply_resident_kernel<PT, MODE_CURLMASS, false, true>,
-                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    PA_HIP(hipFuncSetAttribute((const void *)dense_apply_resident_kernel<PT, MODE_CURLMASS, true, true, true>,
-                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    PA_HIP(hipFuncSetAttribute((const void *)dense_apply_resident_kernel<PT, MODE_CURLMASS, false, true, true>,
-                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    attr_set = true;
-  }
-  if (a.blist && a.affine)
-    hipLaunchKernelGGL((dense_apply_resident_kernel<PT, MODE_CURLMASS, true, true, true>), dim3(grid), dim3(64 * kResWaves), shm, s, a, rows);
-  else if (a.blist)
-    hipLaunchKernelGGL((dense_apply_resident_kernel<PT, MODE_CURLMASS, false, true, true>), dim3(grid), dim3(64 * kResWaves), shm, s, a, rows);
-  else if (a.affine)
-    hipLaunchKernelGGL((dense_apply_resident_kernel<PT, MODE_CURLMASS, true, true>), dim3(grid), dim3(64 * kResWaves), shm, s, a, rows);
-  else
-    hipLaunchKernelGGL((dense_apply_resident_kernel<PT, MODE_CURLMASS, false, true>), dim3(grid), dim3(64 * kResWaves), shm, s, a, rows);
-}
-
 void launch_dense_complex(const DenseSub &dr, const DenseSub &di, const double *xr, const double *xi, double *ye_i, hipStream_t s,
                           bool masked) {
   DenseArgs a = make_args(dr);
@@ -1953,9 +1653,9 @@ void launch_dense_complex(const DenseSub &dr, const DenseSub &di, const double *
   a.qi_mass = di.mode == MODE_CURL ? -1 : 0;
   a.qi_curl = di.mode == MODE_CURL ? 0 : (di.mode == MODE_CURLMASS ? 6 : -1);
   switch (dr.PT) {
-    case 1: launch_resident_complex_pt<1>(dr, a, s); break;
-    case 2: launch_resident_complex_pt<2>(dr, a, s); break;
-    case 3: launch_resident_complex_pt<3>(dr, a, s); break;
+    case 1: launch_resident_mode<1, MODE_CURLMASS, true, false>(dr, a, s); break;
+    case 2: launch_resident_mode<2, MODE_CURLMASS, true, false>(dr, a, s); break;
+    case 3: launch_resident_mode<3, MODE_CURLMASS, true, false>(dr, a, s); break;
     default: throw Error("complex dense kernel not instantiated for this element size");
   }
   PA_HIP(hipGetLastError());
@@ -1970,8 +1670,8 @@ void launch_dense_complex(const DenseSub &dr, const DenseSub &di, const double *
 // vectors of the step side by side (one dof per thread walked its copies one dependent load pair at a time: latency-bound; the
 // transfer gathers of pa_interp.hip got 2x from the same change).  A dof's copies are added in their order, an absent copy adds
 // an exact zero: the sums are those of the one-dof form.
-[[maybe_unused]] constexpr int kGatherWideFrom = 1 << 30;  // (DOFS = 4 is SLOWER on tetrahedra -- 46 -> 60 us, the longest of 4 x 64 rows sets a wave's
-                                         // trip count -- one dof per thread with its copies in chunks of four: 46 -> 40 us)
+// (Measured: DOFS = 4 is SLOWER on tetrahedra -- 46 -> 60 us, the longest of 4 x 64 rows sets a wave's trip count -- one dof per
+// thread with its copies in chunks of four: 46 -> 40 us.  Every launch takes DOFS = 1.)
 template <bool STEP, int DOFS = 1>
 __global__ __launch_bounds__(256) void et_gather_split_kernel_t(const int n, const int32_t *__restrict__ tptr,
                                                                 const int32_t *__restrict__ tent, const double *__restrict__ ye,

@@ -286,7 +286,6 @@ struct DenseSub {
   DevBuf<double> d_interp, d_deriv;  // plain tables (diagonal assembly)
   DevBuf<int32_t> d_off;    // plain [ne][P] offsets (diagonal assembly)
   DevBuf<int8_t> d_cor;     // plain curl_orients or nullptr
-  DevBuf<uint8_t> d_ori;
   DevBuf<double> d_ye;      // E-vector [nb][4 KP][16]
   DevBuf<int32_t> d_tptr, d_tent;
   std::vector<uint8_t> ctx_blob;
@@ -427,6 +426,14 @@ void launch_dense_apply(const DenseSub &ds, const double *x, bool masked, hipStr
 void launch_dense_gather(const DenseSub &ds, double *y, bool accumulate, hipStream_t s, const double *ye = nullptr,
                          const SplitIO *split = nullptr, const double *x = nullptr, int ess_policy = -1);
 bool dense_split_ok(const DenseSub &ds);
+// The apply kernel a dense block runs on: resident (tables in LDS) or staged, on curved / affine blocks or on the lists of a mesh
+// with both, and 16 PT padded dofs.  The launchers select through it and pa_op_dense_kernel reports it.
+enum DenseGeo { kGeoCurved = 0, kGeoAffine = 1, kGeoList = 2 };
+struct DenseCell {
+  bool resident;
+  int geo, PT;
+};
+DenseCell dense_kernel_cell(const DenseSub &ds);
 bool dense_complex_ok(const DenseSub &dr, const DenseSub &di);
 void launch_dense_gather_signed(const DenseSub &ds, double *y, double sign, bool skip_ess, hipStream_t s);
 // the fused smoother step / residual on a dense block (round 6): the CSR-form gather owns every row; its epilogue consumes the sum

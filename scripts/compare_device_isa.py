@@ -8,7 +8,7 @@ compiled to assembly with `--cuda-device-only -S` and the flags the Makefile of 
 `make -n`, so per-file flags are included).  Required per file:
   * the same set of kernel symbols,
   * for every kernel the same text from its label to `.end_amdhsa_kernel` (code and kernel descriptor; the function's position
-    in the file is taken out of its local labels),
+    in the file is taken out of its local labels and of the comments that name them),
   * for every kernel the same entry in the `amdhsa.kernels` metadata (registers, spills, scratch, LDS, kernarg size).
 Text is compared for equality only; the names of the kernels that differ are printed.  Exit status 1 on any difference.
 """
@@ -61,7 +61,9 @@ def kernels(asm):
             j += 1
         # local labels carry the function's position in the file (.LBB<function>_<block>): drop it, so that adding or removing
         # another kernel does not make every kernel after it differ
-        text[n] = re.sub(r"\.(LBB|Lfunc_end)\d+", r".\1", "\n".join(lines[start[n]:j + 1]))
+        # (the assembler's loop comments name the same blocks without the dot, `Header=BB37_3`, and are aligned behind the label)
+        text[n] = re.sub(r"(\.LBB|\.Lfunc_end|\bBB)\d+", r"\1", "\n".join(lines[start[n]:j + 1]))
+        text[n] = re.sub(r"[ \t]+;", " ;", text[n])
     # metadata: the items of the amdhsa.kernels list
     meta, i = {}, lines.index("amdhsa.kernels:") + 1
     item = []

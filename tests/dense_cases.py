@@ -18,7 +18,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 KEB = 16  # elements per block
-PTS = (1, 2, 3, 4, 6, 9)  # kPT of make_dense_sub
+PTS = (1, 2, 3, 4, 6, 9)  # kPT of pa_dense_host.hpp
 RES_PTS = (1, 2, 3, 4, 6)  # the PT switch of the resident launcher
 SMALL_PTS = (1, 2, 3)  # affine, list, split and complex kernels
 MODES = ("CURL", "VMASS", "CURLMASS", "DIFF", "DIFFMASS", "MASS", "CURL2", "VMASS2", "CURLMASS2", "DIFF2", "DIFFMASS2", "VMASS1",
@@ -34,7 +34,7 @@ MODE_INFO = {"CURL": (True, 3, 0, 3), "VMASS": (True, 3, 3, 0), "CURLMASS": (Tru
 WAVES = {"staged": 4, "curved": 8, "affine": 12}  # waves per workgroup
 
 
-# ---- the host's arithmetic (make_dense_sub) ------------------------------------------------------------------------------------
+# ---- the host's arithmetic (pa_dense_host.hpp; tests/test_dense_host.py compares the two value by value) ----------------------
 def pt_of(P):
     for v in PTS:
         if P <= 16 * v:
@@ -289,8 +289,8 @@ def compiled_apply_cells(res_modes=MODES, res_pts=RES_PTS, split_modes=SPLIT_MOD
 # A cell may stand here only when a rule of make_dense_sub or of a launcher shuts it out for EVERY input; the entry names the rule.
 # Every compiled apply cell is reachable, so the map is empty; what the rules shut out are combinations that are not compiled:
 NOT_COMPILED = {
-    "affine / list / split / complex at PT > 3": "make_dense_sub: the affine flags need PT <= 3; launch_resident_pt: `affine = a.affine && PT <= 3`, "
-                                                 "LIST = (PT <= 3); dense_split_ok and dense_complex_ok: PT <= 3",
+    "affine / list / split / complex at PT > 3": "affine_fits: the affine flags need PT <= 3; dense_kernel_cell and launch_resident_mode: "
+                                                 "SMALL = PT <= 3; dense_split_ok and dense_complex_ok: PT <= 3",
     "2-D and line modes in the staged form": "make_dense_sub: PA_REQUIRE((dim == 3 && mode < MODE_CURL2 && !contra) || d_L); PA_DENSE_CASE lists the "
                                              "six 3-D modes",
     "resident form at PT = 9": "make_dense_sub keeps blocks of more than 96 dofs on the staged kernel: launch_dense_apply has no resident case 9",

@@ -1,8 +1,9 @@
 """Keeps the case table of the dense MFMA element kernels (tests/dense_cases.py, run on the GPU by tests/test_dense_cells_gpu.py) in
 step with the instantiations palace_amd/csrc/pa_dense.hip compiles: every (form, PT, mode, geometry form) a launcher can start, and
 every set-up and diagonal kernel, must have a case or stand in EXCLUDED with the rule that shuts it out.  And the inputs of every
-case are built here and pushed through the host's arithmetic (restated in dense_cases.py), so that a case whose stated cell is not
-the one make_dense_sub will choose fails without a GPU.  CPU only."""
+case are built here and pushed through the host's arithmetic as dense_cases.py states it (tests/test_dense_host.py holds that
+statement to palace_amd/csrc/pa_dense_host.hpp, value by value), so that a case whose stated cell is not the one make_dense_sub
+will choose fails without a GPU.  CPU only."""
 import os
 import re
 
@@ -13,8 +14,8 @@ from tests import dense_cases as dc
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _src():
-    with open(os.path.join(ROOT, "palace_amd", "csrc", "pa_dense.hip")) as f:
+def _src(name="pa_dense.hip"):
+    with open(os.path.join(ROOT, "palace_amd", "csrc", name)) as f:
         return f.read()
 
 
@@ -24,17 +25,19 @@ def _modes(src, macro):
 
 
 def _parse():
-    src = _src()
+    src, host = _src(), _src("pa_dense_host.hpp")  # (the modes and the element sizes live in the host header)
     P = {}
-    enum = re.search(r"enum DenseMode \{(.*?)\};", src, re.S).group(1)
+    enum = re.search(r"enum DenseMode \{(.*?)\};", host, re.S).group(1)
     P["enum"] = [(n, int(v)) for n, v in re.findall(r"MODE_(\w+) = (\d+)", enum)]
-    P["kPT"] = [int(v) for v in re.search(r"static const int kPT\[\] = \{([^}]*)\}", src).group(1).split(",")]
+    P["kPT"] = [int(v) for v in re.search(r"constexpr int kPT\[\] = \{([^}]*)\}", host).group(1).split(",")]
     for macro in ("PA_RES_CASE", "PA_RES_SPLIT_CASE", "PA_DENSE_CASE", "PA_QD1_CASE", "PA_QD2_CASE", "PA_QD_CASE", "PA_DIAG_CASE",
                   "PA_DIAG2_CASE"):
         P[macro] = _modes(src, macro)
     P["res_pt"] = [int(v) for v in re.findall(r"case (\d+): launch_resident_pt<\1>\(ds, a, s\)", src)]
     P["split_pt"] = sorted({int(v) for v in re.findall(r"launch_resident_split<(\d+)>\(ds, a, s\)", src)})
-    P["cplx_pt"] = [int(v) for v in re.findall(r"case (\d+): launch_resident_complex_pt<\1>\(dr, a, s\)", src)]
+    P["cplx_pt"] = [int(v) for v in re.findall(r"case (\d+): launch_resident_mode<\1, MODE_CURLMASS, true, false>\(dr, a, s\)", src)]
+    # the one launch helper: every resident instantiation is one of the four geometry forms launch_resident_mode names
+    P["cell_forms"] = re.findall(r"launch_resident_cell<PT, MODE, (\w+), CPLX, (\w+), SPLIT>", src)
     P["staged_pt"] = [int(v) for v in re.findall(r"case (\d+): launch_pt<\1>\(ds, a, s\)", src)]
     P["qd1_sdim"] = sorted({int(v) for v in re.findall(r"dense_qdata1_kernel<MODE, (\d+)>", src)})
     P["qd2_rows"] = sorted({int(v) for v in re.findall(r"dense_qdata2_kernel<MODE, (\d+)>", src)})
@@ -82,12 +85,11 @@ def test_the_source_lists_are_found_and_are_the_expected_ones():
     # resident 5 x 14 curved + 3 x 14 x {affine, list}, split 3 x 4 x 2, complex 3 x 3, staged 6 x 6
     assert len(apply_cells) == 70 + 84 + 24 + 9 + 36
     assert len(setup) == 6 + 8 + 12 + 1 + 6 + 10
-    # the host's arithmetic that dense_cases.py restates
+    # the forms compiled_apply_cells counts per (PT, mode): affine-list and curved-list (PT <= 3), affine (PT <= 3), curved
+    assert P["cell_forms"] == [("SMALL", "SMALL"), ("false", "SMALL"), ("SMALL", "false"), ("false", "false")]
+    assert "constexpr bool SMALL = PT <= 3;" in P["src"] and "if constexpr (!SPLIT)" in P["src"]
+    # (the host's arithmetic that dense_cases.py restates is compared value by value in tests/test_dense_host.py)
     src = P["src"]
-    assert "const int S = 16 * PT + ((PT & 1) ? 2 : 18);" in src and "static constexpr int S = 16 * PT + ((PT & 1) ? 2 : 18);" in src
-    assert "(r.curl_orients ? (size_t)8 * 4 * PT * 64 : 0)" in src and "(r.curl_orients ? (size_t)kAffWaves * 4 * PT * 64 : 0)" in src
-    assert "if (!staged && PT <= 6 && lds <= 150 * 1024 && is_sym(ds->c0)" in src and "PT <= 3 && lds_aff <= 160 * 1024" in src
-    assert "ds->n_affine < nb && ds->n_affine * 4 >= nb" in src
     assert "constexpr int kDenseWaves = 4;" in src and "constexpr int kResWaves = 8;" in src and "constexpr int kAffWaves = 12;" in src
     assert dc.WAVES == {"staged": 4, "curved": 8, "affine": 12}
 
