@@ -526,6 +526,58 @@ int pa_interp_create_refinement(pa_context *ctx, const pa_restriction_desc *doma
 int pa_interp_mult(pa_interp *P, const double *x_coarse, double *y_fine);
 int pa_interp_mult_transpose(pa_interp *P, const double *x_fine, double *y_coarse);
 void pa_interp_destroy(pa_interp *P);
+/* An assembled rectangular operator [nrows x ncols] behind the same handle (Mult only: pa_interp_mult): a discrete curl or a
+ * transfer that some other code assembled.  `csr` stays owned by the caller and must outlive the handle. */
+int pa_interp_create_csr(pa_context *ctx, const pa_csr *csr, pa_interp **P);
+
+/* --- transient solves: the first-order system of models/timeoperator.cpp:22-282 advanced by the generalized-alpha stepper
+ *     (rho_inf = 1 in the reference, :317-322) on the state u = (dE/dt, E, B), one device allocation with the blocks at offsets
+ *     0, nE and 2 nE (palace_amd/csrc/timeoperator.hpp: palace::TimeOperator).  One step: one apply of K, of C and of Curl, one
+ *     solve with A = M + a C + a^2 K, four element-wise launches (five when rho_inf != 1). -------------------------------------- */
+typedef struct pa_time_op pa_time_op;
+/* the excitation pulses of utils/excitations.hpp: g(t) and g'(t).  t0 is the delay the caller chooses (the reference's driver
+ * takes 4.5 tau for the three Gaussian shapes, 0 otherwise: drivers/transientsolver.cpp:135-138) */
+enum pa_pulse_kind {
+  PA_PULSE_SINUSOIDAL = 0,    /* sin(omega (t - t0)) */
+  PA_PULSE_GAUSSIAN = 1,      /* exp(-(t - t0)^2 / (2 tau^2)) */
+  PA_PULSE_DIFF_GAUSSIAN = 2, /* -(t - t0) / tau^2 exp(-(t - t0)^2 / (2 tau^2)) */
+  PA_PULSE_MOD_GAUSSIAN = 3,  /* sin(omega (t - t0)) exp(-(t - t0)^2 / (2 tau^2)) */
+  PA_PULSE_RAMP = 4,          /* 0, (t - t0) / tau, 1 */
+  PA_PULSE_SMOOTH_STEP = 5    /* 6 s^5 - 15 s^4 + 10 s^3 with s the ramp */
+};
+typedef struct {
+  int kind;
+  double omega, tau, t0;
+} pa_pulse_desc;
+int pa_pulse_eval(const pa_pulse_desc *pulse, double t, double *value, double *derivative); /* either output may be NULL */
+/* a = alpha_f gamma / alpha_m dt: the factor of A(a) = M + a C + a^2 K that a step of size dt solves with (dt / 2 for
+ * rho_inf = 1); call it first, build A(a) and its solver, then create the stepper */
+int pa_time_op_stage_factor(double rho_inf, double dt, double *a);
+/* K, C (or NULL): ParOperators with DIAG_ZERO on the essential rows; Curl: nB x nE; M_solver: solves with M (DIAG_ONE; Jacobi-PCG
+ * in the reference); A_solver: solves with A(a) for the stage factor above (its solution vector is reused as the starting
+ * iterate from step to step); negJ (or NULL: no source): the excitation vector [nE], device memory, copied; pulse: its time
+ * dependence (g' multiplies negJ).  dt is fixed for the life of the object, as in the reference's driver.  Nothing is owned. */
+int pa_time_op_create(pa_context *ctx, pa_par_op *K, pa_par_op *C, pa_interp *Curl, pa_solver *M_solver, pa_solver *A_solver,
+                      const double *negJ, const pa_pulse_desc *pulse, double rho_inf, double dt, pa_time_op **T);
+int pa_time_op_init(pa_time_op *T); /* zero state; the next step starts a new integration */
+/* any other initial state (the reference always starts from zero); device pointers, copied */
+int pa_time_op_set_state(pa_time_op *T, const double *Edot, const double *E, const double *B);
+int pa_time_op_step(pa_time_op *T, double *t); /* t -> t + dt */
+/* device pointers to the three blocks and their sizes; `derivative`: the stepper's du/dt in the same layout; `guard`: the number
+ * of doubles the object keeps untouched in front of Edot and behind B (and around the derivative).  Outputs may be NULL. */
+int pa_time_op_state(const pa_time_op *T, const double **Edot, const double **E, const double **B, int *nE, int *nB,
+                     const double **derivative, int *guard);
+/* what ran since creation (the first step of an integration adds one apply of K, C and Curl, one solve with M and three
+ * element-wise launches for du/dt = f(u)) */
+typedef struct {
+  long long steps, k_applies, c_applies, curl_applies, a_solves, m_solves, a_iterations, m_iterations, ew_launches,
+      predictor_launches;
+} pa_time_op_stats_t;
+int pa_time_op_stats(const pa_time_op *T, pa_time_op_stats_t *stats);
+/* *intact = 1 when the guard doubles around every allocation of the object (state, derivative, stage vectors, work vectors) still
+ * hold the bits written at creation; waits for the stream (tests) */
+int pa_time_op_guards_intact(const pa_time_op *T, int *intact);
+void pa_time_op_destroy(pa_time_op *T);
 
 #ifdef __cplusplus
 }

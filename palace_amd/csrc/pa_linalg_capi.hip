@@ -8,6 +8,7 @@
 #include "amg_solver.hpp"
 #include "ksp.hpp"
 #include "linalg.hpp"
+#include "timeoperator.hpp"
 
 using namespace palace;
 
@@ -1374,5 +1375,118 @@ int pa_interp_mult_transpose(pa_interp *P, const double *x, double *y) {
   });
 }
 void pa_interp_destroy(pa_interp *P) { delete P; }
+int pa_interp_create_csr(pa_context *ctx, const pa_csr *csr, pa_interp **P) {
+  return guarded([&] {
+    PA_REQUIRE(ctx && csr && P, "null argument");
+    auto p = std::make_unique<pa_interp>();
+    p->ctx = ctx;
+    p->op = std::make_unique<CsrOperator>(ctx->ctx, csr);
+    *P = p.release();
+  });
+}
+
+/* --- transient solves -------------------------------------------------------------------------- */
+struct pa_time_op {
+  pa_context *ctx;
+  Vector negJ;  // a copy of the caller's excitation vector
+  pa_pulse_desc pulse;
+  double dt;
+  std::unique_ptr<TimeOperator> op;
+};
+
+int pa_pulse_eval(const pa_pulse_desc *pulse, double t, double *value, double *derivative) {
+  return guarded([&] {
+    PA_REQUIRE(pulse, "null argument");
+    if (value) *value = PulseValue(pulse->kind, pulse->omega, pulse->tau, pulse->t0, t);
+    if (derivative) *derivative = PulseDerivative(pulse->kind, pulse->omega, pulse->tau, pulse->t0, t);
+  });
+}
+int pa_time_op_stage_factor(double rho_inf, double dt, double *a) {
+  return guarded([&] {
+    PA_REQUIRE(a, "null argument");
+    *a = TimeOperator::StageFactor(rho_inf, dt);
+  });
+}
+int pa_time_op_create(pa_context *ctx, pa_par_op *K, pa_par_op *C, pa_interp *Curl, pa_solver *M_solver, pa_solver *A_solver,
+                      const double *negJ, const pa_pulse_desc *pulse, double rho_inf, double dt, pa_time_op **T) {
+  return guarded([&] {
+    PA_REQUIRE(ctx && K && Curl && M_solver && A_solver && T, "null argument");
+    PA_REQUIRE(!negJ || pulse, "an excitation vector needs its pulse");
+    PA_REQUIRE(dt > 0.0, "the time step must be positive");
+    auto t = std::make_unique<pa_time_op>();
+    t->ctx = ctx, t->dt = dt;
+    t->pulse = pulse ? *pulse : pa_pulse_desc{PA_PULSE_SINUSOIDAL, 0.0, 0.0, 0.0};
+    const int nE = K->op->Height();
+    if (negJ) {
+      t->negJ.SetSize(nE);
+      Vector src(const_cast<double *>(negJ), nE);
+      linalg::Copy(ctx->ctx, src, t->negJ);
+    }
+    const pa_pulse_desc pd = t->pulse;
+    auto dJ = [pd](double time) { return PulseDerivative(pd.kind, pd.omega, pd.tau, pd.t0, time); };
+    // the C ABI keeps dt fixed, as the reference's driver does: A_solver was built for pa_time_op_stage_factor(rho_inf, dt), and a
+    // step that asks for another factor is refused
+    const double a0 = TimeOperator::StageFactor(rho_inf, dt);
+    pa_time_op *raw = t.get();
+    Solver *As = A_solver->solver.get();
+    auto configure = [raw, As, a0](double a) {
+      PA_REQUIRE(a == a0, "the stage factor differs from the one the solver of A was built for");
+      raw->op->SetLinearSolver(*As);
+    };
+    t->op = std::make_unique<TimeOperator>(ctx->ctx, K->op.get(), C ? C->op.get() : nullptr, nullptr, *Curl->op, t->negJ, dJ, rho_inf,
+                                           TimeOperator::LinearSolve(*M_solver->solver), configure);
+    *T = t.release();
+  });
+}
+int pa_time_op_init(pa_time_op *T) {
+  return guarded([&] {
+    PA_REQUIRE(T, "null argument");
+    T->op->Init();
+  });
+}
+int pa_time_op_set_state(pa_time_op *T, const double *Edot, const double *E, const double *B) {
+  return guarded([&] {
+    PA_REQUIRE(T && Edot && E && B, "null argument");
+    Vector v1(const_cast<double *>(Edot), T->op->SizeE()), v2(const_cast<double *>(E), T->op->SizeE()),
+        v3(const_cast<double *>(B), T->op->SizeB());
+    T->op->SetState(v1, v2, v3);
+  });
+}
+int pa_time_op_step(pa_time_op *T, double *t) {
+  return guarded([&] {
+    PA_REQUIRE(T && t, "null argument");
+    double dt = T->dt;
+    T->op->Step(*t, dt);
+  });
+}
+int pa_time_op_state(const pa_time_op *T, const double **Edot, const double **E, const double **B, int *nE, int *nB,
+                     const double **derivative, int *guard) {
+  return guarded([&] {
+    PA_REQUIRE(T, "null argument");
+    const double *u = T->op->State();
+    if (Edot) *Edot = u;
+    if (E) *E = u + T->op->SizeE();
+    if (B) *B = u + 2LL * T->op->SizeE();
+    if (nE) *nE = T->op->SizeE();
+    if (nB) *nB = T->op->SizeB();
+    if (derivative) *derivative = T->op->StateDot();
+    if (guard) *guard = TimeOperator::kGuard;
+  });
+}
+int pa_time_op_stats(const pa_time_op *T, pa_time_op_stats_t *stats) {
+  return guarded([&] {
+    PA_REQUIRE(T && stats, "null argument");
+    const TimeOperator::Stats &s = T->op->GetStats();
+    *stats = {s.steps, s.k_applies, s.c_applies, s.curl_applies, s.a_solves, s.m_solves, s.a_iterations, s.m_iterations,
+              s.ew_launches, s.predictor_launches};
+  });
+}
+int pa_time_op_guards_intact(const pa_time_op *T, int *intact) {
+  return guarded([&] {
+    PA_REQUIRE(T && intact, "null argument");
+    *intact = T->op->GuardsIntact() ? 1 : 0;
+  });
+}
+void pa_time_op_destroy(pa_time_op *T) { delete T; }
 
 }  // extern "C"

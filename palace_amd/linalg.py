@@ -1273,3 +1273,140 @@ class ComplexGmg(ComplexSmoother):
         v = (C.c_double * 2)()
         _lib.check(_L().pa_complex_gmg_smoother_lambda_max(self.handle, int(level), v))
         return v[0], v[1]
+
+
+class CsrInterp(Interp):
+    """An assembled rectangular operator behind the Interp handle (pa_interp_create_csr): `csr` is a ceed.DeviceCsr, for instance
+    a discrete curl that some other code assembled.  mult only: the assembled operator has no transposed product."""
+
+    def __init__(self, ctx, csr):
+        self.ctx, self.csr = ctx, csr
+        self.handle = C.c_void_p()
+        _lib.check(_L().pa_interp_create_csr(ctx.handle, csr.handle, C.byref(self.handle)))
+
+    def mult_transpose(self, x, y):
+        raise NotImplementedError("CsrInterp applies the assembled operator only (mult)")
+
+
+PULSE_KINDS = {"sinusoidal": 0, "gaussian": 1, "diff_gaussian": 2, "mod_gaussian": 3, "ramp": 4, "smooth_step": 5}
+
+
+class PulseDesc(C.Structure):
+    """pa_pulse_desc: one of the excitation shapes of utils/excitations.hpp; t0 is the delay (4.5 tau for the Gaussian shapes in
+    the reference's driver, drivers/transientsolver.cpp:135-138)."""
+    _fields_ = [("kind", C.c_int), ("omega", C.c_double), ("tau", C.c_double), ("t0", C.c_double)]
+
+    def eval(self, t):
+        """(g(t), g'(t)) through the library (pa_pulse_eval)."""
+        v, d = C.c_double(), C.c_double()
+        _lib.check(_L().pa_pulse_eval(C.byref(self), C.c_double(t), C.byref(v), C.byref(d)))
+        return v.value, d.value
+
+
+def pulse(kind, omega=0.0, tau=0.0, t0=None):
+    k = PULSE_KINDS[kind]
+    if t0 is None:
+        t0 = 4.5 * tau if k in (1, 2, 3) else 0.0
+    return PulseDesc(k, float(omega), float(tau), float(t0))
+
+
+class _TimeOpStats(C.Structure):
+    _fields_ = [(n, C.c_longlong) for n in ("steps", "k_applies", "c_applies", "curl_applies", "a_solves", "m_solves",
+                                            "a_iterations", "m_iterations", "ew_launches", "predictor_launches")]
+
+
+def time_op_stage_factor(rho_inf, dt):
+    """a = alpha_f gamma / alpha_m dt of the generalized-alpha stepper: the factor in A(a) = M + a C + a^2 K (dt / 2 for rho_inf = 1)."""
+    a = C.c_double()
+    _lib.check(_L().pa_time_op_stage_factor(C.c_double(rho_inf), C.c_double(dt), C.byref(a)))
+    return a.value
+
+
+class TimeOperator:
+    """palace::TimeOperator (palace_amd/csrc/timeoperator.hpp) through pa_time_op_*: the state (dE/dt, E, B) advanced by the
+    generalized-alpha stepper.  K, C (or None): ParOperators with DIAG_ZERO; curl: an Interp (nB x nE); m_solver / a_solver:
+    Solvers of M (DIAG_ONE) and of A(a) = M + a C + a^2 K with a = time_op_stage_factor(rho_inf, dt); neg_j: the excitation
+    vector (CUDA tensor, copied) with its PulseDesc, or None."""
+
+    def __init__(self, ctx, K, C_op, curl, m_solver, a_solver, neg_j=None, pulse_desc=None, rho_inf=1.0, dt=1.0):
+        self.ctx, self._keep = ctx, (K, C_op, curl, m_solver, a_solver)
+        self.dt, self.rho_inf, self.t = float(dt), float(rho_inf), 0.0
+        self.handle = C.c_void_p()
+        L = _L()
+        L.pa_time_op_create.argtypes = [C.c_void_p] * 8 + [C.c_double, C.c_double, C.c_void_p]
+        L.pa_time_op_destroy.restype = None
+        L.pa_time_op_destroy.argtypes = [C.c_void_p]
+        _lib.check(L.pa_time_op_create(ctx.handle, K.handle, C_op.handle if C_op is not None else None, curl.handle,
+                                       m_solver.handle, a_solver.handle,
+                                       C.c_void_p(neg_j.data_ptr()) if neg_j is not None else None,
+                                       C.cast(C.pointer(pulse_desc), C.c_void_p) if pulse_desc is not None else None,
+                                       self.rho_inf, self.dt, C.byref(self.handle)))
+        p = [C.c_void_p() for _ in range(4)]
+        nE, nB, g = C.c_int(), C.c_int(), C.c_int()
+        _lib.check(L.pa_time_op_state(self.handle, C.byref(p[0]), C.byref(p[1]), C.byref(p[2]), C.byref(nE), C.byref(nB),
+                                      C.byref(p[3]), C.byref(g)))
+        self.nE, self.nB, self.guard = nE.value, nB.value, g.value
+        self._state_ptr, self._dot_ptr = p[0].value, p[3].value
+
+    def _view(self, ptr, count):
+        import torch
+
+        class _V:
+            __cuda_array_interface__ = dict(shape=(count,), typestr="<f8", data=(ptr, False), version=2)
+
+        return torch.as_tensor(_V(), device="cuda")
+
+    def state(self, with_guards=False):
+        """The state allocation as a CUDA tensor that aliases it: [dE/dt | E | B], with the guard doubles on either side on request."""
+        g = self.guard if with_guards else 0
+        return self._view(self._state_ptr - 8 * g, 2 * self.nE + self.nB + 2 * g)
+
+    def state_dot(self, with_guards=False):
+        g = self.guard if with_guards else 0
+        return self._view(self._dot_ptr - 8 * g, 2 * self.nE + self.nB + 2 * g)
+
+    @property
+    def Edot(self):
+        return self.state()[: self.nE]
+
+    @property
+    def E(self):
+        return self.state()[self.nE : 2 * self.nE]
+
+    @property
+    def B(self):
+        return self.state()[2 * self.nE :]
+
+    def init(self, t=0.0):
+        _lib.check(_L().pa_time_op_init(self.handle))
+        self.t = float(t)
+
+    def set_state(self, edot, e, b, t=0.0):
+        assert edot.numel() == self.nE and e.numel() == self.nE and b.numel() == self.nB
+        _lib.check(_L().pa_time_op_set_state(self.handle, C.c_void_p(edot.data_ptr()), C.c_void_p(e.data_ptr()),
+                                             C.c_void_p(b.data_ptr())))
+        self.t = float(t)
+
+    def step(self):
+        t = C.c_double(self.t)
+        _lib.check(_L().pa_time_op_step(self.handle, C.byref(t)))
+        self.t = t.value
+        return self.t
+
+    def guards_intact(self):
+        """True when the guard doubles around every allocation of the stepper (state, derivative, stage and work vectors) still
+        hold the bits written at creation (pa_time_op_guards_intact; waits for the stream)."""
+        ok = C.c_int()
+        _lib.check(_L().pa_time_op_guards_intact(self.handle, C.byref(ok)))
+        return bool(ok.value)
+
+    def stats(self):
+        s = _TimeOpStats()
+        _lib.check(_L().pa_time_op_stats(self.handle, C.byref(s)))
+        return {n: int(getattr(s, n)) for n, _ in _TimeOpStats._fields_}
+
+    def __del__(self):
+        try:
+            _L().pa_time_op_destroy(self.handle)
+        except Exception:
+            pass
